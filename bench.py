@@ -33,7 +33,17 @@ as the timed baseline) on one single-threaded process per host core
 received words the GPU decoded, bounded in time (rank 0, N=1 only).  The
 decisions of both are compared over the whole sample.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run measures the headline only: it sets up the C2 batch, warms up,
+times --steps decodes and prints the line.  --full adds everything else this
+file measures or checks (the R=1.3 and double-precision C2 companions, C3 and
+its variants, C4, the notebook geometry, C5, and the CPU baselines with their
+decision comparisons); the --no-* switches and the batch / step options of
+those lines act under --full only.  --dump-outputs DIR writes what the last
+timed step returned to its caller (MAP section indices, stopping iterations,
+error counters) as DIR/<name>.npy; the inputs are a function of the arguments
+alone, so two builds can be compared output for output.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        N>1 without a launcher's environment: bench.py starts its N ranks
        itself (ldpc_sparc_amd.launch, one process per GPU, no PyTorch) before
        touching the GPU, and exits non-zero when fewer than N GPUs are
@@ -103,6 +113,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the companion lines (C2 at R=1.3 and in f64, C3, C4, notebook, C5) and the CPU "
+                         "baselines; without it only the headline C2 line is set up, timed and printed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed C2 step (map_idx, t_final, error_counts) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--rate", type=float, default=1.5)
     ap.add_argument("--t-max", type=int, default=25)
@@ -137,8 +152,9 @@ def parse():
                     help="launch/rendezvous only (no GPU): rank 0 prints the ranks that joined")
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
     ap.add_argument("--seed", type=int, default=1, help="Philox key of the synthetic inputs (stream = rank)")
-    ap.add_argument("--detail-dir", default="profiles",
-                    help="directory of bench_detail_<libsha>.json, the full per-configuration record")
+    ap.add_argument("--detail-dir", default=os.path.join("build", "bench"),
+                    help="directory of bench_detail_<libsha>.json, the full per-configuration record (default: the "
+                         "git-ignored build/bench, so a run never rewrites the records committed under profiles/)")
     return ap.parse_args()
 
 
@@ -1036,7 +1052,7 @@ def main():
                                  f"expected {d.world}\n")
                 sys.exit(2)
     procs = args.cpu_procs or 0
-    if d.rank == 0 and d.world == 1 and args.cpu_seconds > 0 and not procs:
+    if args.full and d.rank == 0 and d.world == 1 and args.cpu_seconds > 0 and not procs:
         from oracle import cpu_pool
         procs = cpu_pool.host_cores()
 
@@ -1151,7 +1167,26 @@ def main():
                 "bit_errors": int(cnt[1]), "codeword_errors": int(cnt[2]),
                 "ber": float(cnt[1]) / (d.world * st["B"] * st["L"] * st["logM"])},
     }
+    if args.dump_outputs and d.rank == 0:
+        dump_outputs(args.dump_outputs, st, cnt, tf)
+    if args.full:
+        companions(args, d, comm, st, out, procs)
+    finish(args, d, comm, out)
 
+
+def dump_outputs(path, st, cnt, tf):
+    """--dump-outputs: what the last timed step handed back (sg_amp_decode_device's MAP section indices and
+    stopping iterations, sg_amp_count_errors_device's counters after the all-reduce) as <path>/<name>.npy.  The
+    integers are exact in the float types (indices < M, iterations <= t_max in float32; counters in float64)."""
+    os.makedirs(path, exist_ok=True)
+    gmap = st["d_map"].download(np.zeros((st["B"], st["L"]), np.int32))
+    np.save(os.path.join(path, "map_idx.npy"), gmap.astype(np.float32))
+    np.save(os.path.join(path, "t_final.npy"), tf.astype(np.float32))
+    np.save(os.path.join(path, "error_counts.npy"), cnt.astype(np.float64))
+
+
+def companions(args, d, comm, st, out, procs):
+    """--full: every line beside the headline, and the CPU baselines (rank 0 of a single-GPU run), added to `out`."""
     cpu_on = d.rank == 0 and d.world == 1 and args.cpu_seconds > 0
     if not args.no_r13:
         out["amp_r13"] = amp_decodable(args, d, comm, 0.75 * args.cpu_seconds if cpu_on else 0, procs)
@@ -1234,6 +1269,9 @@ def main():
         out["cpu_baseline"] = amp_cpu_baseline(st, args, args.cpu_seconds, procs)
         if not args.no_bp:
             out["bp"]["cpu_baseline"] = bp_cpu_baseline(bst, 0.4 * args.cpu_seconds, procs)
+
+
+def finish(args, d, comm, out):
     out["summary"] = summary(out)
     if d.rank == 0:
         line = compact_line(out, write_detail(out, args.detail_dir))

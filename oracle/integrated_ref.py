@@ -15,7 +15,7 @@ Follows, function by function:
     :411-439, integrated_decoder :472-502, integrated_decoder_posteriors
     :675-705, with eta :709-735 and eta_posteriors :793-822.
 
-Pinned against tests/golden/integrated_golden.npz (made by running the
+Pinned against tests/golden/integrated_golden_p*.npz (made by running the
 reference, tests/golden/make_golden_integrated.py) in tests/test_oracle_pin.py.
 Used only by tests/ as the checker.  Never imported by the product.
 """

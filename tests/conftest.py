@@ -8,6 +8,21 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 
+def _golden_parts(name):
+    """A fixture stored as tests/golden/<name>_p<k>.npz parts (each under the 1 MiB limit for a committed file,
+    tests/golden/golden_parts.py), merged into one name -> array mapping."""
+    import glob
+    import numpy as np
+    paths = sorted(glob.glob(os.path.join(REPO, "tests", "golden", name + "_p*.npz")))
+    if not paths:
+        raise FileNotFoundError(f"tests/golden/{name}_p*.npz")
+    out = {}
+    for path in paths:
+        with np.load(path) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (run with -m gpu on the GPU box)")
     config.addinivalue_line("markers", "slow: long-running statistical test")
@@ -15,8 +30,7 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def ldpc_golden():
-    import numpy as np
-    return np.load(os.path.join(REPO, "tests", "golden", "ldpc_golden.npz"))
+    return _golden_parts("ldpc_golden")
 
 
 @pytest.fixture(scope="session")
@@ -32,8 +46,7 @@ def oracle_built():
 
 @pytest.fixture(scope="session")
 def sparc_golden():
-    import numpy as np
-    return np.load(os.path.join(REPO, "tests", "golden", "sparc_golden.npz"))
+    return _golden_parts("sparc_golden")
 
 
 @pytest.fixture(scope="session")
@@ -44,8 +57,7 @@ def sophie_golden():
 
 @pytest.fixture(scope="session")
 def integrated_golden():
-    import numpy as np
-    return np.load(os.path.join(REPO, "tests", "golden", "integrated_golden.npz"))
+    return _golden_parts("integrated_golden")
 
 
 @pytest.fixture(scope="session")

@@ -75,8 +75,9 @@ def make_ldpc():
                         out[key + "_app"] = np.array(apps)
                     else:
                         out[key + "_hard"] = (np.array(apps) < 0).astype(np.uint8)
-    np.savez_compressed(os.path.join(HERE, "ldpc_golden.npz"), **out)
-    print("wrote ldpc_golden.npz", sum(v.nbytes for v in out.values()) / 1e6, "MB raw")
+    import golden_parts
+    golden_parts.save_parts("ldpc_golden", out)
+    print("wrote ldpc_golden_p*.npz", sum(v.nbytes for v in out.values()) / 1e6, "MB raw")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 """SPARC fixtures from the reference (sparc_public and sparc_sophie), written to
-tests/golden/sparc_golden.npz and tests/golden/sophie_golden.npz.
+tests/golden/sparc_golden_p*.npz and tests/golden/sophie_golden.npz.
 
 Build-container only (imports /root/reference via ref_harness).  The hooks
 wrap reference functions to record what the reference computed:
@@ -98,8 +98,9 @@ def make_sparc():
     out["pa_16"] = sparc.pa_iterative(15.0, 1.0, 16, 1.4)
     out["sc_6_32"] = sparc.sc_basic(np.array(15.0), 6, 32)
     out["scpa_2_4_q"] = sparc.sc_basic(sparc.pa_iterative(15.0, 1.0, 2, 0.96), 2, 4)
-    np.savez_compressed(os.path.join(HERE, "sparc_golden.npz"), **out)
-    print("wrote sparc_golden.npz", sum(v.nbytes for v in out.values()) / 1e6, "MB raw")
+    import golden_parts
+    golden_parts.save_parts("sparc_golden", out)
+    print("wrote sparc_golden_p*.npz", sum(v.nbytes for v in out.values()) / 1e6, "MB raw")
 
 
 def make_sophie():

@@ -199,6 +199,17 @@ def _bench_module():
     return m
 
 
+def test_full_and_dump_outputs_are_opt_in(monkeypatch):
+    """A plain run times the headline only: --full and --dump-outputs are off unless given."""
+    b = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
 def test_summary_is_compact_and_last_key_material():
     """The line's closing "summary" repeats every configuration's value,
     roofline fraction and CPU decision match in a few hundred bytes (a log that

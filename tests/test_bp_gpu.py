@@ -1,5 +1,5 @@
 """GPU parity tests of the batched BP kernels (bp.hip) through the C ABI,
-against the reference vectors (tests/golden/ldpc_golden.npz, produced by the
+against the reference vectors (tests/golden/ldpc_golden_p*.npz, produced by the
 reference's own c_ldpc.c) and the CPU restatement oracle/bp_oracle.c.
 
 Bars: double-precision min-sum is bit-identical to the (index-corrected)

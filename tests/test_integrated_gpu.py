@@ -1,6 +1,6 @@
 """GPU parity tests of the AMP <-> BP integrated decoders (integrated.hip,
 sg_integrated_decode) against the reference's outputs
-(tests/golden/integrated_golden.npz, made by running the reference) and the
+(tests/golden/integrated_golden_p*.npz, made by running the reference) and the
 CPU restatement oracle/integrated_ref.py.
 
 Bars (stated tolerances):

@@ -91,20 +91,28 @@ def test_oracle_bitexact_vs_reference_vectors(ldpc_golden, oracle_built, dectype
                         assert np.array_equal(app, ldpc_golden[key + "_app"][j], equal_nan=True), key
 
 
+def _ref_pin():
+    """Outputs of the reference's own C decoder core on the inputs drawn below."""
+    return np.load(os.path.join(REPO, "tests", "golden", "ldpc_ref_pin.npz"))
+
+
 def test_minsum_fixed_equals_reference_on_uniform_degree(oracle_built):
     """With uniform check degree the reference's offset defect is inert, so the
-    corrected minsum must agree with the reference library bit for bit."""
-    if not bp.ref_available():
-        pytest.skip("oracle/_ref not built (reference absent)")
+    corrected minsum must agree with the reference library bit for bit: with its
+    recorded outputs (tests/golden/ldpc_ref_pin.npz, make_golden_ref_pin.py), and
+    with the library itself where oracle/_ref is built."""
+    pin = _ref_pin()
     c = code("802.16", "5/6", 27)          # cdeg == 20 everywhere
     assert len(set(c.cdeg.tolist())) == 1
     rng = np.random.default_rng(7)
-    for _ in range(6):
+    for j in range(6):
         x = c.encode(rng.integers(0, 2, c.K))
         llr = 2 * ((1 - 2 * x) + 0.6 * rng.standard_normal(c.N)) / 0.36
         a1, i1 = bp.decode("minsum", llr, c.vdeg, c.cdeg, c.intrlv, 50)
-        a2, i2 = bp.decode("minsum_refbug", llr, c.vdeg, c.cdeg, c.intrlv, 50, use_ref=True)
-        assert i1 == i2 and np.array_equal(a1, a2)
+        assert i1 == pin["minsum_it"][j] and np.array_equal(a1, pin["minsum_app"][j])
+        if bp.ref_available():
+            a2, i2 = bp.decode("minsum_refbug", llr, c.vdeg, c.cdeg, c.intrlv, 50, use_ref=True)
+            assert i1 == i2 and np.array_equal(a1, a2)
 
 
 def test_minsum_fixed_decodes_nonuniform_code(oracle_built):
@@ -126,16 +134,24 @@ def test_minsum_fixed_decodes_nonuniform_code(oracle_built):
 
 
 def test_lxor_lxfb_oracle(oracle_built):
-    if not bp.ref_available():
-        pytest.skip("oracle/_ref not built")
+    """Lxor / Lxfb of the restatement against the reference library's recorded
+    outputs (tests/golden/ldpc_ref_pin.npz), and against the library itself where
+    oracle/_ref is built."""
+    pin = _ref_pin()
+    live = bp.ref_available()
     rng = np.random.default_rng(0)
-    for _ in range(50):
+    for j in range(50):
         a, b = rng.standard_normal(2) * 5
         for corr in (0, 1):
-            assert bp.lxor(a, b, corr) == bp.lxor(a, b, corr, use_ref=True)
+            assert bp.lxor(a, b, corr) == pin["lxor"][j, corr]
+            if live:
+                assert bp.lxor(a, b, corr) == bp.lxor(a, b, corr, use_ref=True)
         L = rng.standard_normal(7) * 3
-        assert bp.lxfb(L, 1)[0] == bp.lxfb(L, 1, use_ref=True)[0]
-        assert np.array_equal(bp.lxfb(L, 1)[1], bp.lxfb(L, 1, use_ref=True)[1])
+        assert bp.lxfb(L, 1)[0] == pin["lxfb_total"][j]
+        assert np.array_equal(bp.lxfb(L, 1)[1], pin["lxfb_ext"][j])
+        if live:
+            assert bp.lxfb(L, 1)[0] == bp.lxfb(L, 1, use_ref=True)[0]
+            assert np.array_equal(bp.lxfb(L, 1)[1], bp.lxfb(L, 1, use_ref=True)[1])
 
 
 @pytest.mark.parametrize("std,rate,z", [("802.11n", "1/2", 27), ("802.11n", "5/6", 27), ("802.16", "2/3", 24)])

@@ -9,7 +9,7 @@ O=gpurun_out/abenv; rm -rf $O; mkdir -p $O
 if [ "${AB_TESTS:-0}" = 1 ]; then
   timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method thread tests/test_bp_grouped_gpu.py tests/test_bp_f32_exact_gpu.py tests/test_bp_gpu.py > $O/tests.log 2>&1
 fi
-A="--no-sc --no-sc-notebook --no-concat --no-r13 --no-f64 --cpu-seconds 0 --steps 1 --warmup 1 --bp-steps 10 --bp-ebn0-extra"
+A="--full --no-sc --no-sc-notebook --no-concat --no-r13 --no-f64 --cpu-seconds 0 --steps 1 --warmup 1 --bp-steps 10 --bp-ebn0-extra"
 for i in 1 2; do
   for cfg in "$@"; do
     name=${cfg%%:*}; envs=${cfg#*:}

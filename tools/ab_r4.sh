@@ -12,10 +12,10 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/ab_$1; rm -rf $O; mkdir -p $O
 case $1 in
-  c2) ARGS="--no-bp --no-sc --no-sc-notebook --no-concat --no-f64";;
-  concat) ARGS="--no-bp --no-sc --no-sc-notebook --no-r13 --no-f64 --steps 1 --warmup 1";;
-  bp) ARGS="--no-sc --no-sc-notebook --no-concat --no-r13 --no-f64 --bp-ebn0-extra --steps 1 --warmup 1";;
-  sc) ARGS="--no-bp --no-concat --no-r13 --no-f64 --steps 1 --warmup 1";;
+  c2) ARGS="--full --no-bp --no-sc --no-sc-notebook --no-concat --no-f64";;
+  concat) ARGS="--full --no-bp --no-sc --no-sc-notebook --no-r13 --no-f64 --steps 1 --warmup 1";;
+  bp) ARGS="--full --no-sc --no-sc-notebook --no-concat --no-r13 --no-f64 --bp-ebn0-extra --steps 1 --warmup 1";;
+  sc) ARGS="--full --no-bp --no-concat --no-r13 --no-f64 --steps 1 --warmup 1";;
 esac
 if [ -n "$2" ]; then
   timeout -k 10 600 python -u -m pytest $2 -x -q --timeout 300 --timeout-method thread > $O/tests.log 2>&1
