@@ -364,6 +364,44 @@ int sg_amp_count_errors_device(const int32_t *d_map_idx, const int32_t *d_true_i
 int sg_section_softmax(const double *x, int L, int M, double scale, double *out);
 int sg_section_argmax(const double *x, int L, int M, int32_t *idx);
 
+/* ------------------------------------------------- complex / K-PSK AMP */
+typedef struct sg_camp_plan sg_camp_plan;
+
+/* Design of a complex SPARC with sub-sampled FFT operator (sparc.py:593-646,
+ * 703-880 with csparc=True): W, L, M, n and the transforms as sg_amp_plan_create;
+ * order0[t][Mr] / order1[t][Mc] index the bins of a w-point FFT,
+ * w = 2^ceil(log2(max(Mr+2, Mc+2))), 16 <= w <= 2^16 (SG_ERR_UNSUPPORTED
+ * otherwise).  Double precision only.  Complex arrays cross this ABI as
+ * interleaved double[2] (re, im). */
+int sg_camp_plan_create(int ndim, const double *W, int Lr, int Lc, int L, int M, int n,
+                        const uint32_t *order0, const uint32_t *order1, sg_camp_plan **out);
+int sg_camp_plan_destroy(sg_camp_plan *p);
+int sg_camp_plan_info(const sg_camp_plan *p, int *w, int *nT, int *Mr, int *Mc, int *P, int *Q);
+/* transpose 0: A x, in[B][L*M] -> out[B][n];  transpose 1: A^H y, in[B][n] -> out[B][L*M]
+ * (the Ab / Az closures of sparc_transforms(..., csparc=True)). */
+int sg_camp_apply(sg_camp_plan *p, int transpose, const double *in, int B, double *out);
+/* Batched AMP decode of complex received words y[B][n] (sparc.py:883-999).
+ * K = 1: unmodulated; K = 2 .. 64 (a power of two; larger: SG_ERR_UNSUPPORTED):
+ * K-PSK with the host's constellation constel[K] (psk_constel, sparc.py:225-239).
+ * true_idx / true_sym [B][L] (optional): the transmitted locations and
+ * constellation indices, used for NMSE.  Outputs: map_idx / map_sym [B][L] the
+ * MAP location and constellation index of the last s (sparc.py:997), t_final[B],
+ * nmse[B][t_max][Lc], psi[B][Lc].  The *_sym arrays are ignored (may be NULL)
+ * for K = 1. */
+int sg_camp_decode(sg_camp_plan *p, const double *y, int B, int K, const double *constel,
+                   const int32_t *true_idx, const int32_t *true_sym, double awgn_var, int t_max,
+                   double rtol, int phi_method, int32_t *map_idx, int32_t *map_sym,
+                   int32_t *t_final, double *nmse, double *psi);
+/* Stand-alone K-PSK section estimators (sparc.py:402-512).  x = s / tau with
+ * tau already halved for complex s, [L*M] interleaved complex if x_is_complex
+ * else real; out[L*M] interleaved complex (imaginary part 0 for K <= 2). */
+int sg_section_mmse_psk(const double *x, int L, int M, int K, const double *constel,
+                        int x_is_complex, double *out);
+/* idx[l] the MAP location of section l, sym[l] its constellation index (0 for
+ * K = 1, where sym may be NULL); first maximum in row-major order. */
+int sg_section_map_psk(const double *s, int L, int M, int K, const double *constel,
+                       int s_is_complex, int32_t *idx, int32_t *sym);
+
 #ifdef __cplusplus
 }
 #endif

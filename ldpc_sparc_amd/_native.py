@@ -84,6 +84,16 @@ SIGNATURES = [
     ("sg_amp_count_errors_device", ct.c_int, [vp, vp, vp, ct.c_int, ct.c_int, ct.c_int, vp, vp]),
     ("sg_section_softmax", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_double, vp]),
     ("sg_section_argmax", ct.c_int, [vp, ct.c_int, ct.c_int, vp]),
+    # complex / K-PSK AMP engine
+    ("sg_camp_plan_create", ct.c_int, [ct.c_int, vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                       vp, vp, ct.POINTER(vp)]),
+    ("sg_camp_plan_destroy", ct.c_int, [vp]),
+    ("sg_camp_plan_info", ct.c_int, [vp] + [ct.POINTER(ct.c_int)] * 6),
+    ("sg_camp_apply", ct.c_int, [vp, ct.c_int, vp, ct.c_int, vp]),
+    ("sg_camp_decode", ct.c_int, [vp, vp, ct.c_int, ct.c_int, vp, vp, vp, ct.c_double, ct.c_int, ct.c_double,
+                                  ct.c_int, vp, vp, vp, vp, vp]),
+    ("sg_section_mmse_psk", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, vp, ct.c_int, vp]),
+    ("sg_section_map_psk", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, vp, ct.c_int, vp, vp]),
     ("Lxfb", ct.c_double, [dp, ct.c_long, ct.c_int]),
     ("sg_device_synchronize", ct.c_int, []),
     ("sg_profile_enable", ct.c_int, [ct.c_int]),

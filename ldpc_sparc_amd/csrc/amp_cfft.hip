@@ -1,0 +1,512 @@
+// AMP decoder for complex SPARCs with sub-sampled FFT designs and K-PSK
+// modulated message vectors on gfx950, double precision.
+//
+// Reference: sparc_public/sparc.py sparc_amp :883-999 (loop), sparc_transforms
+// :703-880 with sub_fft :593-646 (design operator), msg_vector_mmse_estimator
+// :402-465 (denoisers, K branches), msg_vector_map_estimator :467-512 (MAP).
+//
+// Operator (DESIGN.md "Complex engine"): for each transform (nonzero block of W)
+//   Ab:  r = sqrt(W_rc/L) * FFT_w(scatter(beta_c, order1))[order0]
+//   Az:  u = sqrt(W_rc/L) * conj(FFT_w(conj(scatter(z_r/phi_r, order0))))[order1]
+// The second is the unnormalised inverse transform, so both directions are one
+// w-point complex FFT, run four-step with w = P Q, input m = Q m1 + m2, output
+// k = k1 + P k2:
+//   pass A  (per tile of CT columns m2): scatter the input into h[m1][m2],
+//           P-point FFTs over m1, twiddle w_w^{m2 k1}, store T[k1][m2]
+//   pass B  (per tile of RT rows k1): Q-point FFTs over m2, store X[k1][k2]
+// The needed outputs are single bins, read where they are used (the residual
+// of the control kernel, the s update of eta) from X at (k mod P) Q + k / P.
+//   eta     (one wavefront per section): s = beta + tau u, the K-PSK MMSE
+//           denoiser (max-shifted per section: the same function as the
+//           reference's global-max float128 form), the MAP decision of s and
+//           the section statistics
+//   control (one workgroup per codeword): Onsager residual, phi, tau, psi,
+//           NMSE, early stop (sparc.py:931-988) with complex quantities.
+#include "amp_cfft.hpp"
+
+namespace sg {
+namespace {
+
+__device__ __forceinline__ double cw_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double cw_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double cblock_sum(double v, double *red) {
+    v = cw_sum(v);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int w = 0; w < nw; ++w) t += red[w];
+    return t;
+}
+
+// ------------------------------------------------------------------ pass A
+// INV = false: input beta of the transform's column block scattered by order1;
+// INV = true: input z / phi of its row block scattered by order0.
+template <bool INV>
+__global__ __launch_bounds__(256) void cfft_passA(CampTables tb, CampBufs bf) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    cxd *d = reinterpret_cast<cxd *>(smem_raw);
+    const int cw = blockIdx.z, t = blockIdx.y;
+    if (!bf.active[cw]) return;
+    const int nthr = blockDim.x, tid = threadIdx.x;
+    const int CT = tb.CT, m2_0 = blockIdx.x * CT, total = tb.P * CT;
+    const int32_t *inmap = (INV ? tb.in0 : tb.in1) + (size_t)t * tb.w;
+    const cxd *src = INV ? bf.z + (size_t)cw * tb.n + (size_t)tb.t_row[t] * tb.Mr
+                         : bf.beta + (size_t)cw * tb.LM + (size_t)tb.t_col[t] * tb.Mc;
+    const double phi = INV ? bf.phi[(size_t)cw * tb.Lr + tb.t_row[t]] : 1.0;
+    for (int idx = tid; idx < total; idx += nthr) {
+        const int m1 = idx / CT, c = idx - m1 * CT;
+        const int j = inmap[tb.Q * m1 + m2_0 + c];
+        cxd v{0.0, 0.0};
+        if (j >= 0) {
+            v = src[j];
+            if (INV) { v.x /= phi; v.y /= phi; }  // z / phi_use, sparc.py:972
+        }
+        d[idx] = v;
+    }
+    __syncthreads();
+    lds_fft<double, INV, CAMP_EPT, true>(d, tb.log2P, CT, CT, 1, tb.twP, tid, nthr);
+    cxd *out = bf.buf0 + ((size_t)cw * tb.nT + t) * tb.w;
+    for (int idx = tid; idx < total; idx += nthr) {
+        const int k1 = idx / CT, c = idx - k1 * CT;
+        const int m2 = m2_0 + c;
+        cxd tw = tb.twW[m2 * k1];
+        if (INV) tw.y = -tw.y;
+        out[(size_t)k1 * tb.Q + m2] = cmul(d[idx], tw);
+    }
+}
+
+// ------------------------------------------------------------------ pass B
+template <bool INV>
+__global__ __launch_bounds__(256) void cfft_passB(CampTables tb, CampBufs bf) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    cxd *d = reinterpret_cast<cxd *>(smem_raw);
+    const int cw = blockIdx.z, t = blockIdx.y;
+    if (!bf.active[cw]) return;
+    const int nthr = blockDim.x, tid = threadIdx.x;
+    const int total = tb.RT * tb.Q;
+    const size_t off = ((size_t)cw * tb.nT + t) * tb.w + (size_t)blockIdx.x * total;
+    for (int idx = tid; idx < total; idx += nthr) d[idx] = bf.buf0[off + idx];
+    __syncthreads();
+    lds_fft<double, INV, CAMP_EPT, false>(d, tb.log2Q, tb.RT, 1, tb.Q, tb.twQ, tid, nthr);
+    for (int idx = tid; idx < total; idx += nthr) bf.buf1[off + idx] = d[idx];
+}
+
+// (A beta)_i of row block r summed over the row's transforms in table order
+__device__ __forceinline__ cxd gather_ab(const CampTables &tb, const CampBufs &bf, int cw, int r, int il) {
+    cxd a{0.0, 0.0};
+    for (int q = tb.row_ptr[r]; q < tb.row_ptr[r + 1]; ++q) {
+        const int t = tb.row_t[q];
+        const cxd v = bf.buf1[((size_t)cw * tb.nT + t) * tb.w + tb.pos0[(size_t)t * tb.Mr + il]];
+        const double sc = tb.t_scale[t];
+        a.x += sc * v.x;
+        a.y += sc * v.y;
+    }
+    return a;
+}
+// (A^H z/phi)_j of column block c summed over the column's transforms in table order
+__device__ __forceinline__ cxd gather_az(const CampTables &tb, const CampBufs &bf, int cw, int c, int jl) {
+    cxd a{0.0, 0.0};
+    for (int q = tb.col_ptr[c]; q < tb.col_ptr[c + 1]; ++q) {
+        const int t = tb.col_t[q];
+        const cxd v = bf.buf1[((size_t)cw * tb.nT + t) * tb.w + tb.pos1[(size_t)t * tb.Mc + jl]];
+        const double sc = tb.t_scale[t];
+        a.x += sc * v.x;
+        a.y += sc * v.y;
+    }
+    return a;
+}
+
+// ------------------------------------------------------------------ K-PSK section estimators
+// x = s / tau (tau already halved for complex s, sparc.py:417-418).  The
+// exponent arguments of entry x are Re x (K = 1), +-Re x (K = 2), +-Re x and
+// +-Im x (K = 4), Re(x conj c_k) (K >= 8); psk_shift is their largest.
+__device__ __forceinline__ double psk_shift(int K, const cxd *__restrict__ c, cxd x) {
+    if (K == 1) return x.x;
+    if (K == 2) return fabs(x.x);
+    if (K == 4) return fmax(fabs(x.x), fabs(x.y));
+    double m = -INFINITY;
+    for (int k = 0; k < K; ++k) m = fmax(m, x.x * c[k].x + x.y * c[k].y);
+    return m;
+}
+// numerator of the entry's estimate and its part of the section's denominator
+__device__ __forceinline__ void psk_terms(int K, const cxd *__restrict__ c, cxd x, double m, cxd *top, double *den) {
+    if (K == 1) {
+        const double e = exp(x.x - m);
+        *top = cxd{e, 0.0};
+        *den = e;
+    } else if (K == 2) {
+        const double e1 = exp(x.x - m), e2 = exp(-x.x - m);
+        *top = cxd{e1 - e2, 0.0};
+        *den = e1 + e2;
+    } else if (K == 4) {
+        const double x1 = exp(x.x - m), x2 = exp(-x.x - m), y1 = exp(x.y - m), y2 = exp(-x.y - m);
+        *top = cxd{x1 - x2, y1 - y2};
+        *den = (x1 + x2) + (y1 + y2);
+    } else {
+        cxd a{0.0, 0.0};
+        double dn = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double e = exp(x.x * c[k].x + x.y * c[k].y - m);
+            a.x += e * c[k].x;
+            a.y += e * c[k].y;
+            dn += e;
+        }
+        *top = a;
+        *den = dn;
+    }
+}
+
+// MAP decision of a section (sparc.py:485-510): the lane's running best
+struct MapBest {
+    double v;
+    int flat;  // entry e (K < 8) or e K + k (K >= 8, row-major over (entry, symbol))
+    cxd s;
+};
+__device__ __forceinline__ MapBest map_init() { return MapBest{-INFINITY, 0x7fffffff, cxd{0.0, 0.0}}; }
+__device__ __forceinline__ void map_update(int K, const cxd *__restrict__ c, cxd s, int e, MapBest &b) {
+    if (K < 8) {
+        const double v = K == 1 ? s.x : K == 2 ? fabs(s.x) : fmax(fabs(s.x), fabs(s.y));
+        if (b.flat == 0x7fffffff || v > b.v) b = MapBest{v, e, s};
+    } else {
+        for (int k = 0; k < K; ++k) {
+            const double v = s.x * c[k].x + s.y * c[k].y;  // Re(conj(s) c_k)
+            if (b.flat == 0x7fffffff || v > b.v) b = MapBest{v, e * K + k, s};
+        }
+    }
+}
+// the section's first maximum over the wavefront; entry e lives on lane e & 63
+__device__ __forceinline__ void map_finish(int K, const MapBest &b, int *idx, int *sym) {
+    const double g = cw_max(b.v);
+    int cand = (b.flat != 0x7fffffff && b.v == g) ? b.flat : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+    if (cand == 0x7fffffff) cand = 0;
+    const int e = K >= 8 ? cand / K : cand;
+    const double sx = __shfl(b.s.x, e & 63, 64), sy = __shfl(b.s.y, e & 63, 64);
+    int k = 0;
+    if (K == 2) k = sx < 0.0 ? 1 : 0;
+    else if (K == 4) {
+        k = (int)rint(4.0 * atan2(sy, sx) / (2.0 * 3.14159265358979323846));  // sparc.py:496-498
+        if (k < 0) k += 4;
+        k &= 3;
+    } else if (K >= 8) k = cand - e * K;
+    *idx = e;
+    *sym = k;
+}
+
+// ------------------------------------------------------------------ eta
+// One wavefront per section, lane owns entries lane, lane + 64, ...  The
+// section's x and then its numerators are staged in the lane's own beta
+// entries, so any M runs without per-lane register arrays.
+__global__ __launch_bounds__(256) void camp_eta(CampTables tb, CampBufs bf) {
+    const int cw = blockIdx.y;
+    if (!bf.active[cw]) return;
+    const int lane = threadIdx.x & 63;
+    const int l = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (l >= tb.L) return;
+    const int c = l / (tb.L / tb.Lc);
+    const double tau = bf.tau[(size_t)cw * tb.Lc + c];
+    const double th = tau / 2;  // s is complex: sparc.py:417-418
+    const int K = bf.K;
+    const cxd *cs = bf.constel;
+    cxd *beta = bf.beta + (size_t)cw * tb.LM + (size_t)l * tb.M;
+    const int jl0 = l * tb.M - c * tb.Mc;
+    double m = -INFINITY;
+    MapBest mb = map_init();
+    for (int e = lane; e < tb.M; e += 64) {
+        const cxd u = gather_az(tb, bf, cw, c, jl0 + e);
+        const cxd b = beta[e];
+        const cxd s{b.x + tau * u.x, b.y + tau * u.y};  // sparc.py:972
+        const cxd x{s.x / th, s.y / th};
+        beta[e] = x;
+        m = fmax(m, psk_shift(K, cs, x));
+        map_update(K, cs, s, e, mb);
+    }
+    m = cw_max(m);
+    int midx, msym;
+    map_finish(K, mb, &midx, &msym);
+    double den = 0.0;
+    for (int e = lane; e < tb.M; e += 64) {
+        cxd top;
+        double dn;
+        psk_terms(K, cs, beta[e], m, &top, &dn);
+        beta[e] = top;
+        den += dn;
+    }
+    den = cw_sum(den);
+    const int truth = bf.true_idx ? bf.true_idx[(size_t)cw * tb.L + l] : -1;
+    cxd tv{1.0, 0.0};
+    if (K > 1 && bf.true_sym && truth >= 0) tv = cs[bf.true_sym[(size_t)cw * tb.L + l]];
+    double ss = 0.0, se = 0.0;
+    for (int e = lane; e < tb.M; e += 64) {
+        const cxd top = beta[e];
+        const cxd b{top.x / den, top.y / den};
+        beta[e] = b;
+        ss += b.x * b.x + b.y * b.y;
+        const double dx = b.x - (e == truth ? tv.x : 0.0), dy = b.y - (e == truth ? tv.y : 0.0);
+        se += dx * dx + dy * dy;
+    }
+    ss = cw_sum(ss);
+    se = cw_sum(se);
+    if (lane == 0) {
+        const size_t o = (size_t)cw * tb.L + l;
+        bf.sec_sumsq[o] = ss;
+        bf.sec_err[o] = se;
+        bf.sec_idx[o] = midx;
+        bf.sec_sym[o] = msym;
+    }
+}
+
+// ------------------------------------------------------------------ control
+// phase 0 (before Az, iteration t): Onsager residual and phi / tau
+// (sparc.py:932-969); phase 1 (after eta): psi, NMSE, stopping
+// (sparc.py:976-988); phase 2: initialisation.
+__global__ __launch_bounds__(1024) void camp_control(CampTables tb, CampBufs bf, AmpScalars sc, AmpParams pr, int phase,
+                                                     int t) {
+    __shared__ double red[16];
+    const int cw = blockIdx.x, tid = threadIdx.x;
+    const int Lr = tb.Lr, Lc = tb.Lc;
+    double *psi = sc.psi + (size_t)cw * Lc, *psi_prev = sc.psi_prev + (size_t)cw * Lc;
+    double *phi = bf.phi + (size_t)cw * Lr, *phi_prev = sc.phi_prev + (size_t)cw * Lr;
+    double *gamma = sc.gamma + (size_t)cw * Lr, *bco = sc.bcoef + (size_t)cw * Lr;
+    double *tau = bf.tau + (size_t)cw * Lc;
+    double *nmse = sc.nmse + (size_t)cw * pr.t_max * Lc;
+    if (phase == 2) {  // init: beta = 0 (memset on host), nmse = 1
+        for (int i = tid; i < pr.t_max * Lc; i += blockDim.x) nmse[i] = 1.0;
+        if (tid == 0) { bf.active[cw] = 1; sc.t_final[cw] = 0; }
+        return;
+    }
+    if (!bf.active[cw]) return;
+    if (phase == 0) {
+        cxd *z = bf.z + (size_t)cw * tb.n;
+        const cxd *y = bf.y + (size_t)cw * tb.n;
+        if (t > 0) {
+            for (int r = tid; r < Lr; r += blockDim.x) {
+                phi_prev[r] = phi[r];
+                double g;
+                if (tb.ndim == 0) g = pr.W[0] * psi[0];
+                else {
+                    double acc = 0.0;
+                    for (int c = 0; c < Lc; ++c) acc += pr.W[r * Lc + c] * psi[c];
+                    g = acc / Lc;
+                }
+                gamma[r] = g;
+                bco[r] = g / phi[r];
+            }
+            __syncthreads();
+            for (int c = tid; c < Lc; c += blockDim.x) psi_prev[c] = psi[c];
+            for (int i = tid; i < tb.n; i += blockDim.x) {  // z = y - A beta + b z
+                const int r = i / tb.Mr;
+                const cxd ab = gather_ab(tb, bf, cw, r, i - r * tb.Mr);
+                const double b = bco[r];
+                const cxd yv = y[i], zv = z[i];
+                z[i] = cxd{(yv.x - ab.x) + b * zv.x, (yv.y - ab.y) + b * zv.y};
+            }
+        } else {
+            for (int i = tid; i < tb.n; i += blockDim.x) z[i] = y[i];
+            if (tid == 0) {
+                if (tb.ndim == 0) gamma[0] = pr.W[0];
+                else
+                    for (int r = 0; r < Lr; ++r) {
+                        double acc = 0.0;
+                        for (int c = 0; c < Lc; ++c) acc += pr.W[r * Lc + c];
+                        gamma[r] = acc / Lc;
+                    }
+            }
+        }
+        __syncthreads();
+        if (pr.phi_method == 1) {
+            if (tid == 0)
+                for (int r = 0; r < Lr; ++r) phi[r] = pr.awgn_var + gamma[r];
+        } else {  // mean |z|^2 per row block
+            for (int r = 0; r < Lr; ++r) {
+                double acc = 0.0;
+                for (int i = r * tb.Mr + tid; i < (r + 1) * tb.Mr; i += blockDim.x) acc += z[i].x * z[i].x + z[i].y * z[i].y;
+                acc = cblock_sum(acc, red);
+                if (tid == 0) phi[r] = acc / (double)tb.Mr;
+            }
+        }
+        __syncthreads();
+        for (int c = tid; c < (tb.ndim == 0 ? 1 : Lc); c += blockDim.x) {
+            if (tb.ndim == 0) tau[0] = (tb.L * phi[0] / tb.n) / pr.W[0];
+            else if (tb.ndim == 1) tau[c] = (tb.L * phi[0] / tb.n) / pr.W[c];
+            else {
+                double acc = 0.0;
+                for (int r = 0; r < Lr; ++r) acc += pr.W[r * Lc + c] * (1.0 / phi[r]);
+                tau[c] = ((double)tb.L / tb.Mr) / acc;
+            }
+        }
+        return;
+    }
+    // phase 1: psi / NMSE / stop
+    const int spc = tb.L / Lc;
+    const double denom = (tb.ndim == 0) ? (double)tb.L : ((double)tb.L / Lc);
+    for (int c = 0; c < Lc; ++c) {
+        double a = 0.0, e = 0.0;
+        for (int l = c * spc + tid; l < (c + 1) * spc; l += blockDim.x) {
+            a += bf.sec_sumsq[(size_t)cw * tb.L + l];
+            e += bf.sec_err[(size_t)cw * tb.L + l];
+        }
+        a = cblock_sum(a, red);
+        e = cblock_sum(e, red);
+        if (tid == 0) {
+            psi[c] = 1.0 - a / denom;
+            nmse[(size_t)(t + 1) * Lc + c] = e / denom;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        bool stop = false;
+        if (t > 0) {  // np.allclose(psi, psi_prev, rtol, atol), sparc.py:984
+            stop = true;
+            for (int c = 0; c < Lc; ++c)
+                if (!(fabs(psi[c] - psi_prev[c]) <= pr.atol + pr.rtol * fabs(psi_prev[c]))) stop = false;
+        }
+        if (stop) {  // nmse[t:] = nmse[t]
+            for (int tt = t + 1; tt < pr.t_max; ++tt)
+                for (int c = 0; c < Lc; ++c) nmse[(size_t)tt * Lc + c] = nmse[(size_t)t * Lc + c];
+            sc.t_final[cw] = t + 1;
+            bf.active[cw] = 0;
+        } else if (t == pr.t_max - 2) {
+            sc.t_final[cw] = t + 1;
+            bf.active[cw] = 0;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ operator outputs
+__global__ void camp_rowsum(CampTables tb, CampBufs bf, cxd *out) {
+    const int cw = blockIdx.y;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < tb.n; i += gridDim.x * blockDim.x) {
+        const int r = i / tb.Mr;
+        out[(size_t)cw * tb.n + i] = gather_ab(tb, bf, cw, r, i - r * tb.Mr);
+    }
+}
+__global__ void camp_colgather(CampTables tb, CampBufs bf, cxd *out) {
+    const int cw = blockIdx.y;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < tb.LM; j += gridDim.x * blockDim.x) {
+        const int c = j / tb.Mc;
+        out[(size_t)cw * tb.LM + j] = gather_az(tb, bf, cw, c, j - c * tb.Mc);
+    }
+}
+
+// ------------------------------------------------------------------ stand-alone estimators
+__global__ __launch_bounds__(256) void psk_mmse_kernel(const cxd *__restrict__ x, int L, int M, int K,
+                                                       const cxd *__restrict__ cs, cxd *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int l = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (l >= L) return;
+    const cxd *xs = x + (size_t)l * M;
+    double m = -INFINITY;
+    for (int e = lane; e < M; e += 64) m = fmax(m, psk_shift(K, cs, xs[e]));
+    m = cw_max(m);
+    double den = 0.0;
+    for (int e = lane; e < M; e += 64) {
+        cxd top;
+        double dn;
+        psk_terms(K, cs, xs[e], m, &top, &dn);
+        out[(size_t)l * M + e] = top;
+        den += dn;
+    }
+    den = cw_sum(den);
+    for (int e = lane; e < M; e += 64) {
+        cxd &o = out[(size_t)l * M + e];
+        o = cxd{o.x / den, o.y / den};
+    }
+}
+
+__global__ __launch_bounds__(256) void psk_map_kernel(const cxd *__restrict__ sv, int L, int M, int K,
+                                                      const cxd *__restrict__ cs, int32_t *__restrict__ idx,
+                                                      int32_t *__restrict__ sym) {
+    const int lane = threadIdx.x & 63;
+    const int l = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (l >= L) return;
+    MapBest mb = map_init();
+    for (int e = lane; e < M; e += 64) map_update(K, cs, sv[(size_t)l * M + e], e, mb);
+    int i, k;
+    map_finish(K, mb, &i, &k);
+    if (lane == 0) { idx[l] = i; sym[l] = k; }
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ launchers
+int camp_launch_fft(const CampTables &tb, const CampBufs &bf, bool inverse, hipStream_t s) {
+    if (bf.B <= 0) return SG_OK;
+    const int totA = tb.P * tb.CT, totB = tb.RT * tb.Q;
+    if (totA % CAMP_EPT || totB % CAMP_EPT || totA / CAMP_EPT > 256 || totB / CAMP_EPT > 256 || tb.Q % tb.CT ||
+        tb.P % tb.RT)
+        return fail(SG_ERR_UNSUPPORTED, "complex FFT geometry P=%d Q=%d CT=%d RT=%d unsupported", tb.P, tb.Q, tb.CT,
+                    tb.RT);
+    const dim3 gA(tb.Q / tb.CT, tb.nT, bf.B), gB(tb.P / tb.RT, tb.nT, bf.B);
+    const size_t ldsA = sizeof(cxd) * totA, ldsB = sizeof(cxd) * totB;
+    {
+        ProfScope ps(inverse ? SG_PH_AZ_A : SG_PH_AB_A, s);
+        if (inverse) hipLaunchKernelGGL(cfft_passA<true>, gA, dim3(totA / CAMP_EPT), ldsA, s, tb, bf);
+        else hipLaunchKernelGGL(cfft_passA<false>, gA, dim3(totA / CAMP_EPT), ldsA, s, tb, bf);
+    }
+    SG_HIP(hipGetLastError());
+    {
+        ProfScope ps(inverse ? SG_PH_AZ_B : SG_PH_AB_B, s);
+        if (inverse) hipLaunchKernelGGL(cfft_passB<true>, gB, dim3(totB / CAMP_EPT), ldsB, s, tb, bf);
+        else hipLaunchKernelGGL(cfft_passB<false>, gB, dim3(totB / CAMP_EPT), ldsB, s, tb, bf);
+    }
+    SG_HIP(hipGetLastError());
+    return SG_OK;
+}
+
+int camp_launch_eta(const CampTables &tb, const CampBufs &bf, hipStream_t s) {
+    if (bf.B <= 0) return SG_OK;
+    const int waves = 4;
+    ProfScope ps(SG_PH_ETA, s);
+    hipLaunchKernelGGL(camp_eta, dim3((tb.L + waves - 1) / waves, bf.B), dim3(64 * waves), 0, s, tb, bf);
+    SG_HIP(hipGetLastError());
+    return SG_OK;
+}
+
+int camp_launch_control(const CampTables &tb, const CampBufs &bf, const AmpScalars &sc, const AmpParams &pr, int phase,
+                        int t, hipStream_t s) {
+    if (bf.B <= 0) return SG_OK;
+    ProfScope ps(SG_PH_CONTROL, s);
+    hipLaunchKernelGGL(camp_control, dim3(bf.B), dim3(1024), 0, s, tb, bf, sc, pr, phase, t);
+    SG_HIP(hipGetLastError());
+    return SG_OK;
+}
+
+int camp_launch_rowsum(const CampTables &tb, const CampBufs &bf, cxd *out, hipStream_t s) {
+    hipLaunchKernelGGL(camp_rowsum, dim3((tb.n + 255) / 256, bf.B), dim3(256), 0, s, tb, bf, out);
+    SG_HIP(hipGetLastError());
+    return SG_OK;
+}
+
+int camp_launch_colgather(const CampTables &tb, const CampBufs &bf, cxd *out, hipStream_t s) {
+    int gx = (tb.LM + 255) / 256;
+    if (gx > 4096) gx = 4096;
+    hipLaunchKernelGGL(camp_colgather, dim3(gx, bf.B), dim3(256), 0, s, tb, bf, out);
+    SG_HIP(hipGetLastError());
+    return SG_OK;
+}
+
+int camp_launch_mmse(const cxd *x, int L, int M, int K, const cxd *constel, cxd *out, hipStream_t s) {
+    hipLaunchKernelGGL(psk_mmse_kernel, dim3((L + 3) / 4), dim3(256), 0, s, x, L, M, K, constel, out);
+    SG_HIP(hipGetLastError());
+    return SG_OK;
+}
+
+int camp_launch_map(const cxd *sv, int L, int M, int K, const cxd *constel, int32_t *idx, int32_t *sym, hipStream_t s) {
+    hipLaunchKernelGGL(psk_map_kernel, dim3((L + 3) / 4), dim3(256), 0, s, sv, L, M, K, constel, idx, sym);
+    SG_HIP(hipGetLastError());
+    return SG_OK;
+}
+
+}  // namespace sg

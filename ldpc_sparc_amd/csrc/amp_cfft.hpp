@@ -1,0 +1,66 @@
+// Declarations shared by the complex AMP engine's kernels (amp_cfft.hip) and
+// its host plan / C ABI (capi_camp.cpp): complex SPARCs with the sub-sampled
+// FFT design (sparc.py:593-646) and K-PSK modulated message vectors, double
+// precision only.
+#pragma once
+#include "amp.hpp"
+
+namespace sg {
+
+typedef cx<double> cxd;
+
+constexpr int CAMP_MAX_K = 64;     // largest PSK constellation
+constexpr int CAMP_EPT = 8;        // FFT elements per thread of every pass
+constexpr int CAMP_MIN_LOG2W = 4;  // w = 16 ... 2^16
+constexpr int CAMP_MAX_LOG2W = 16;
+
+// Design tables of one complex design, device pointers.  A "transform" is one
+// nonzero block (r, c) of the base matrix W: a w-point complex FFT, w = P Q,
+// with its own orders.  Bin k = k1 + P k2 of a transform's output sits at
+// position k1 Q + k2 of the pass-B layout.
+struct CampTables {
+    int nT, w, P, Q, log2P, log2Q;
+    int CT, RT;  // pass A: columns m2 per workgroup; pass B: rows k1 per workgroup
+    int L, M, LM, n, Lr, Lc, Mr, Mc, ndim;
+    const int32_t *t_row, *t_col;    // [nT]
+    const double *t_scale;           // [nT] sqrt(W_rc / L)
+    const int32_t *col_ptr, *col_t;  // CSR: transforms of each column block, row-major order
+    const int32_t *row_ptr, *row_t;  // CSR: transforms of each row block, row-major order
+    const int32_t *in1;              // [nT][w] input index m -> local column index (order1 inverted), or -1
+    const int32_t *in0;              // [nT][w] input index m -> local row index (order0 inverted), or -1
+    const int32_t *pos0;             // [nT][Mr] pass-B position of bin order0[i]
+    const int32_t *pos1;             // [nT][Mc] pass-B position of bin order1[j]
+    const cxd *twP, *twQ, *twW;      // exp(-2 pi i e / len), e < len, len = P, Q, w
+};
+
+// Per-batch device buffers.
+struct CampBufs {
+    int B;
+    int K;               // 1: unmodulated; else the K-PSK constellation size
+    const cxd *constel;  // [K] (unused for K = 1)
+    cxd *beta;           // [B][LM]
+    const cxd *y;        // [B][n]
+    cxd *z;              // [B][n]
+    cxd *buf0;           // [B][nT][w] pass A output T[k1][m2]
+    cxd *buf1;           // [B][nT][w] pass B output X[k1][k2]
+    double *phi;         // [B][Lr]
+    double *tau;         // [B][Lc]
+    int32_t *active;     // [B]
+    double *sec_sumsq;   // [B][L] sum |beta|^2 per section
+    double *sec_err;     // [B][L] sum |beta - beta0|^2 per section
+    int32_t *sec_idx;    // [B][L] MAP location of s per section
+    int32_t *sec_sym;    // [B][L] MAP constellation index of s per section
+    const int32_t *true_idx, *true_sym;  // [B][L] or null
+};
+
+int camp_launch_fft(const CampTables &tb, const CampBufs &bf, bool inverse, hipStream_t s);  // beta (or z/phi) -> buf1
+int camp_launch_eta(const CampTables &tb, const CampBufs &bf, hipStream_t s);
+int camp_launch_control(const CampTables &tb, const CampBufs &bf, const AmpScalars &sc, const AmpParams &pr, int phase,
+                        int t, hipStream_t s);
+int camp_launch_rowsum(const CampTables &tb, const CampBufs &bf, cxd *out, hipStream_t s);     // buf1 -> A x [B][n]
+int camp_launch_colgather(const CampTables &tb, const CampBufs &bf, cxd *out, hipStream_t s);  // buf1 -> A^H y [B][LM]
+// stand-alone section estimators on device arrays of L sections
+int camp_launch_mmse(const cxd *x, int L, int M, int K, const cxd *constel, cxd *out, hipStream_t s);
+int camp_launch_map(const cxd *sv, int L, int M, int K, const cxd *constel, int32_t *idx, int32_t *sym, hipStream_t s);
+
+}  // namespace sg

@@ -1,0 +1,392 @@
+// Host plan and C ABI of the complex AMP engine (amp_cfft.hip): complex SPARCs
+// with the sub-sampled FFT design and K-PSK modulated message vectors, double
+// precision.  Complex arrays cross the ABI as interleaved double[2].
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "amp_cfft.hpp"
+
+using namespace sg;
+
+struct sg_camp_plan {
+    int device = 0;
+    int ndim = 0, L = 0, M = 0, LM = 0, n = 0, Lr = 1, Lc = 1, Mr = 0, Mc = 0, nT = 0;
+    int w = 0, P = 0, Q = 0, log2P = 0, log2Q = 0, CT = 0, RT = 0;
+    std::vector<void *> allocs;  // design tables
+    int32_t *t_row = nullptr, *t_col = nullptr, *col_ptr = nullptr, *col_t = nullptr, *row_ptr = nullptr,
+            *row_t = nullptr, *in0 = nullptr, *in1 = nullptr, *pos0 = nullptr, *pos1 = nullptr;
+    double *t_scale = nullptr, *dW = nullptr;
+    cxd *twP = nullptr, *twQ = nullptr, *twW = nullptr, *constel = nullptr;
+    // workspace of the largest (B, t_max) seen: one allocation carved below
+    void *ws = nullptr;
+    int ws_B = 0, ws_tmax = 0;
+    cxd *beta = nullptr, *y = nullptr, *z = nullptr, *buf0 = nullptr, *buf1 = nullptr, *io = nullptr;
+    double *phi = nullptr, *tau = nullptr, *sec_sumsq = nullptr, *sec_err = nullptr, *psi = nullptr,
+           *psi_prev = nullptr, *phi_prev = nullptr, *gamma = nullptr, *bco = nullptr, *nmse = nullptr;
+    int32_t *active = nullptr, *sec_idx = nullptr, *sec_sym = nullptr, *true_idx = nullptr, *true_sym = nullptr,
+            *t_final = nullptr;
+};
+
+namespace {
+
+template <typename X>
+int upload(sg_camp_plan *p, X **dst, const std::vector<X> &src) {
+    void *d = nullptr;
+    SG_HIP(hipMalloc(&d, std::max<size_t>(src.size(), 1) * sizeof(X)));
+    p->allocs.push_back(d);
+    if (!src.empty()) SG_HIP(hipMemcpy(d, src.data(), src.size() * sizeof(X), hipMemcpyHostToDevice));
+    *dst = (X *)d;
+    return SG_OK;
+}
+
+std::vector<cxd> twiddles(int len) {  // exp(-2 pi i e / len)
+    std::vector<cxd> t(len);
+    for (int e = 0; e < len; ++e) {
+        const double a = -2.0 * M_PI * (double)e / (double)len;
+        t[e] = cxd{std::cos(a), std::sin(a)};
+    }
+    // exact values on the axes
+    t[0] = cxd{1.0, 0.0};
+    if (len % 4 == 0) {
+        t[len / 4] = cxd{0.0, -1.0};
+        t[len / 2] = cxd{-1.0, 0.0};
+        t[3 * len / 4] = cxd{0.0, 1.0};
+    } else if (len % 2 == 0) {
+        t[len / 2] = cxd{-1.0, 0.0};
+    }
+    return t;
+}
+
+int ensure_ws(sg_camp_plan *p, int B, int t_max) {
+    if (p->ws && B <= p->ws_B && t_max <= p->ws_tmax) return SG_OK;
+    B = std::max(B, p->ws_B);
+    t_max = std::max(t_max, p->ws_tmax);
+    if (p->ws) hipFree(p->ws);
+    p->ws = nullptr;
+    p->ws_B = p->ws_tmax = 0;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    const size_t sB = (size_t)B, big = sB * std::max(p->LM, p->n);
+    const size_t o_beta = take(sB * p->LM * sizeof(cxd)), o_y = take(sB * p->n * sizeof(cxd)),
+                 o_z = take(sB * p->n * sizeof(cxd)), o_b0 = take(sB * p->nT * p->w * sizeof(cxd)),
+                 o_b1 = take(sB * p->nT * p->w * sizeof(cxd)), o_io = take(big * sizeof(cxd)),
+                 o_phi = take(sB * p->Lr * 8), o_tau = take(sB * p->Lc * 8), o_ss = take(sB * p->L * 8),
+                 o_se = take(sB * p->L * 8), o_psi = take(sB * p->Lc * 8), o_psp = take(sB * p->Lc * 8),
+                 o_php = take(sB * p->Lr * 8), o_gam = take(sB * p->Lr * 8), o_bco = take(sB * p->Lr * 8),
+                 o_nm = take(sB * t_max * p->Lc * 8), o_act = take(sB * 4), o_si = take(sB * p->L * 4),
+                 o_sy = take(sB * p->L * 4), o_ti = take(sB * p->L * 4), o_ts = take(sB * p->L * 4),
+                 o_tf = take(sB * 4);
+    SG_HIP(hipMalloc(&p->ws, off));
+    char *b = (char *)p->ws;
+    p->beta = (cxd *)(b + o_beta); p->y = (cxd *)(b + o_y); p->z = (cxd *)(b + o_z);
+    p->buf0 = (cxd *)(b + o_b0); p->buf1 = (cxd *)(b + o_b1); p->io = (cxd *)(b + o_io);
+    p->phi = (double *)(b + o_phi); p->tau = (double *)(b + o_tau);
+    p->sec_sumsq = (double *)(b + o_ss); p->sec_err = (double *)(b + o_se);
+    p->psi = (double *)(b + o_psi); p->psi_prev = (double *)(b + o_psp); p->phi_prev = (double *)(b + o_php);
+    p->gamma = (double *)(b + o_gam); p->bco = (double *)(b + o_bco); p->nmse = (double *)(b + o_nm);
+    p->active = (int32_t *)(b + o_act); p->sec_idx = (int32_t *)(b + o_si); p->sec_sym = (int32_t *)(b + o_sy);
+    p->true_idx = (int32_t *)(b + o_ti); p->true_sym = (int32_t *)(b + o_ts); p->t_final = (int32_t *)(b + o_tf);
+    p->ws_B = B;
+    p->ws_tmax = t_max;
+    return SG_OK;
+}
+
+CampTables tables(const sg_camp_plan *p) {
+    CampTables tb;
+    tb.nT = p->nT; tb.w = p->w; tb.P = p->P; tb.Q = p->Q; tb.log2P = p->log2P; tb.log2Q = p->log2Q;
+    tb.CT = p->CT; tb.RT = p->RT;
+    tb.L = p->L; tb.M = p->M; tb.LM = p->LM; tb.n = p->n; tb.Lr = p->Lr; tb.Lc = p->Lc; tb.Mr = p->Mr; tb.Mc = p->Mc;
+    tb.ndim = p->ndim;
+    tb.t_row = p->t_row; tb.t_col = p->t_col; tb.t_scale = p->t_scale;
+    tb.col_ptr = p->col_ptr; tb.col_t = p->col_t; tb.row_ptr = p->row_ptr; tb.row_t = p->row_t;
+    tb.in1 = p->in1; tb.in0 = p->in0; tb.pos0 = p->pos0; tb.pos1 = p->pos1;
+    tb.twP = p->twP; tb.twQ = p->twQ; tb.twW = p->twW;
+    return tb;
+}
+
+CampBufs bufs(const sg_camp_plan *p, int B, int K) {
+    CampBufs bf;
+    bf.B = B; bf.K = K; bf.constel = p->constel;
+    bf.beta = p->beta; bf.y = p->y; bf.z = p->z; bf.buf0 = p->buf0; bf.buf1 = p->buf1;
+    bf.phi = p->phi; bf.tau = p->tau; bf.active = p->active;
+    bf.sec_sumsq = p->sec_sumsq; bf.sec_err = p->sec_err; bf.sec_idx = p->sec_idx; bf.sec_sym = p->sec_sym;
+    bf.true_idx = nullptr; bf.true_sym = nullptr;
+    return bf;
+}
+
+bool psk_order_ok(int K) { return K >= 1 && (K & (K - 1)) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int sg_camp_plan_destroy(sg_camp_plan *p) {
+    if (!p) return SG_OK;
+    if (p->ws) hipFree(p->ws);
+    for (void *a : p->allocs) hipFree(a);
+    delete p;
+    return SG_OK;
+}
+
+int sg_camp_plan_create(int ndim, const double *W, int Lr_in, int Lc_in, int L, int M, int n, const uint32_t *order0,
+                        const uint32_t *order1, sg_camp_plan **out) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(out && W && order0 && order1, "null argument");
+    SG_CHECK_ARG(ndim >= 0 && ndim <= 2, "W.ndim must be 0, 1 or 2");
+    SG_CHECK_ARG(L > 0 && M > 0 && n > 0 && (M & (M - 1)) == 0, "bad (L, M, n)");
+    int Lr = 1, Lc = 1;
+    if (ndim == 1) Lc = Lc_in;
+    if (ndim == 2) { Lr = Lr_in; Lc = Lc_in; }
+    SG_CHECK_ARG(Lr >= 1 && Lc >= 1, "bad base-matrix shape");
+    const long long LM = (long long)L * M;
+    SG_CHECK_ARG(LM < (1LL << 30), "L*M too large");
+    SG_CHECK_ARG(L % Lc == 0, "Lc must divide L");
+    SG_CHECK_ARG(ndim != 2 || n % Lr == 0, "Lr must divide n");
+    const int Mr = (ndim == 2) ? n / Lr : n;
+    const int Mc = (int)(LM / Lc);
+    int lg = 0;
+    while ((1LL << lg) < std::max(Mr + 2, Mc + 2)) ++lg;  // sparc.py:618,748
+    if (lg < CAMP_MIN_LOG2W || lg > CAMP_MAX_LOG2W)
+        return fail(SG_ERR_UNSUPPORTED, "complex transform size w=2^%d outside [2^%d, 2^%d]", lg, CAMP_MIN_LOG2W,
+                    CAMP_MAX_LOG2W);
+    std::unique_ptr<sg_camp_plan, int (*)(sg_camp_plan *)> p(new sg_camp_plan(), sg_camp_plan_destroy);
+    hipGetDevice(&p->device);
+    p->ndim = ndim; p->L = L; p->M = M; p->LM = (int)LM; p->n = n; p->Lr = Lr; p->Lc = Lc; p->Mr = Mr; p->Mc = Mc;
+    const int w = 1 << lg;
+    p->w = w;
+    p->log2P = lg / 2; p->log2Q = lg - p->log2P;
+    p->P = 1 << p->log2P; p->Q = 1 << p->log2Q;
+    p->CT = std::min(8, p->Q);
+    p->RT = std::min(8, p->P);
+    std::vector<double> Wv(W, W + (ndim == 0 ? 1 : (size_t)Lr * Lc));
+    // transforms = nonzero blocks in row-major order (sparc.py:758-771)
+    std::vector<int32_t> t_row, t_col;
+    std::vector<double> t_scale;
+    for (int r = 0; r < Lr; ++r)
+        for (int c = 0; c < Lc; ++c) {
+            const double wv = (ndim == 0) ? Wv[0] : Wv[(size_t)r * Lc + c];
+            SG_CHECK_ARG(wv >= 0.0, "negative base-matrix entry");
+            if (wv != 0.0) {
+                t_row.push_back(r); t_col.push_back(c);
+                t_scale.push_back(std::sqrt(wv / L));  // np.sqrt(W/L)
+            }
+        }
+    const int nT = p->nT = (int)t_row.size();
+    SG_CHECK_ARG(nT > 0, "base matrix is all zero");
+    SG_CHECK_ARG((long long)nT * w < (1LL << 31), "design too large");
+    std::vector<int32_t> col_ptr(Lc + 1, 0), col_t, row_ptr(Lr + 1, 0), row_t;
+    for (int c = 0; c < Lc; ++c) {
+        for (int t = 0; t < nT; ++t)
+            if (t_col[t] == c) col_t.push_back(t);
+        col_ptr[c + 1] = (int32_t)col_t.size();
+    }
+    for (int r = 0; r < Lr; ++r) {
+        for (int t = 0; t < nT; ++t)
+            if (t_row[t] == r) row_t.push_back(t);
+        row_ptr[r + 1] = (int32_t)row_t.size();
+    }
+    std::vector<int32_t> in0((size_t)nT * w, -1), in1((size_t)nT * w, -1), pos0((size_t)nT * Mr), pos1((size_t)nT * Mc);
+    const int P = p->P, Q = p->Q;
+    for (int t = 0; t < nT; ++t) {
+        for (int i = 0; i < Mr; ++i) {
+            const uint32_t k = order0[(size_t)t * Mr + i];
+            SG_CHECK_ARG(k < (uint32_t)w && in0[(size_t)t * w + k] < 0, "order0 entry out of range or repeated");
+            in0[(size_t)t * w + k] = i;
+            pos0[(size_t)t * Mr + i] = (int32_t)((k % P) * Q + k / P);
+        }
+        for (int j = 0; j < Mc; ++j) {
+            const uint32_t k = order1[(size_t)t * Mc + j];
+            SG_CHECK_ARG(k < (uint32_t)w && in1[(size_t)t * w + k] < 0, "order1 entry out of range or repeated");
+            in1[(size_t)t * w + k] = j;
+            pos1[(size_t)t * Mc + j] = (int32_t)((k % P) * Q + k / P);
+        }
+    }
+    sg_camp_plan *q = p.get();
+    SG_TRY(upload(q, &q->t_row, t_row)); SG_TRY(upload(q, &q->t_col, t_col)); SG_TRY(upload(q, &q->t_scale, t_scale));
+    SG_TRY(upload(q, &q->col_ptr, col_ptr)); SG_TRY(upload(q, &q->col_t, col_t));
+    SG_TRY(upload(q, &q->row_ptr, row_ptr)); SG_TRY(upload(q, &q->row_t, row_t));
+    SG_TRY(upload(q, &q->in0, in0)); SG_TRY(upload(q, &q->in1, in1));
+    SG_TRY(upload(q, &q->pos0, pos0)); SG_TRY(upload(q, &q->pos1, pos1));
+    SG_TRY(upload(q, &q->dW, Wv));
+    SG_TRY(upload(q, &q->twP, twiddles(P))); SG_TRY(upload(q, &q->twQ, twiddles(Q)));
+    SG_TRY(upload(q, &q->twW, twiddles(w)));
+    SG_TRY(upload(q, &q->constel, std::vector<cxd>(CAMP_MAX_K, cxd{1.0, 0.0})));
+    *out = p.release();
+    return SG_OK;
+}
+
+int sg_camp_plan_info(const sg_camp_plan *p, int *w, int *nT, int *Mr, int *Mc, int *P, int *Q) {
+    SG_CHECK_ARG(p, "plan is NULL");
+    if (w) *w = p->w;
+    if (nT) *nT = p->nT;
+    if (Mr) *Mr = p->Mr;
+    if (Mc) *Mc = p->Mc;
+    if (P) *P = p->P;
+    if (Q) *Q = p->Q;
+    return SG_OK;
+}
+
+int sg_camp_apply(sg_camp_plan *p, int transpose, const double *in, int B, double *out) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p && in && out, "null argument");
+    SG_CHECK_ARG(B >= 0, "negative batch");
+    if (B == 0) return SG_OK;
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = lib_stream();
+    SG_TRY(ensure_ws(p, B, 2));
+    const CampTables tb = tables(p);
+    const CampBufs bf = bufs(p, B, 1);
+    const size_t nin = (size_t)B * (transpose ? p->n : p->LM), nout = (size_t)B * (transpose ? p->LM : p->n);
+    const std::vector<int32_t> ones(B, 1);
+    SG_HIP(hipMemcpyAsync(p->active, ones.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    SG_HIP(hipMemcpyAsync(transpose ? p->z : p->beta, in, nin * sizeof(cxd), hipMemcpyHostToDevice, s));
+    const std::vector<double> ph((size_t)B * p->Lr, 1.0);
+    if (transpose) SG_HIP(hipMemcpyAsync(p->phi, ph.data(), sizeof(double) * ph.size(), hipMemcpyHostToDevice, s));
+    SG_TRY(camp_launch_fft(tb, bf, transpose != 0, s));
+    if (transpose) SG_TRY(camp_launch_colgather(tb, bf, p->io, s));
+    else SG_TRY(camp_launch_rowsum(tb, bf, p->io, s));
+    SG_HIP(hipMemcpyAsync(out, p->io, nout * sizeof(cxd), hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));  // (also keeps the host vectors above alive long enough)
+    return SG_OK;
+}
+
+int sg_camp_decode(sg_camp_plan *p, const double *y, int B, int K, const double *constel, const int32_t *true_idx,
+                   const int32_t *true_sym, double awgn_var, int t_max, double rtol, int phi_method, int32_t *map_idx,
+                   int32_t *map_sym, int32_t *t_final, double *nmse, double *psi) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    SG_CHECK_ARG(B >= 0, "negative batch");
+    if (B == 0) return SG_OK;
+    SG_CHECK_ARG(y && map_idx && t_final && nmse && psi, "null host buffer");
+    SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
+    SG_CHECK_ARG(rtol > 0 && rtol < 1, "rtol must be in (0, 1)");
+    SG_CHECK_ARG(phi_method == 1 || phi_method == 2, "phi_est_method must be 1 or 2");
+    SG_CHECK_ARG(awgn_var >= 0, "awgn_var must be >= 0");
+    SG_CHECK_ARG(psk_order_ok(K), "K must be 1 or a power of two");
+    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    SG_CHECK_ARG(K == 1 || (constel && map_sym), "K > 1 needs the constellation and map_sym");
+    SG_CHECK_ARG(K == 1 || !true_idx || true_sym, "K > 1 with true_idx needs true_sym");
+    if (true_idx)
+        for (size_t i = 0; i < (size_t)B * p->L; ++i) {
+            SG_CHECK_ARG(true_idx[i] >= 0 && true_idx[i] < p->M, "true_idx out of range");
+            SG_CHECK_ARG(K == 1 || (true_sym[i] >= 0 && true_sym[i] < K), "true_sym out of range");
+        }
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = lib_stream();
+    SG_TRY(ensure_ws(p, B, t_max));
+    const CampTables tb = tables(p);
+    CampBufs bf = bufs(p, B, K);
+    SG_HIP(hipMemcpyAsync(p->y, y, (size_t)B * p->n * sizeof(cxd), hipMemcpyHostToDevice, s));
+    if (K > 1) SG_HIP(hipMemcpyAsync(p->constel, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
+    if (true_idx) {
+        SG_HIP(hipMemcpyAsync(p->true_idx, true_idx, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
+        bf.true_idx = p->true_idx;
+        if (K > 1) {
+            SG_HIP(hipMemcpyAsync(p->true_sym, true_sym, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
+            bf.true_sym = p->true_sym;
+        }
+    }
+    AmpScalars sc;
+    sc.psi = p->psi; sc.psi_prev = p->psi_prev; sc.phi_prev = p->phi_prev; sc.gamma = p->gamma; sc.bcoef = p->bco;
+    sc.nmse = p->nmse; sc.t_final = p->t_final;
+    AmpParams pr;
+    pr.W = p->dW; pr.awgn_var = awgn_var; pr.rtol = rtol;
+    pr.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
+    pr.phi_method = phi_method; pr.t_max = t_max;
+    SG_HIP(hipMemsetAsync(p->beta, 0, (size_t)B * p->LM * sizeof(cxd), s));
+    SG_HIP(hipMemsetAsync(p->sec_idx, 0, sizeof(int32_t) * B * p->L, s));
+    SG_HIP(hipMemsetAsync(p->sec_sym, 0, sizeof(int32_t) * B * p->L, s));
+    SG_TRY(camp_launch_control(tb, bf, sc, pr, 2, 0, s));
+    std::vector<int32_t> act(B);
+    for (int t = 0; t < t_max - 1; ++t) {
+        if (t > 0) SG_TRY(camp_launch_fft(tb, bf, false, s));
+        SG_TRY(camp_launch_control(tb, bf, sc, pr, 0, t, s));
+        SG_TRY(camp_launch_fft(tb, bf, true, s));
+        SG_TRY(camp_launch_eta(tb, bf, s));
+        SG_TRY(camp_launch_control(tb, bf, sc, pr, 1, t, s));
+        if (t % 4 == 3 && t + 1 < t_max - 1) {  // skip the remaining launches once every codeword stopped
+            SG_HIP(hipMemcpyAsync(act.data(), p->active, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+            SG_HIP(hipStreamSynchronize(s));
+            int na = 0;
+            for (int b = 0; b < B; ++b) na += act[b] != 0;
+            if (na == 0) break;
+        }
+    }
+    SG_HIP(hipMemcpyAsync(map_idx, p->sec_idx, sizeof(int32_t) * B * p->L, hipMemcpyDeviceToHost, s));
+    if (map_sym) SG_HIP(hipMemcpyAsync(map_sym, p->sec_sym, sizeof(int32_t) * B * p->L, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(t_final, p->t_final, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(nmse, p->nmse, sizeof(double) * B * t_max * p->Lc, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(psi, p->psi, sizeof(double) * B * p->Lc, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    return SG_OK;
+}
+
+// x[L*M] (interleaved complex if x_is_complex, else real) holds s / tau with
+// tau already halved for complex s; out[L*M] is interleaved complex.
+int sg_section_mmse_psk(const double *x, int L, int M, int K, const double *constel, int x_is_complex, double *out) {
+    SG_CHECK_ARG(x && out && L >= 0 && M > 0, "bad arguments");
+    SG_CHECK_ARG(psk_order_ok(K) && (K == 1 || constel), "K must be 1 or a power of two with its constellation");
+    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    if (L == 0) return SG_OK;
+    SG_TRY(ensure_device());
+    hipStream_t s = lib_stream();
+    const size_t N = (size_t)L * M;
+    std::vector<cxd> hx(N);
+    for (size_t i = 0; i < N; ++i) hx[i] = x_is_complex ? cxd{x[2 * i], x[2 * i + 1]} : cxd{x[i], 0.0};
+    cxd *d = nullptr;
+    SG_HIP(hipMalloc((void **)&d, (2 * N + CAMP_MAX_K) * sizeof(cxd)));
+    cxd *dout = d + N, *dc = d + 2 * N;
+    int rc = SG_OK;
+    auto run = [&]() -> int {
+        SG_HIP(hipMemcpyAsync(d, hx.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
+        if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
+        SG_TRY(camp_launch_mmse(d, L, M, K, dc, dout, s));
+        SG_HIP(hipMemcpyAsync(out, dout, N * sizeof(cxd), hipMemcpyDeviceToHost, s));
+        SG_HIP(hipStreamSynchronize(s));
+        return SG_OK;
+    };
+    rc = run();
+    hipFree(d);
+    return rc;
+}
+
+// s[L*M] as above; idx[L] the MAP location, sym[L] the constellation index
+// (0 for K = 1; may be NULL then).
+int sg_section_map_psk(const double *sv, int L, int M, int K, const double *constel, int s_is_complex, int32_t *idx,
+                       int32_t *sym) {
+    SG_CHECK_ARG(sv && idx && L >= 0 && M > 0, "bad arguments");
+    SG_CHECK_ARG(psk_order_ok(K) && (K == 1 || (constel && sym)), "K must be 1 or a power of two with its constellation");
+    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    if (L == 0) return SG_OK;
+    SG_TRY(ensure_device());
+    hipStream_t s = lib_stream();
+    const size_t N = (size_t)L * M;
+    std::vector<cxd> hs(N);
+    for (size_t i = 0; i < N; ++i) hs[i] = s_is_complex ? cxd{sv[2 * i], sv[2 * i + 1]} : cxd{sv[i], 0.0};
+    std::vector<int32_t> hsym(L);
+    cxd *d = nullptr;
+    SG_HIP(hipMalloc((void **)&d, (N + CAMP_MAX_K) * sizeof(cxd) + 2 * (size_t)L * sizeof(int32_t)));
+    cxd *dc = d + N;
+    int32_t *di = (int32_t *)(dc + CAMP_MAX_K), *dsym = di + L;
+    auto run = [&]() -> int {
+        SG_HIP(hipMemcpyAsync(d, hs.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
+        if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
+        SG_TRY(camp_launch_map(d, L, M, K, dc, di, dsym, s));
+        SG_HIP(hipMemcpyAsync(idx, di, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        SG_HIP(hipMemcpyAsync(hsym.data(), dsym, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        SG_HIP(hipStreamSynchronize(s));
+        return SG_OK;
+    };
+    const int rc = run();
+    hipFree(d);
+    if (rc == SG_OK && sym) std::memcpy(sym, hsym.data(), (size_t)L * sizeof(int32_t));
+    return rc;
+}
+
+}  // extern "C"

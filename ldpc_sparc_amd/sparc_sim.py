@@ -2,6 +2,11 @@
 
 sparc_sim(code_params, decode_params, awgn_var, rand_seed) returns the
 reference's result dict (sparc_sim.py:8-58); the decoder runs on the GPU.
+Complex SPARCs, unmodulated or K-PSK modulated (K up to 64), run on the
+complex engine in double precision; modulated codes add the location / value
+error statistics of calc_ler_ver.  Out of scope (NotImplementedError): real
+K=2 modulated SPARCs on the DCT engines, and state evolution for complex PSK
+with K>2 (sparc_se.py).
 """
 import numpy as np
 
@@ -18,11 +23,22 @@ def sparc_sim(code_params, decode_params, awgn_var, rand_seed=None):
     cer = 1.0 * (ber > 0)
     detect = 1.0 * (not (ber > 0) ^ expect)
     results = {'ber': ber, 'cer': cer, 't_final': T, 'nmse': nmse, 'detect': detect}
-    if code_params['modulated']:
-        raise NotImplementedError("modulated SPARCs are not part of the GPU engine")
-    ser, loc_of_sec_errs, num_of_sec_errs = calc_ser(beta0, beta, code_params['L'])
-    results.update({'ser': ser, 'loc_of_sec_errs': loc_of_sec_errs,
-                    'num_of_sec_errs': num_of_sec_errs})
+    if not code_params['modulated']:
+        ser, loc_of_sec_errs, num_of_sec_errs = calc_ser(beta0, beta, code_params['L'])
+        results.update({'ser': ser, 'loc_of_sec_errs': loc_of_sec_errs,
+                        'num_of_sec_errs': num_of_sec_errs})
+    else:
+        err_rates, loc_of_errs, num_of_errs = calc_ler_ver(beta0, beta, code_params['L'], code_params['K'])
+        ler, ver, ser = err_rates
+        loc_of_loc_errs, loc_of_val_errs, loc_of_sec_errs = loc_of_errs
+        num_of_loc_errs, num_of_val_errs, num_of_sec_errs = num_of_errs
+        results.update({'ser': ser, 'ler': ler, 'ver': ver,
+                        'loc_of_sec_errs': loc_of_sec_errs,
+                        'loc_of_loc_errs': loc_of_loc_errs,
+                        'loc_of_val_errs': loc_of_val_errs,
+                        'num_of_sec_errs': num_of_sec_errs,
+                        'num_of_loc_errs': num_of_loc_errs,
+                        'num_of_val_errs': num_of_val_errs})
     return results
 
 
@@ -45,6 +61,28 @@ def calc_ser(beta0, beta, L):
     err = np.any(beta.reshape(L, M) != beta0.reshape(L, M), axis=1)
     num = int(np.count_nonzero(err))
     return num / L, np.flatnonzero(err), num
+
+
+def calc_ler_ver(beta0, beta, L, K):
+    """Location, value and section error rates of a modulated message vector
+    (sparc_sim.py:100-175): ((ler, ver, ser), (loc_of_loc_errs, loc_of_val_errs,
+    loc_of_sec_errs), (num_of_loc_errs, num_of_val_errs, num_of_sec_errs))."""
+    assert beta.size == beta0.size, 'beta and beta0 are of different size'
+    assert beta.dtype == beta0.dtype, 'beta and beta0 are of different type'
+    assert type(L) == int and L > 0
+    assert beta.size % L == 0
+    M = beta.size // L
+    b0, b = beta0.reshape(L, M), beta.reshape(L, M)
+    r0, c0 = np.nonzero(b0)
+    r1, c1 = np.nonzero(b)
+    assert np.array_equal(r0, np.arange(L))  # exactly one nonzero per section
+    assert np.array_equal(r1, np.arange(L))
+    loc_err = c0 != c1
+    val_err = b0[r0, c0] != b[r1, c1]
+    sec_err = np.logical_or(loc_err, val_err)
+    nums = tuple(int(np.count_nonzero(e)) for e in (loc_err, val_err, sec_err))
+    return (tuple(k / L for k in nums),
+            tuple(np.flatnonzero(e) for e in (loc_err, val_err, sec_err)), nums)
 
 
 def awgn_channel(input_array, awgn_var, rand_seed):
