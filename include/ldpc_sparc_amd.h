@@ -240,9 +240,18 @@ int sg_ldpc_encode_device(sg_ldpc_encoder *e, const uint8_t *d_info, int B, uint
 /* SPARC state evolution (sparc_public/sparc_se.py:82-183): Monte-Carlo samples
  * u [mc][M] (the reference's np.random.randn draw) stay on the device;
  * sg_se_expectation evaluates sparc_se_E (:82-115) for nt values of tau at
- * once (K = 1, or K = 2 for real modulated SPARCs). */
+ * once (K = 1, or K = 2 for real modulated SPARCs).  Complex K-PSK SPARCs,
+ * K = 4 .. 64 (a power of two; larger: SG_ERR_UNSUPPORTED), take complex
+ * samples u [mc][M] interleaved double[2] (the reference's randn + 1j randn,
+ * :154-155) from sg_se_samples_create_complex: K = 4 is the closed form in
+ * sinh / cosh of the real and imaginary parts (:95-98), K >= 8 the mean over
+ * the constellation of exp(Re(. conj c_k)) (:99-111), evaluated with the
+ * section's largest exponent subtracted -- the same quantity wherever the
+ * reference's unguarded exp is finite.  K >= 4 on real samples and K <= 2 on
+ * complex samples are SG_ERR_INVALID. */
 typedef struct sg_se_samples sg_se_samples;
 int sg_se_samples_create(const double *u, int mc, int M, sg_se_samples **out);
+int sg_se_samples_create_complex(const double *u, int mc, int M, sg_se_samples **out);
 int sg_se_samples_destroy(sg_se_samples *h);
 int sg_se_expectation(sg_se_samples *h, int K, const double *taus, int nt, double *E);
 
@@ -392,6 +401,54 @@ int sg_camp_decode(sg_camp_plan *p, const double *y, int B, int K, const double 
                    const int32_t *true_idx, const int32_t *true_sym, double awgn_var, int t_max,
                    double rtol, int phi_method, int32_t *map_idx, int32_t *map_sym,
                    int32_t *t_final, double *nmse, double *psi);
+/* Device variant (sg_camp_decode is upload -> this -> download): d_y [B][n]
+ * interleaved complex, only read; every d_* output may be NULL.  constel stays
+ * a host array.  The checks of sg_camp_decode apply except the range scan of
+ * the true indices: d_true_idx must lie in [0, M) and d_true_sym in [0, K).
+ * The decoder's state lives in the plan, so one call at a time per plan; the
+ * host polls the codewords' `active` flags every four iterations (the only
+ * synchronisation), otherwise the call returns without synchronising. */
+int sg_camp_decode_device(sg_camp_plan *p, const void *d_y, int B, int K, const double *constel,
+                          const int32_t *d_true_idx, const int32_t *d_true_sym, double awgn_var, int t_max,
+                          double rtol, int phi_method, int32_t *d_map_idx, int32_t *d_map_sym,
+                          int32_t *d_t_final, double *d_nmse, double *d_psi, void *stream);
+
+/* Device-resident Monte-Carlo campaign of a complex / K-PSK SPARC (all d_*
+ * device pointers; Philox generation as "device encoder and channel" above):
+ *   sg_rng_bits_device               B x L (logM + logK) message bits
+ *   sg_bits_to_psk_sections_device   bits -> location and constellation index
+ *   sg_camp_encode_device            x = A beta0
+ *   sg_awgn_device                   complex AWGN of variance awgn_var is
+ *       sg_awgn_device(SG_F64, seed, stream_id, d_x, B, 2 * n, sqrt(awgn_var / 2),
+ *       d_y, stream) on the interleaved reals (sparc_sim.py:179-204, complex
+ *       branch): there is no complex noise entry point
+ *   sg_camp_decode_device            AMP
+ *   sg_camp_count_errors_device      error counters. */
+/* d_bits [B][L*(logM+logK)] uint8 -> per section the location d_idx [B][L] from
+ * logM MSB-first bits and the constellation index d_sym [B][L] = gray2bin of
+ * the following logK Gray-coded PSK bits (bin_arr_2_msg_vector, sparc.py:330-364).
+ * logK = 0 (K = 1): d_sym may be NULL, and is written as zero otherwise. */
+int sg_bits_to_psk_sections_device(const uint8_t *d_bits, int B, int L, int logM, int logK, int32_t *d_idx,
+                                   int32_t *d_sym, void *stream);
+/* x = A beta0 [B][n] interleaved complex, beta0 with constel[d_sym] (1 for
+ * K = 1, where constel and d_sym may be NULL) at location d_idx of every
+ * section (sparc.py:17-53 sparc_encode); constel is the host's psk_constel(K)
+ * as for sg_camp_decode.  A location outside [0, M) or a constellation index
+ * outside [0, K) leaves its section empty. */
+int sg_camp_encode_device(sg_camp_plan *p, int K, const double *constel, const int32_t *d_idx,
+                          const int32_t *d_sym, int B, void *d_x, void *stream);
+/* Adds {section errors, location errors, value errors, bit errors, codeword
+ * errors, sum of t_final} into int64 d_counts[6]; if d_rows is not NULL also
+ * writes int32 d_rows[B][4] = {bit, section, location, value errors} of each
+ * codeword.  As calc_ler_ver (sparc_sim.py:100-175) and calc_ber over
+ * msg_vector_2_bin_arr (sparc.py:366-400): location error = locations differ;
+ * value error = constellation indices differ, wherever the location is;
+ * section error = either; bit errors = popcount(idx ^ idx') +
+ * popcount(gray(sym) ^ gray(sym')); codeword error = any bit error.
+ * logK = 0: the *_sym pointers are ignored (may be NULL). */
+int sg_camp_count_errors_device(const int32_t *d_map_idx, const int32_t *d_map_sym, const int32_t *d_true_idx,
+                                const int32_t *d_true_sym, const int32_t *d_t_final, int B, int L, int logM,
+                                int logK, int64_t *d_counts, int32_t *d_rows, void *stream);
 /* Stand-alone K-PSK section estimators (sparc.py:402-512).  x = s / tau with
  * tau already halved for complex s, [L*M] interleaved complex if x_is_complex
  * else real; out[L*M] interleaved complex (imaginary part 0 for K <= 2). */

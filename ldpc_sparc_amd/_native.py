@@ -92,6 +92,12 @@ SIGNATURES = [
     ("sg_camp_apply", ct.c_int, [vp, ct.c_int, vp, ct.c_int, vp]),
     ("sg_camp_decode", ct.c_int, [vp, vp, ct.c_int, ct.c_int, vp, vp, vp, ct.c_double, ct.c_int, ct.c_double,
                                   ct.c_int, vp, vp, vp, vp, vp]),
+    ("sg_camp_decode_device", ct.c_int, [vp, vp, ct.c_int, ct.c_int, vp, vp, vp, ct.c_double, ct.c_int, ct.c_double,
+                                         ct.c_int, vp, vp, vp, vp, vp, vp]),
+    ("sg_bits_to_psk_sections_device", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp, vp, vp]),
+    ("sg_camp_encode_device", ct.c_int, [vp, ct.c_int, vp, vp, vp, ct.c_int, vp, vp]),
+    ("sg_camp_count_errors_device", ct.c_int, [vp, vp, vp, vp, vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp, vp,
+                                               vp]),
     ("sg_section_mmse_psk", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, vp, ct.c_int, vp]),
     ("sg_section_map_psk", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, vp, ct.c_int, vp, vp]),
     ("Lxfb", ct.c_double, [dp, ct.c_long, ct.c_int]),
@@ -137,6 +143,7 @@ SIGNATURES = [
     ("sg_ldpc_encode_device", ct.c_int, [vp, vp, ct.c_int, vp, vp]),
     # state evolution
     ("sg_se_samples_create", ct.c_int, [vp, ct.c_int, ct.c_int, vp]),
+    ("sg_se_samples_create_complex", ct.c_int, [vp, ct.c_int, ct.c_int, vp]),
     ("sg_se_samples_destroy", ct.c_int, [vp]),
     ("sg_se_expectation", ct.c_int, [vp, ct.c_int, vp, ct.c_int, vp]),
     # integrated AMP <-> BP decoders

@@ -62,5 +62,14 @@ int camp_launch_colgather(const CampTables &tb, const CampBufs &bf, cxd *out, hi
 // stand-alone section estimators on device arrays of L sections
 int camp_launch_mmse(const cxd *x, int L, int M, int K, const cxd *constel, cxd *out, hipStream_t s);
 int camp_launch_map(const cxd *sv, int L, int M, int K, const cxd *constel, int32_t *idx, int32_t *sym, hipStream_t s);
+// campaign kernels (camp_campaign.hip): bits [B][L (logM + logK)] -> idx / sym [B][L] (sym may be null);
+// one-hot K-PSK beta0 into bf.beta (and bf.active = 1); error counters (sg_camp_count_errors_device)
+int camp_launch_bits_to_psk(const uint8_t *bits, int B, int L, int logM, int logK, int32_t *idx, int32_t *sym,
+                            hipStream_t s);
+int camp_launch_scatter(const CampTables &tb, const CampBufs &bf, const int32_t *idx, const int32_t *sym,
+                        hipStream_t s);
+int camp_launch_count(const int32_t *map_idx, const int32_t *map_sym, const int32_t *true_idx, const int32_t *true_sym,
+                      const int32_t *t_final, int B, int L, int logM, int logK, int64_t *counts, int32_t *rows,
+                      hipStream_t s);
 
 }  // namespace sg

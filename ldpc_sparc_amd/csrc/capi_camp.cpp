@@ -27,6 +27,7 @@ struct sg_camp_plan {
            *psi_prev = nullptr, *phi_prev = nullptr, *gamma = nullptr, *bco = nullptr, *nmse = nullptr;
     int32_t *active = nullptr, *sec_idx = nullptr, *sec_sym = nullptr, *true_idx = nullptr, *true_sym = nullptr,
             *t_final = nullptr;
+    std::vector<cxd> h_constel;  // what `constel` holds (set_constel)
 };
 
 namespace {
@@ -121,6 +122,21 @@ CampBufs bufs(const sg_camp_plan *p, int B, int K) {
 }
 
 bool psk_order_ok(int K) { return K >= 1 && (K & (K - 1)) == 0; }
+
+constexpr int CAMP_MAX_B = 65535;  // the batch is a grid dimension of every kernel
+
+// The plan's device constellation, uploaded from the plan's own host copy (an
+// asynchronous copy must not outlive the caller's array) when it changes.
+int set_constel(sg_camp_plan *p, int K, const double *constel, hipStream_t s) {
+    if (K <= 1) return SG_OK;
+    const cxd *c = reinterpret_cast<const cxd *>(constel);
+    if ((int)p->h_constel.size() == K && std::memcmp(p->h_constel.data(), c, (size_t)K * sizeof(cxd)) == 0)
+        return SG_OK;
+    SG_HIP(hipStreamSynchronize(s));  // an earlier upload may still read h_constel
+    p->h_constel.assign(c, c + K);
+    SG_HIP(hipMemcpyAsync(p->constel, p->h_constel.data(), (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
+    return SG_OK;
+}
 
 }  // namespace
 
@@ -256,12 +272,72 @@ int sg_camp_apply(sg_camp_plan *p, int transpose, const double *in, int B, doubl
     return SG_OK;
 }
 
+int sg_camp_decode_device(sg_camp_plan *p, const void *d_y, int B, int K, const double *constel,
+                          const int32_t *d_true_idx, const int32_t *d_true_sym, double awgn_var, int t_max, double rtol,
+                          int phi_method, int32_t *d_map_idx, int32_t *d_map_sym, int32_t *d_t_final, double *d_nmse,
+                          double *d_psi, void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B, "batch must be in [0, 65535]");
+    if (B == 0) return SG_OK;
+    SG_CHECK_ARG(d_y, "null received words");
+    SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
+    SG_CHECK_ARG(rtol > 0 && rtol < 1, "rtol must be in (0, 1)");
+    SG_CHECK_ARG(phi_method == 1 || phi_method == 2, "phi_est_method must be 1 or 2");
+    SG_CHECK_ARG(awgn_var >= 0, "awgn_var must be >= 0");
+    SG_CHECK_ARG(psk_order_ok(K), "K must be 1 or a power of two");
+    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    SG_CHECK_ARG(K == 1 || constel, "K > 1 needs the constellation");
+    SG_CHECK_ARG(K == 1 || !d_true_idx || d_true_sym, "K > 1 with true_idx needs true_sym");
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = pick_stream(stream);
+    SG_TRY(ensure_ws(p, B, t_max));
+    SG_TRY(set_constel(p, K, constel, s));
+    const CampTables tb = tables(p);
+    // y is only read (z = y at t = 0); outputs the caller does not want land in the workspace
+    CampBufs bf = bufs(p, B, K);
+    bf.y = (const cxd *)d_y;
+    bf.sec_idx = d_map_idx ? d_map_idx : p->sec_idx;
+    bf.sec_sym = d_map_sym ? d_map_sym : p->sec_sym;
+    bf.true_idx = d_true_idx;
+    bf.true_sym = (K > 1 && d_true_idx) ? d_true_sym : nullptr;
+    AmpScalars sc;
+    sc.psi = d_psi ? d_psi : p->psi; sc.psi_prev = p->psi_prev; sc.phi_prev = p->phi_prev; sc.gamma = p->gamma;
+    sc.bcoef = p->bco;
+    sc.nmse = d_nmse ? d_nmse : p->nmse; sc.t_final = d_t_final ? d_t_final : p->t_final;
+    AmpParams pr;
+    pr.W = p->dW; pr.awgn_var = awgn_var; pr.rtol = rtol;
+    pr.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
+    pr.phi_method = phi_method; pr.t_max = t_max;
+    SG_HIP(hipMemsetAsync(p->beta, 0, (size_t)B * p->LM * sizeof(cxd), s));
+    SG_HIP(hipMemsetAsync(bf.sec_idx, 0, sizeof(int32_t) * B * p->L, s));
+    SG_HIP(hipMemsetAsync(bf.sec_sym, 0, sizeof(int32_t) * B * p->L, s));
+    SG_TRY(camp_launch_control(tb, bf, sc, pr, 2, 0, s));
+    std::vector<int32_t> act(B);
+    for (int t = 0; t < t_max - 1; ++t) {
+        if (t > 0) SG_TRY(camp_launch_fft(tb, bf, false, s));
+        SG_TRY(camp_launch_control(tb, bf, sc, pr, 0, t, s));
+        SG_TRY(camp_launch_fft(tb, bf, true, s));
+        SG_TRY(camp_launch_eta(tb, bf, s));
+        SG_TRY(camp_launch_control(tb, bf, sc, pr, 1, t, s));
+        if (t % 4 == 3 && t + 1 < t_max - 1) {  // skip the remaining launches once every codeword stopped
+            SG_HIP(hipMemcpyAsync(act.data(), p->active, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+            SG_HIP(hipStreamSynchronize(s));
+            int na = 0;
+            for (int b = 0; b < B; ++b) na += act[b] != 0;
+            if (na == 0) break;
+        }
+    }
+    return SG_OK;
+}
+
+// upload -> sg_camp_decode_device on the plan's own buffers -> download
 int sg_camp_decode(sg_camp_plan *p, const double *y, int B, int K, const double *constel, const int32_t *true_idx,
                    const int32_t *true_sym, double awgn_var, int t_max, double rtol, int phi_method, int32_t *map_idx,
                    int32_t *map_sym, int32_t *t_final, double *nmse, double *psi) {
     SG_TRY(ensure_device());
     SG_CHECK_ARG(p, "plan is NULL");
-    SG_CHECK_ARG(B >= 0, "negative batch");
+    SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B, "batch must be in [0, 65535]");
     if (B == 0) return SG_OK;
     SG_CHECK_ARG(y && map_idx && t_final && nmse && psi, "null host buffer");
     SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
@@ -280,44 +356,14 @@ int sg_camp_decode(sg_camp_plan *p, const double *y, int B, int K, const double 
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = lib_stream();
     SG_TRY(ensure_ws(p, B, t_max));
-    const CampTables tb = tables(p);
-    CampBufs bf = bufs(p, B, K);
     SG_HIP(hipMemcpyAsync(p->y, y, (size_t)B * p->n * sizeof(cxd), hipMemcpyHostToDevice, s));
-    if (K > 1) SG_HIP(hipMemcpyAsync(p->constel, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
     if (true_idx) {
         SG_HIP(hipMemcpyAsync(p->true_idx, true_idx, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
-        bf.true_idx = p->true_idx;
-        if (K > 1) {
-            SG_HIP(hipMemcpyAsync(p->true_sym, true_sym, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
-            bf.true_sym = p->true_sym;
-        }
+        if (K > 1) SG_HIP(hipMemcpyAsync(p->true_sym, true_sym, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
     }
-    AmpScalars sc;
-    sc.psi = p->psi; sc.psi_prev = p->psi_prev; sc.phi_prev = p->phi_prev; sc.gamma = p->gamma; sc.bcoef = p->bco;
-    sc.nmse = p->nmse; sc.t_final = p->t_final;
-    AmpParams pr;
-    pr.W = p->dW; pr.awgn_var = awgn_var; pr.rtol = rtol;
-    pr.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
-    pr.phi_method = phi_method; pr.t_max = t_max;
-    SG_HIP(hipMemsetAsync(p->beta, 0, (size_t)B * p->LM * sizeof(cxd), s));
-    SG_HIP(hipMemsetAsync(p->sec_idx, 0, sizeof(int32_t) * B * p->L, s));
-    SG_HIP(hipMemsetAsync(p->sec_sym, 0, sizeof(int32_t) * B * p->L, s));
-    SG_TRY(camp_launch_control(tb, bf, sc, pr, 2, 0, s));
-    std::vector<int32_t> act(B);
-    for (int t = 0; t < t_max - 1; ++t) {
-        if (t > 0) SG_TRY(camp_launch_fft(tb, bf, false, s));
-        SG_TRY(camp_launch_control(tb, bf, sc, pr, 0, t, s));
-        SG_TRY(camp_launch_fft(tb, bf, true, s));
-        SG_TRY(camp_launch_eta(tb, bf, s));
-        SG_TRY(camp_launch_control(tb, bf, sc, pr, 1, t, s));
-        if (t % 4 == 3 && t + 1 < t_max - 1) {  // skip the remaining launches once every codeword stopped
-            SG_HIP(hipMemcpyAsync(act.data(), p->active, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-            SG_HIP(hipStreamSynchronize(s));
-            int na = 0;
-            for (int b = 0; b < B; ++b) na += act[b] != 0;
-            if (na == 0) break;
-        }
-    }
+    SG_TRY(sg_camp_decode_device(p, p->y, B, K, constel, true_idx ? p->true_idx : nullptr,
+                                 (true_idx && K > 1) ? p->true_sym : nullptr, awgn_var, t_max, rtol, phi_method,
+                                 p->sec_idx, p->sec_sym, p->t_final, p->nmse, p->psi, nullptr));
     SG_HIP(hipMemcpyAsync(map_idx, p->sec_idx, sizeof(int32_t) * B * p->L, hipMemcpyDeviceToHost, s));
     if (map_sym) SG_HIP(hipMemcpyAsync(map_sym, p->sec_sym, sizeof(int32_t) * B * p->L, hipMemcpyDeviceToHost, s));
     SG_HIP(hipMemcpyAsync(t_final, p->t_final, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
@@ -325,6 +371,49 @@ int sg_camp_decode(sg_camp_plan *p, const double *y, int B, int K, const double 
     SG_HIP(hipMemcpyAsync(psi, p->psi, sizeof(double) * B * p->Lc, hipMemcpyDeviceToHost, s));
     SG_HIP(hipStreamSynchronize(s));
     return SG_OK;
+}
+
+int sg_bits_to_psk_sections_device(const uint8_t *d_bits, int B, int L, int logM, int logK, int32_t *d_idx,
+                                   int32_t *d_sym, void *stream) {
+    SG_CHECK_ARG(d_bits && d_idx, "null device buffer");
+    SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B && L >= 0, "bad (B, L)");
+    SG_CHECK_ARG(logM >= 0 && logM <= 30 && logK >= 0 && logK <= 30 && logM + logK >= 1, "bad (logM, logK)");
+    SG_CHECK_ARG(logK == 0 || d_sym, "logK > 0 needs d_sym");
+    if (!B || !L) return SG_OK;
+    SG_TRY(ensure_device());
+    return camp_launch_bits_to_psk(d_bits, B, L, logM, logK, d_idx, d_sym, pick_stream(stream));
+}
+
+int sg_camp_encode_device(sg_camp_plan *p, int K, const double *constel, const int32_t *d_idx, const int32_t *d_sym,
+                          int B, void *d_x, void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p && d_idx && d_x, "null argument");
+    SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B, "batch must be in [0, 65535]");
+    if (B == 0) return SG_OK;
+    SG_CHECK_ARG(psk_order_ok(K), "K must be 1 or a power of two");
+    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    SG_CHECK_ARG(K == 1 || (constel && d_sym), "K > 1 needs the constellation and d_sym");
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = pick_stream(stream);
+    SG_TRY(ensure_ws(p, B, 2));
+    SG_TRY(set_constel(p, K, constel, s));
+    const CampTables tb = tables(p);
+    const CampBufs bf = bufs(p, B, K);
+    SG_TRY(camp_launch_scatter(tb, bf, d_idx, d_sym, s));
+    SG_TRY(camp_launch_fft(tb, bf, false, s));
+    return camp_launch_rowsum(tb, bf, (cxd *)d_x, s);
+}
+
+int sg_camp_count_errors_device(const int32_t *d_map_idx, const int32_t *d_map_sym, const int32_t *d_true_idx,
+                                const int32_t *d_true_sym, const int32_t *d_t_final, int B, int L, int logM, int logK,
+                                int64_t *d_counts, int32_t *d_rows, void *stream) {
+    SG_CHECK_ARG(d_map_idx && d_true_idx && d_t_final && d_counts, "null device buffer");
+    SG_CHECK_ARG(B >= 0 && L >= 0, "bad (B, L)");
+    SG_CHECK_ARG(logM >= 0 && logM <= 30 && logK >= 0 && logK <= 30, "bad (logM, logK)");
+    SG_CHECK_ARG(logK == 0 || (d_map_sym && d_true_sym), "logK > 0 needs the constellation indices");
+    SG_TRY(ensure_device());
+    return camp_launch_count(d_map_idx, d_map_sym, d_true_idx, d_true_sym, d_t_final, B, L, logM, logK, d_counts,
+                             d_rows, pick_stream(stream));
 }
 
 // x[L*M] (interleaved complex if x_is_complex, else real) holds s / tau with

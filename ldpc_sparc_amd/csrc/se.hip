@@ -5,16 +5,31 @@
 //
 //   K = 1:  E = mean_s  e^(1/tau + u_s0/sqrt(tau)) / (e^(1/tau + u_s0/sqrt(tau)) + sum_{j>0} e^(u_sj/sqrt(tau)))
 //   K = 2:  sinh / cosh in place of exp (real modulated SPARCs, :91-94)
+// Complex K-PSK SPARCs (complex samples u = randn + 1j randn, :154-155):
+//   K = 4:  E = mean_s  sinh(x0) / (cosh(x0) + cosh(Im u_s0/sqrt(tau))
+//                + sum_{j>0} cosh(Re u_sj/sqrt(tau)) + cosh(Im u_sj/sqrt(tau))),
+//           x0 = 1/tau + Re u_s0/sqrt(tau)  (:95-98)
+//   K >= 8: with g_0k = Re((1/tau + u_s0/sqrt(tau)) conj c_k) and
+//           g_jk = Re(u_sj/sqrt(tau) conj c_k) over the constellation c,
+//           E = mean_s  sum_k Re(c_k) e^(g_0k) / sum_{j>=0} sum_k e^(g_jk)
+//           (:99-113; the reference's means over k cancel), every exponent
+//           shifted by the sample's largest one so that no exp overflows.
 //
 // One wavefront per sample (lanes stride the M entries); per-block partial
 // sums, then a fixed-order sum, so E is deterministic.
 #include <algorithm>
+#include <cmath>
+#include <vector>
 
 #include "common.hpp"
 
+constexpr int SE_MAX_K = 64;  // largest PSK constellation, as the complex AMP engine
+
 struct sg_se_samples {
     int mc = 0, M = 0;
-    double *u = nullptr;     // [mc][M]
+    bool cplx = false;       // u holds interleaved complex samples
+    double *u = nullptr;     // [mc][M], or [mc][M][2]
+    double *constel = nullptr;  // [SE_MAX_K][2] K-PSK constellation of the last K >= 8 call
     double *part = nullptr;  // [nt_cap][nblk]
     int nt_cap = 0;
     double *taus = nullptr, *E = nullptr;
@@ -50,6 +65,55 @@ __global__ __launch_bounds__(256) void se_E_kernel(const double *__restrict__ u,
     }
 }
 
+// complex samples, K = 4 .. SE_MAX_K; c [K] is the constellation for K >= 8
+__global__ __launch_bounds__(256) void se_E_cplx_kernel(const double2 *__restrict__ u, int mc, int M, int K,
+                                                        const double2 *__restrict__ c, const double *taus, double *part,
+                                                        int nblk) {
+    __shared__ double red[SE_WAVES];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int s = blockIdx.x * SE_WAVES + wid, t = blockIdx.y;
+    const double itau = 1.0 / taus[t], rtau = sqrt(itau);
+    double e = 0.0;
+    if (s < mc) {
+        const double2 *row = u + (size_t)s * M;
+        const double x0 = itau + rtau * row[0].x, y0 = rtau * row[0].y;
+        if (K == 4) {
+            double cs = 0.0;
+            for (int j = 1 + lane; j < M; j += 64) cs += cosh(rtau * row[j].x) + cosh(rtau * row[j].y);
+            for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o, 64);
+            e = sinh(x0) / ((cosh(x0) + cosh(y0)) + cs);
+        } else {
+            double m = -INFINITY;
+            for (int k = 0; k < K; ++k) m = fmax(m, x0 * c[k].x + y0 * c[k].y);
+            for (int j = 1 + lane; j < M; j += 64) {
+                const double xj = rtau * row[j].x, yj = rtau * row[j].y;
+                for (int k = 0; k < K; ++k) m = fmax(m, xj * c[k].x + yj * c[k].y);
+            }
+            for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+            double cs = 0.0;
+            for (int j = 1 + lane; j < M; j += 64) {
+                const double xj = rtau * row[j].x, yj = rtau * row[j].y;
+                for (int k = 0; k < K; ++k) cs += exp(xj * c[k].x + yj * c[k].y - m);
+            }
+            for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o, 64);
+            double a = 0.0, b = 0.0;
+            for (int k = 0; k < K; ++k) {
+                const double w = exp(x0 * c[k].x + y0 * c[k].y - m);
+                a += c[k].x * w;
+                b += w;
+            }
+            e = a / (b + cs);
+        }
+    }
+    if (lane == 0) red[wid] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double v = 0.0;
+        for (int w = 0; w < SE_WAVES; ++w) v += red[w];
+        part[(size_t)t * nblk + blockIdx.x] = v;
+    }
+}
+
 __global__ void se_finish_kernel(const double *part, int nblk, int mc, double *E) {
     __shared__ double red[4];
     const int t = blockIdx.x;
@@ -69,13 +133,14 @@ using namespace sg;
 
 extern "C" {
 
-int sg_se_samples_create(const double *u, int mc, int M, sg_se_samples **out) {
+static int se_samples_create(const double *u, int mc, int M, bool cplx, sg_se_samples **out) {
     SG_CHECK_ARG(u && out && mc > 0 && M > 1, "bad argument");
     SG_TRY(ensure_device());
     sg_se_samples *h = new sg_se_samples();
     h->mc = mc;
     h->M = M;
-    const size_t bytes = (size_t)mc * M * 8;
+    h->cplx = cplx;
+    const size_t bytes = (size_t)mc * M * (cplx ? 16 : 8);
     if (hipMalloc(&h->u, bytes) != hipSuccess) {
         delete h;
         return fail(SG_ERR_NOMEM, "cannot allocate %zu bytes of samples", bytes);
@@ -89,9 +154,17 @@ int sg_se_samples_create(const double *u, int mc, int M, sg_se_samples **out) {
     return SG_OK;
 }
 
+int sg_se_samples_create(const double *u, int mc, int M, sg_se_samples **out) {
+    return se_samples_create(u, mc, M, false, out);
+}
+
+int sg_se_samples_create_complex(const double *u, int mc, int M, sg_se_samples **out) {
+    return se_samples_create(u, mc, M, true, out);
+}
+
 int sg_se_samples_destroy(sg_se_samples *h) {
     if (!h) return SG_OK;
-    for (void *p : {(void *)h->u, (void *)h->part, (void *)h->taus, (void *)h->E})
+    for (void *p : {(void *)h->u, (void *)h->part, (void *)h->taus, (void *)h->E, (void *)h->constel})
         if (p) hipFree(p);
     delete h;
     return SG_OK;
@@ -99,7 +172,9 @@ int sg_se_samples_destroy(sg_se_samples *h) {
 
 int sg_se_expectation(sg_se_samples *h, int K, const double *taus, int nt, double *E) {
     SG_CHECK_ARG(h && taus && E && nt >= 0, "bad argument");
-    SG_CHECK_ARG(K == 1 || K == 2, "state evolution supports K = 1 and K = 2 (real SPARCs)");
+    SG_CHECK_ARG(K >= 1 && (K & (K - 1)) == 0, "K must be 1 or a power of two");
+    if (K > SE_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, SE_MAX_K);
+    SG_CHECK_ARG(h->cplx == (K >= 4), "K = 1, 2 take real samples, K >= 4 complex samples");
     if (!nt) return SG_OK;
     SG_TRY(ensure_device());
     const int nblk = (h->mc + SE_WAVES - 1) / SE_WAVES;
@@ -115,7 +190,21 @@ int sg_se_expectation(sg_se_samples *h, int K, const double *taus, int nt, doubl
     }
     hipStream_t s = lib_stream();
     SG_HIP(hipMemcpyAsync(h->taus, taus, (size_t)nt * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(se_E_kernel, dim3(nblk, nt), dim3(256), 0, s, h->u, h->mc, h->M, K, h->taus, h->part, nblk);
+    std::vector<double> c;  // psk_constel, sparc.py:225-239 (alive until the synchronize below)
+    if (K >= 8) {
+        if (!h->constel) SG_HIP(hipMalloc(&h->constel, (size_t)SE_MAX_K * 16));
+        for (int k = 0; k < K; ++k) {
+            const double theta = 2.0 * M_PI * k / K;
+            c.push_back(std::cos(theta));
+            c.push_back(std::sin(theta));
+        }
+        SG_HIP(hipMemcpyAsync(h->constel, c.data(), c.size() * 8, hipMemcpyHostToDevice, s));
+    }
+    if (h->cplx)
+        hipLaunchKernelGGL(se_E_cplx_kernel, dim3(nblk, nt), dim3(256), 0, s, (const double2 *)h->u, h->mc, h->M, K,
+                           (const double2 *)h->constel, h->taus, h->part, nblk);
+    else
+        hipLaunchKernelGGL(se_E_kernel, dim3(nblk, nt), dim3(256), 0, s, h->u, h->mc, h->M, K, h->taus, h->part, nblk);
     hipLaunchKernelGGL(se_finish_kernel, dim3(nt), dim3(256), 0, s, h->part, nblk, h->mc, h->E);
     SG_HIP(hipGetLastError());
     SG_HIP(hipMemcpyAsync(E, h->E, (size_t)nt * 8, hipMemcpyDeviceToHost, s));

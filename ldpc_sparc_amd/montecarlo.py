@@ -12,7 +12,8 @@ rank the global counts that drive the stopping rule.
 
 Counters per point: [units, bit_errors, frame_errors, aux0, aux1] where aux
 is decoder-specific (BP: executed iterations; AMP: section errors, AMP
-iterations; concatenated: unprotected / protected bit errors).
+iterations; concatenated: unprotected / protected bit errors).  A trial may
+declare a longer vector with an `nc` attribute (CSparcTrial: 7).
 
 Checkpoint/resume: with `checkpoint_dir`, the global counters
 and next block of every point are written after each round; a restarted
@@ -85,7 +86,9 @@ def run_point(trial, point, *, block, blocks_per_round, rank, world, agg, min_er
               checkpoint_dir=None, tag="campaign", params=None, max_rounds=None):
     """Run one point until `min_errors` frame errors or `max_units` units
     (globally).  trial(point, first_block, n_blocks, block) -> int64[NC]
-    counters of the blocks [first_block, first_block + n_blocks).
+    counters of the blocks [first_block, first_block + n_blocks); a trial
+    with an `nc` attribute returns that many counters instead of NC, the first
+    three with the same meaning.
 
     A trial with `per_unit = True` returns int64[n_blocks * block, NC] (one
     row per codeword, in block order) instead; the round's rows of every rank
@@ -100,7 +103,8 @@ def run_point(trial, point, *, block, blocks_per_round, rank, world, agg, min_er
     different experiments.  `max_rounds` ends this call after that many rounds
     without marking the point done (an interrupted run; the checkpoint lets a
     later call continue it)."""
-    total = np.zeros(NC, dtype=np.int64)
+    nc = int(getattr(trial, "nc", NC))
+    total = np.zeros(nc, dtype=np.int64)
     next_block = 0
     done = False
     params = dict(params or {}, block=int(block))
@@ -134,10 +138,10 @@ def run_point(trial, point, *, block, blocks_per_round, rank, world, agg, min_er
             nb = min(nb, -(-(max_units - int(total[0])) // block))
         a, b = shard_range(nb, rank, world)
         if per_unit:
-            rows = np.zeros((nb * block, NC), dtype=np.int64)
+            rows = np.zeros((nb * block, nc), dtype=np.int64)
             if b > a:
                 rows[a * block:b * block] = trial(point, next_block + a, b - a, block)
-            rows = agg.allreduce(rows.ravel()).reshape(nb * block, NC)  # the one collective per round
+            rows = agg.allreduce(rows.ravel()).reshape(nb * block, nc)  # the one collective per round
             cut = len(rows)
             if min_errors is not None:
                 k = _first_reaching(total[2] + np.cumsum(rows[:, 2]), min_errors)
@@ -147,7 +151,7 @@ def run_point(trial, point, *, block, blocks_per_round, rank, world, agg, min_er
                 cut, done = max_units - int(total[0]), True
             total = total + rows[:cut].sum(axis=0)
         else:
-            local = trial(point, next_block + a, b - a, block) if b > a else np.zeros(NC, dtype=np.int64)
+            local = trial(point, next_block + a, b - a, block) if b > a else np.zeros(nc, dtype=np.int64)
             total = total + agg.allreduce(local)  # the campaign's one collective per round
         next_block += nb
         if checkpoint_dir and rank == 0:
@@ -291,6 +295,148 @@ class SparcTrial:
         _native.check(lib.sg_amp_count_errors_device(d_map.ptr, d_true.ptr, d_tf.ptr, B, L, logM, d_cnt.ptr, None))
         cnt = d_cnt.download(np.zeros(4, np.int64))
         return np.array([B, cnt[1], cnt[2], cnt[3], cnt[0]], dtype=np.int64)
+
+
+class CSparcTrial:
+    """Complex SPARC with the sub-sampled FFT design, unmodulated (K = 1) or
+    K-PSK modulated (K up to 64), over complex AWGN, generated and decoded on
+    the GPU in double precision: Philox bits -> (location, constellation
+    index) per section (sparc.py:330-364) -> x = A beta0 -> y = x + CN(0,
+    awgn_var) (sparc_sim.py:179-204, complex branch) -> AMP (sparc.py:883-999)
+    -> the error counts of calc_ber / calc_ler_ver.  Nothing crosses to the
+    host between the generation and the counters.
+
+    Counters (nc = 7): [codewords, bit errors, codeword errors, AMP
+    iterations, section errors, location errors, value errors]; with
+    `per_unit` one such row per codeword, in block order (run_point).  Block b
+    of point p draws its bits and its noise from the Philox stream
+    (p << 32) | b, one call per block, so results depend neither on the rank
+    count nor on how blocks are batched.
+
+    op: sparc.ComplexDesignOperator.  ONE design is shared by the whole
+    campaign, as in SparcTrial; sparc_sim instead draws a new design from
+    every seed, so a campaign estimates the error rate of a fixed design and
+    sparc_sim runs average over designs too."""
+
+    nc = 7
+
+    def __init__(self, op, K, awgn_vars, t_max=25, rtol=1e-6, phi_method=1, seed=0, per_unit=False):
+        from .sparc import _check_psk, _interleaved, psk_constel
+        if not getattr(op, "csparc", False):
+            raise ValueError("CSparcTrial needs a sparc.ComplexDesignOperator")
+        self.op, self.K, self.vars = op, int(K), list(awgn_vars)
+        _check_psk(self.K)
+        self.t_max, self.rtol, self.phi = int(t_max), float(rtol), int(phi_method)
+        self.seed, self.per_unit = int(seed), bool(per_unit)
+        self.logM = int(round(np.log2(op.M)))
+        self.logK = int(round(np.log2(self.K)))
+        self.bits_per_codeword = op.L * (self.logM + self.logK)
+        self.constel = _interleaved(psk_constel(self.K)) if self.K != 1 else None
+
+    def generate(self, point, first_block, n_blocks, block):
+        """Device buffers (d_true_idx int32 [B, L], d_true_sym int32 [B, L],
+        d_y complex [B, n]) of the blocks [first_block, first_block + n_blocks),
+        B = n_blocks * block."""
+        op, lib, off = self.op, _native.lib(), _native.offset
+        L, n, nbits = op.L, op.n, self.bits_per_codeword
+        B = n_blocks * block
+        plan = op.plan()
+        d_bits = _native.DeviceBuffer(B * nbits)
+        d_idx = _native.DeviceBuffer(B * L * 4)
+        d_sym = _native.DeviceBuffer(B * L * 4)
+        d_x = _native.DeviceBuffer(B * n * 16)
+        d_y = _native.DeviceBuffer(B * n * 16)
+        sids = [(int(point) << 32) | int(blk) for blk in range(first_block, first_block + n_blocks)]
+        for i, sid in enumerate(sids):
+            _native.check(lib.sg_rng_bits_device(self.seed, sid, block, nbits, off(d_bits.ptr, i * block * nbits), None))
+        _native.check(lib.sg_bits_to_psk_sections_device(d_bits.ptr, B, L, self.logM, self.logK, d_idx.ptr, d_sym.ptr,
+                                                         None))
+        _native.check(lib.sg_camp_encode_device(plan, self.K, _native.ptr(self.constel), d_idx.ptr, d_sym.ptr, B,
+                                                d_x.ptr, None))
+        sigma = float(np.sqrt(self.vars[point] / 2))  # per real dimension
+        for i, sid in enumerate(sids):
+            o = i * block * n * 16
+            _native.check(lib.sg_awgn_device(_native.SG_F64, self.seed, sid, off(d_x.ptr, o), block, 2 * n, sigma,
+                                             off(d_y.ptr, o), None))
+        return d_idx, d_sym, d_y
+
+    def __call__(self, point, first_block, n_blocks, block):
+        op, lib = self.op, _native.lib()
+        L, B = op.L, n_blocks * block
+        d_idx, d_sym, d_y = self.generate(point, first_block, n_blocks, block)
+        d_map = _native.DeviceBuffer(B * L * 4)
+        d_msym = _native.DeviceBuffer(B * L * 4)
+        d_tf = _native.DeviceBuffer(B * 4)
+        d_cnt = _native.DeviceBuffer(6 * 8)
+        d_cnt.zero()
+        d_rows = _native.DeviceBuffer(B * 4 * 4) if self.per_unit else None
+        _native.check(lib.sg_camp_decode_device(op.plan(), d_y.ptr, B, self.K, _native.ptr(self.constel), d_idx.ptr,
+                                                d_sym.ptr, float(self.vars[point]), self.t_max, self.rtol, self.phi,
+                                                d_map.ptr, d_msym.ptr, d_tf.ptr, None, None, None))
+        _native.check(lib.sg_camp_count_errors_device(d_map.ptr, d_msym.ptr, d_idx.ptr, d_sym.ptr, d_tf.ptr, B, L,
+                                                      self.logM, self.logK, d_cnt.ptr,
+                                                      d_rows.ptr if d_rows else None, None))
+        if self.per_unit:  # one row per codeword
+            r = d_rows.download(np.zeros((B, 4), np.int32)).astype(np.int64)
+            tf = d_tf.download(np.zeros(B, np.int32)).astype(np.int64)
+            return np.stack([np.ones(B, np.int64), r[:, 0], (r[:, 0] > 0).astype(np.int64), tf, r[:, 1], r[:, 2],
+                             r[:, 3]], 1)
+        cnt = d_cnt.download(np.zeros(6, np.int64))
+        return np.array([B, cnt[3], cnt[4], cnt[5], cnt[0], cnt[1], cnt[2]], dtype=np.int64)
+
+
+def csparc_ser_sweep(code_params, decode_params, awgn_vars, *, codewords, block=256, blocks_per_round=None, rank=0,
+                     world=1, agg=None, design_seed=0, seed=0, min_errors=None, checkpoint_dir=None, max_rounds=None):
+    """Error rates of a complex (K-PSK) SPARC against the noise variance:
+    `codewords` per point of `awgn_vars`, sharded over the ranks, every point
+    a run_point over CSparcTrial.  The design is built once, from
+    `design_seed` (check_code_params, create_base_matrix at awgn_vars[0] --
+    only a power allocation depends on the variance -- and
+    sparc_transforms(..., csparc=True)), and shared by every point.  Returns
+    one dict per point: awgn_var, codewords, ber (over L log2(K M) bits per
+    codeword), cer, ser / ler / ver (section, location and value error rates
+    over L sections per codeword; K = 1: ler = ser, ver = 0), t_final_mean and
+    the raw `counts` (CSparcTrial's seven)."""
+    from . import sparc
+    cp, dp = dict(code_params), dict(decode_params)
+    sparc.check_code_params(cp)
+    sparc.check_decode_params(dp)
+    if not cp['complex']:
+        raise ValueError("csparc_ser_sweep runs complex SPARCs: code_params['complex'] must be True")
+    if sparc._precision(dp) != _native.SG_F64:
+        raise NotImplementedError("complex SPARCs run in double precision only ('precision': 'f64')")
+    awgn_vars = [float(v) for v in awgn_vars]
+    R, L, M = cp['R'], cp['L'], cp['M']
+    K = cp['K'] if cp['modulated'] else 1
+    sparc._check_psk(K)
+    tmp = cp.copy()
+    tmp.update({'awgn_var': awgn_vars[0]})
+    W = sparc.create_base_matrix(**tmp)
+    bit_len = int(round(L * np.log2(K * M)))
+    n = int(round(bit_len / R))  # as sparc_encode (sparc.py:36-41)
+    if W.ndim == 2:
+        n = int(round(n / W.shape[0])) * W.shape[0]
+    Ab, Az = sparc.sparc_transforms(W, L, M, n, design_seed, True)
+    op = sparc.operator_of(Ab, Az)
+    trial = CSparcTrial(op, K, awgn_vars, dp['t_max'], dp['rtol'], dp['phi_est_method'], seed)
+    agg = agg or Aggregator()
+    bpr = blocks_per_round or max(1, world)
+    out = []
+    for point, var in enumerate(awgn_vars):
+        params = {"code_params": {k: cp[k] for k in sorted(cp)}, "awgn_var": var, "design_awgn_var": awgn_vars[0],
+                  "t_max": dp['t_max'], "rtol": dp['rtol'], "phi_est_method": dp['phi_est_method'], "seed": seed,
+                  "design_seed": design_seed, "codewords": codewords, "min_errors": min_errors}
+        if min_errors is not None:  # the counters stop at round granularity (concat_ber_sweep)
+            params["blocks_per_round"] = bpr
+        tot = run_point(trial, point, block=block, blocks_per_round=bpr, rank=rank, world=world, agg=agg,
+                        min_errors=min_errors, max_units=codewords, checkpoint_dir=checkpoint_dir,
+                        tag=f"csparc_L{L}_M{M}_K{K}_n{n}", params=params, max_rounds=max_rounds)
+        cw = int(tot[0])
+        rate = (lambda c, per: float(c) / (cw * per)) if cw else (lambda c, per: None)
+        out.append({"awgn_var": var, "codewords": cw, "ber": rate(tot[1], bit_len), "cer": rate(tot[2], 1),
+                    "ser": rate(tot[4], L), "ler": rate(tot[5], L), "ver": rate(tot[6], L),
+                    "t_final_mean": rate(tot[3], 1), "counts": [int(c) for c in tot]})
+    return out
 
 
 class ConcatTrial:

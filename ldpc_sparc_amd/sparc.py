@@ -15,9 +15,11 @@ path).
 Complex SPARCs (the sub-sampled FFT design, sub_fft sparc.py:593-646) and
 K-PSK modulated complex SPARCs (K up to 64) run on the complex engine
 (csrc/amp_cfft.hip) in double precision only: 'precision': 'f32' with a
-complex design raises NotImplementedError.  Two things remain out of scope and
-raise NotImplementedError: real K=2 modulated SPARCs on the DCT engines, and
-state evolution for complex PSK with K>2 (sparc_se.py).
+complex design raises NotImplementedError.  Also out of scope, raising
+NotImplementedError: real K=2 modulated SPARCs on the DCT engines, and K > 64.
+Monte-Carlo campaigns of complex SPARCs that stay on the GPU are
+montecarlo.CSparcTrial / csparc_ser_sweep; state evolution, K-PSK included, is
+sparc_se.py.
 """
 import ctypes as ct
 from copy import copy

@@ -4,11 +4,12 @@ sparc_se(awgn_var, code_params, t_max, mc_samples) keeps the reference's
 arguments, code_params rewrite (check_code_params) and return value
 (psi [t_max] or [t_max, Lc], final tau).  The Monte-Carlo samples are drawn
 exactly as the reference draws them -- np.random.randn(mc_samples, M) from
-numpy's global state -- then stay resident on the GPU, where every
+numpy's global state, and randn + 1j * randn in that order for complex K-PSK
+with K > 2 (:154-155) -- then stay resident on the GPU, where every
 expectation sparc_se_E (:82-115) of an iteration is evaluated for all column
-blocks in one launch (se.hip).  Real SPARCs (K = 1, and K = 2 modulated) and
-complex unmodulated ones are supported; complex PSK-modulated SPARCs (K > 2)
-are outside the engine.
+blocks in one launch (se.hip).  Real SPARCs (K = 1, and K = 2 modulated),
+complex unmodulated ones and complex K-PSK modulated ones up to K = 64 are
+supported; K > 64 raises NotImplementedError, as in the AMP engine.
 """
 import ctypes as ct
 from copy import copy
@@ -16,7 +17,14 @@ from copy import copy
 import numpy as np
 
 from . import _native
-from .sparc import create_base_matrix, is_power_of_2
+from .sparc import MAX_PSK, create_base_matrix, is_power_of_2
+
+
+def _check_psk_order(K):
+    if not (type(K) == int and K >= 1 and is_power_of_2(K)):
+        raise ValueError("K must be 1 or a power of two, not {!r}".format(K))
+    if K > MAX_PSK:
+        raise NotImplementedError("K-PSK with K > {} is not part of the GPU engine".format(MAX_PSK))
 
 
 def check_code_params(code_params):
@@ -60,14 +68,17 @@ def check_code_params(code_params):
 
 
 class SeSamples:
-    """Monte-Carlo samples u [mc, M] resident on the GPU."""
+    """Monte-Carlo samples u [mc, M] resident on the GPU: real for K = 1, 2,
+    complex (interleaved on the device) for complex K-PSK with K >= 4."""
 
     def __init__(self, u):
         _native.require_gpu()
-        self.u = np.ascontiguousarray(u, dtype=np.float64)
+        self.complex = np.iscomplexobj(u)
+        self.u = np.ascontiguousarray(u, dtype=np.complex128 if self.complex else np.float64)
         self.h = ct.c_void_p()
-        _native.check(_native.lib().sg_se_samples_create(_native.ptr(self.u), self.u.shape[0], self.u.shape[1],
-                                                         ct.byref(self.h)))
+        lib = _native.lib()
+        create = lib.sg_se_samples_create_complex if self.complex else lib.sg_se_samples_create
+        _native.check(create(_native.ptr(self.u), self.u.shape[0], self.u.shape[1], ct.byref(self.h)))
 
     def expectation(self, taus, K):
         taus = np.ascontiguousarray(np.atleast_1d(taus), dtype=np.float64)
@@ -86,9 +97,9 @@ class SeSamples:
 
 def sparc_se_E(tau, K, u):
     """Mean over the samples of the posterior weight of the true entry
-    (sparc_se.py:82-115), on the GPU; tau may be a vector."""
-    if K not in (1, 2):
-        raise NotImplementedError("complex PSK-modulated SPARCs (K > 2) are not part of the GPU engine")
+    (sparc_se.py:82-115), on the GPU; tau may be a vector.  u is real for
+    K = 1, 2 and complex for K >= 4."""
+    _check_psk_order(K)
     E = SeSamples(u).expectation(tau, K)
     return E if np.ndim(tau) else float(E[0])
 
@@ -109,9 +120,12 @@ def sparc_se(awgn_var, code_params, t_max, mc_samples):
     else:
         Lr, Lc = (1, W.size) if W.ndim == 1 else W.shape
         psi = np.ones((t_max, Lc))
+    _check_psk_order(K)
+    # the reference's draw from numpy's global state (sparc_se.py:154-157)
     if K > 2:
-        raise NotImplementedError("complex PSK-modulated SPARCs (K > 2) are not part of the GPU engine")
-    u = np.random.randn(mc_samples, M)  # the reference's draw from numpy's global state
+        u = np.random.randn(mc_samples, M) + 1j * np.random.randn(mc_samples, M)
+    else:
+        u = np.random.randn(mc_samples, M)
     samples = SeSamples(u)
     for t in range(t_max - 1):
         if t > 0:
