@@ -8,13 +8,6 @@ namespace sg {
 
 constexpr int AMP_MAX_EPT = 32;
 
-// Stage twiddles of the block engines' 2^14-point transforms: bit 0 forward,
-// bit 1 inverse from the hardware sine / cosine, otherwise from the plan's
-// table (tb.stw)
-#ifndef SG_BLK_SINCOS
-#define SG_BLK_SINCOS 2
-#endif
-
 // Design operator tables of one design (all transforms), device pointers.
 // A "transform" is one nonzero block (r, c) of the base matrix W
 // (sparc.py:777-875): a sub-sampled DCT of size w with its own orders.
@@ -46,8 +39,7 @@ struct BlkTables {
     const uint32_t *pos2;     // [nT][8][1024] real LDS index (2 fsw(m) + component) of column entry
                               // j = tid + 1024 i, pairs (i = 2 i2, 2 i2 + 1) at [t][i2][tid]; the two-class
                               // engine: [nT][2][16][1024], 2 ppos(m1) + component per class (amp_block2.hip)
-    const uint32_t *pos1;     // two-class engine, one-table form (A/B, -DB2_ONETABLE=1): [nT][16][1024] per column
-                              // entry m1 << 2 | component << 1 | class (16 bits, pairs), both classes' passes
+    const uint32_t *pos1 = nullptr;  // unused (kept: without it the block kernels' register allocation moves)
     const uint32_t *oab;      // [nT][Mr] (a mod 4096) | (b mod 4096) << 16 of output i
     const cx<float> *oc;      // [nT][Mr][8] X_i = Re(sum_r al_r Y[a mod 4096 + 4096 r] + be_r conj Y[b mod ...]),
                               // al_r = c1 w_N2^(r a), be_r = c2 conj w_N2^(r b) (the last FFT stage folded in)
@@ -203,9 +195,7 @@ size_t cw_lds_bytes(int img, int nslots);
 constexpr int CW2_THREADS = 512;
 // f32 split engine: workgroups per codeword at most (Cw2Tables.np: 2, or 4 once codewords have stopped), each
 // taking Q / np of the classes; the partial buffers are sized for CW2_NP
-#ifndef CW2_NP
-#define CW2_NP 4
-#endif
+constexpr int CW2_NP = 4;
 constexpr int CW2_SLICE = 9216;     // class entries per workgroup pass (18 per thread)
 // P-point image layout of the split engine: complex element i at c2pos(i) =
 // i + i / 32 (one pad value per 32), so every LDS access of the transform's
@@ -231,9 +221,9 @@ struct Cw2Tables {
     const uint32_t *kat;      // [512][OTP] the same, thread-major (a thread's slots in 16-byte loads)
     const int32_t *oi;        // [OT][512] output index (invalid slots: 0)
     const float4 *cf;         // [OT][512] (c1, c2): output = Re(c1 H[a] + c2 conj H[N2 - a])
-    const float4 *gf;         // [OT][512] (al, be): G[a] += al z/phi, G[N2 - a] += be z/phi
+    const float4 *gf = nullptr;  // unused (kept with rab, wab: without them cw2_ctrl's instruction count moves)
     const float2 *gm;         // [OT][512] (|al|, |be|) of the polar form (CW_OFFSHIFT; cw2_ctrl scales z/phi)
-    const float4 *gmt;        // [512][OTP / 2] the same thread-major, two slots per 16 bytes (C2_VZ_HALF rows)
+    const float4 *gmt;        // [512][OTP / 2] the same thread-major, two slots per 16 bytes (cw2_az rows)
     int sh_off;               // log2(N / 2): the slot's phase offset o N/2 = o << sh_off
     uint32_t m4n;             // 4N - 1 (phases in units of 1 / 4N revolutions, N = 2 N2 a power of two)
     float inv_4n;             // 1 / 4N
@@ -244,11 +234,9 @@ struct Cw2Tables {
     const int32_t *qpos;      // [Mc]
     const uint16_t *seg;      // [Q][Lblk+1]
     float *xr;                // [B][2][OT][512] each half's part of Re(c1 H[a] + c2 conj H[b]) per output
-    const uint2 *rab;         // [OT][512] LDS byte addresses of rows r, P - r of the slot's output (cw2_ab reads)
-    const uint2 *wab;         // [OT][512] LDS byte addresses of the slot's row writes (rows r, P - r on the
-                              // pair's last slot, else the trash slot; r = 0, P / 2: row r and trash)
-    float *vz;                // z / phi in slot order, times (|al|, |be|) (two floats per slot): [B][512][OTP][2]
-                              // thread-major (OTP = OT rounded up to 4) if cw2_vz_tm(OT), else [B][OT][512][2]
+    const uint2 *rab = nullptr, *wab = nullptr;  // unused
+    float *vz;                // z / phi in slot order: [B][512][OTP] thread-major (OTP = OT rounded up to 4) if
+                              // cw2_vz_tm(OT), else times (|al|, |be|), two floats per slot, [B][OT][512][2]
     float *ys, *zs;           // [B][OT][512] y (copied at t = 0) and z in slot order (cw2_ctrl reads them
                               // coalesced; z in natural order is still written for a hand-over)
     float4 *part;             // [B][2][Lblk] partial section statistics (max, R1, R2, s of the true entry or NaN)

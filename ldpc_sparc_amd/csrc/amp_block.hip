@@ -94,22 +94,19 @@ __device__ __forceinline__ uint32_t bk_pos(const uint32_t *pv, int i) { return (
 // then 4): the forward transform stops before the radix-4 stage, which Ab
 // folds into the needed outputs.  Stages 0-1 and stage 2 separately, so that
 // the outputs' table entries can be requested in between (in flight during
-// the last stage; across all three stages they would spill).
+// the last stage; across all three stages they would spill).  The forward
+// stage twiddles come from the plan's table (tb.stw), the inverse transform's
+// from the hardware sine / cosine.
 __device__ __forceinline__ void bk_fwd_stages01(cx<float> *d, const cx<float> *__restrict__ stw, int tid,
                                                 cx<float> *w2) {
-    if constexpr (SG_BLK_SINCOS & 1) {
-        lds_fft1_sincos<false, 16, BK_LOG2N, 0, 2, true>(d, tid);
-    } else {
-        cx<float> w0[1], w1[6];
-        fft1_tw_load_ct<float, 16, BK_LOG2N, 1>(stw, tid, w1);
-        stockham1_stage_ct<float, false, 16, 16, BK_LOG2N, 0, true>(d, w0, tid);
-        fft1_tw_load_ct<float, 16, BK_LOG2N, 2>(stw, tid, w2);
-        stockham1_stage_ct<float, false, 16, 16, BK_LOG2N, 4, true>(d, w1, tid);
-    }
+    cx<float> w0[1], w1[6];
+    fft1_tw_load_ct<float, 16, BK_LOG2N, 1>(stw, tid, w1);
+    stockham1_stage_ct<float, false, 16, 16, BK_LOG2N, 0, true>(d, w0, tid);
+    fft1_tw_load_ct<float, 16, BK_LOG2N, 2>(stw, tid, w2);
+    stockham1_stage_ct<float, false, 16, 16, BK_LOG2N, 4, true>(d, w1, tid);
 }
 __device__ __forceinline__ void bk_fwd_stage2(cx<float> *d, int tid, const cx<float> *w2) {
-    if constexpr (SG_BLK_SINCOS & 1) lds_fft1_sincos<false, 16, BK_LOG2N, 2, 3, true>(d, tid);
-    else stockham1_stage_ct<float, false, 16, 16, BK_LOG2N, 8, true>(d, w2, tid);
+    stockham1_stage_ct<float, false, 16, 16, BK_LOG2N, 8, true>(d, w2, tid);
 }
 
 // ------------------------------------------------------------------ Ab

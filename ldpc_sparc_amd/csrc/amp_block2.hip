@@ -104,35 +104,8 @@ __device__ __forceinline__ void b2_pos_load(const BlkTables &tb, int t, int m2, 
     for (int i = 0; i < B2_J / 2; ++i) pv[i] = p2[i * T + tid];
 }
 __device__ __forceinline__ uint32_t b2_pos(const uint32_t *pv, int i) { return (pv[i >> 1] >> (16 * (i & 1))) & 0xffffu; }
-// One-table form (A/B: -DB2_ONETABLE=1): one 16-bit entry per column entry and
-// transform for both classes, m1 << 2 | component << 1 | class, the padded index rebuilt per class pass --
-// half the position-table bytes, four vector instructions more per entry and pass
-// Wave issue priority of the transforms and of the rest (A/B; flat by default: the split C2 engine's
-// scheme -- transforms 0, the rest 1 -- measured 1000 -> 945 codewords/s here, profiles/r05_prio_ab.txt)
-#ifndef B2_PRIO_FFT
-#define B2_PRIO_FFT 0
-#endif
-#ifndef B2_PRIO_REST
-#define B2_PRIO_REST 0
-#endif
-#define B2_SETPRIO(p)                                                       \
-    do {                                                                    \
-        if (B2_PRIO_FFT != B2_PRIO_REST) __builtin_amdgcn_s_setprio(p);     \
-    } while (0)
-#ifndef B2_ONETABLE
-#define B2_ONETABLE 0
-#endif
-template <int LP>
-__device__ __forceinline__ void b2_pos_load1(const BlkTables &tb, int t, int tid, uint32_t *pv) {
-    constexpr int T = B2G<LP>::THREADS;
-    const uint32_t *p1 = tb.pos1 + (size_t)t * (B2_J / 2) * T;
-#pragma unroll
-    for (int i = 0; i < B2_J / 2; ++i) pv[i] = p1[i * T + tid];
-}
-__device__ __forceinline__ uint32_t b2_pos1(const uint32_t *pv, int i, int m2) {
-    const uint32_t e = (pv[i >> 1] >> (16 * (i & 1))) & 0xffffu;
-    return (e & 1u) == (uint32_t)m2 ? 2u * (uint32_t)ppos((int)(e >> 2)) + ((e >> 1) & 1u) : (uint32_t)B2_TRASH;
-}
+// (Wave issue priority stays flat here: the split C2 engine's scheme -- transforms 0, the rest 1 -- measured
+// 1000 -> 945 codewords/s, profiles/r05_prio_ab.txt)
 
 // the first three stages (radix 16) of the P-point FFT over the padded image,
 // twiddles from the hardware sine / cosine (no table entries in flight: blk2_ab
@@ -165,13 +138,12 @@ __device__ __forceinline__ void b2_ab_column(const BlkTables &tb, const AmpBufs<
             const int tl = b2_opaque(tid);
             // the positions, in flight while the image clears
             uint32_t pv[B2_J / 2];
-            if (B2_ONETABLE) b2_pos_load1<LP>(tb, t, tl, pv);
-            else b2_pos_load<LP>(tb, t, m2, tl, pv);
+            b2_pos_load<LP>(tb, t, m2, tl, pv);
             b2_clear<LP>(smem, tl);
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < B2_J; ++i)  // (the other class's entries: trash slot)
-                dr[B2_ONETABLE ? b2_pos1(pv, i, m2) : b2_pos(pv, i)] = bv[i];
+                dr[b2_pos(pv, i)] = bv[i];
             // the output's bins and coefficients, requested before the transform (their L2 round trip
             // hides behind it; requested after it, one workgroup per CU waited for it every class)
             constexpr int RF = B2G<LP>::RF;
@@ -186,9 +158,7 @@ __device__ __forceinline__ void b2_ab_column(const BlkTables &tb, const AmpBufs<
                 be[r] = oc[4 + r];
             }
             __syncthreads();
-            B2_SETPRIO(B2_PRIO_FFT);
             b2_fwd_stages<LP>(d, tl);
-            B2_SETPRIO(B2_PRIO_REST);
             // X_i += Re(sum_r al_r Y[a mod 4096 + 4096 r] + be_r conj Y[b mod ...]), r < RF:
             // the last stage and w_N2^(m2 k) are in the coefficients
             if (own) {
@@ -212,7 +182,6 @@ __global__ __launch_bounds__(B2G<LP>::THREADS, 4) void blk2_ab(BlkTables tb, Amp
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int c = blockIdx.x, cw = blockIdx.y, tid = threadIdx.x;
     if (!bf.active[cw]) return;
-    B2_SETPRIO(B2_PRIO_REST);
     const float *beta = bf.beta + (size_t)cw * tb.LM + (size_t)c * tb.Mc;
     float bv[B2_J];
 #pragma unroll
@@ -231,7 +200,6 @@ __global__ __launch_bounds__(B2G<LP>::THREADS, 4) void blk2_az(BlkTables tb, Amp
     float *dr = reinterpret_cast<float *>(smem);
     const int c = blockIdx.x, cw = blockIdx.y, tid = threadIdx.x;
     if (!bf.active[cw]) return;
-    B2_SETPRIO(B2_PRIO_REST);
     float u[B2_J];
 #pragma unroll
     for (int i = 0; i < B2_J; ++i) u[i] = 0.f;
@@ -273,15 +241,12 @@ __global__ __launch_bounds__(B2G<LP>::THREADS, 4) void blk2_az(BlkTables tb, Amp
             for (int g = tl + 2 * T; g < ng; g += T) row(tb.gk[g0 + g], gcw[g0 + g]);
             __syncthreads();
             // (stage twiddles from the hardware sine / cosine: no table entries in flight, u[] stays in registers)
-            B2_SETPRIO(B2_PRIO_FFT);
             lds_fft1_sincos<true, 16, LP, 0, 4, true>(d, tl);
-            B2_SETPRIO(B2_PRIO_REST);
             uint32_t pv[B2_J / 2];
-            if (B2_ONETABLE) b2_pos_load1<LP>(tb, t, tl, pv);
-            else b2_pos_load<LP>(tb, t, m2, tl, pv);
+            b2_pos_load<LP>(tb, t, m2, tl, pv);
 #pragma unroll
             for (int i = 0; i < B2_J; ++i)  // (the other class's entries read the zero trash slot)
-                u[i] += dr[B2_ONETABLE ? b2_pos1(pv, i, m2) : b2_pos(pv, i)];
+                u[i] += dr[b2_pos(pv, i)];
             __syncthreads();
         }
     }

@@ -61,24 +61,11 @@ __device__ __forceinline__ cx<float> cw_w(const CwTables &tb, uint32_t j) {
     return {__builtin_amdgcn_cosf(x), -__builtin_amdgcn_sinf(x)};
 }
 
-// Radix plan of the P-point FFT at 8 values per thread (CW_RADIX_PLAN 0:
-// fft.hpp's 4, 4, 8, 8, 8; 1: 8, 8, 8, 8, 2; 2: 2, 8, 8, 8, 8; 3: 16, 8, 8, 8
-// with the radix-16 first stage split over lanes l and l ^ 32, cw_stage0_r16)
-#ifndef CW_RADIX_PLAN
-#define CW_RADIX_PLAN 3
-#endif
-constexpr int cw_nstages() { return CW_RADIX_PLAN == 3 ? 4 : 5; }
-constexpr int cw_radix(int st) {
-    return CW_RADIX_PLAN == 0   ? fft1_radix_ct(CW_LOG2P, CW_EPT, st)
-           : CW_RADIX_PLAN == 1 ? (st < 4 ? 8 : 2)
-           : CW_RADIX_PLAN == 2 ? (st == 0 ? 2 : 8)
-                                : (st == 0 ? 16 : 8);
-}
-constexpr int cw_log2ns(int st) {
-    int l = 0;
-    for (int i = 0; i < st; ++i) l += cw_radix(i) == 2 ? 1 : cw_radix(i) == 4 ? 2 : cw_radix(i) == 8 ? 3 : 4;
-    return l;
-}
+// Radix plan of the P-point FFT at 8 values per thread: 16, 8, 8, 8 with the
+// radix-16 first stage split over lanes l and l ^ 32 (cw_stage0_r16)
+constexpr int cw_nstages() { return 4; }
+constexpr int cw_radix(int st) { return st == 0 ? 16 : 8; }
+constexpr int cw_log2ns(int st) { return st == 0 ? 0 : 4 + 3 * (st - 1); }
 
 // lanes 32..63 of a <-> lanes 0..31 of b (v_permlane32_swap, no LDS)
 __device__ __forceinline__ void cw_swap32(cx<float> &a, cx<float> &b) {
@@ -93,13 +80,10 @@ __device__ __forceinline__ void cw_swap32(cx<float> &a, cx<float> &b) {
 // and l ^ 32, lane half H holding inputs m = 8 H + jj (x[j + 512 m]).  A
 // radix-2 step across the halves (two rounds of permlane32 swaps) and a
 // radix-8 DFT in registers give lane half H the outputs 2 q + H, stored at
-// j 16 + 2 q + H like stockham1_stage_ct's.  With CW_MASKIN the image is not
+// j 16 + 2 q + H like stockham1_stage_ct's.  The image is not
 // zeroed before the class scatter / row writes: bit 2 jj + c of msk says
 // whether component c of value jj was written for this transform (host
 // table, capi_amp.cpp build_cw), and the stale ones read as zero.
-#ifndef CW_MASKIN
-#define CW_MASKIN 1
-#endif
 template <bool INV>
 __device__ __forceinline__ void cw_stage0_r16(cx<float> *d, int tid, uint32_t msk) {
     const int l = tid & 63, H = l >> 5, j = ((tid >> 6) << 5) | (l & 31);
@@ -107,13 +91,11 @@ __device__ __forceinline__ void cw_stage0_r16(cx<float> *d, int tid, uint32_t ms
     const int jp = fsw(j);  // adding multiples of 256 commutes with the swizzle
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) v[jj] = d[jp + ((8 * H + jj) << 9)];
-    if constexpr (CW_MASKIN) {
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {  // all-ones / zero from the sign-extended bit
-            const uint32_t mx = (uint32_t)((int)(msk << (31 - 2 * jj)) >> 31);
-            const uint32_t my = (uint32_t)((int)(msk << (30 - 2 * jj)) >> 31);
-            v[jj] = {__uint_as_float(__float_as_uint(v[jj].x) & mx), __uint_as_float(__float_as_uint(v[jj].y) & my)};
-        }
+    for (int jj = 0; jj < 8; ++jj) {  // all-ones / zero from the sign-extended bit
+        const uint32_t mx = (uint32_t)((int)(msk << (31 - 2 * jj)) >> 31);
+        const uint32_t my = (uint32_t)((int)(msk << (30 - 2 * jj)) >> 31);
+        v[jj] = {__uint_as_float(__float_as_uint(v[jj].x) & mx), __uint_as_float(__float_as_uint(v[jj].y) & my)};
     }
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) cw_swap32(v[jj], v[jj + 4]);  // lane half H: x[J], x[8 + J], J = jj + 4 H
@@ -142,8 +124,7 @@ __device__ __forceinline__ void cw_stage0_r16(cx<float> *d, int tid, uint32_t ms
 // global loads between its barriers.
 template <bool INV, int ST>
 __device__ __forceinline__ void cw_fft_from(cx<float> *d, int tid, uint32_t msk = 0xffffu) {
-    static_assert(!CW_MASKIN || cw_radix(0) == 16, "the masked first stage is the radix-16 one");
-    if constexpr (ST == 0 && cw_radix(0) == 16) {
+    if constexpr (ST == 0) {  // the masked radix-16 stage
         cw_stage0_r16<INV>(d, tid, msk);
         cw_fft_from<INV, 1>(d, tid);
     } else if constexpr (ST < cw_nstages()) {
@@ -151,7 +132,8 @@ __device__ __forceinline__ void cw_fft_from(cx<float> *d, int tid, uint32_t msk 
         constexpr int NB = CW_EPT / R, TWN = tw_per_k(R);
         cx<float> wl[LNS > 0 ? NB * TWN : 1];
         if constexpr (LNS > 0) {
-            constexpr int LR = R == 2 ? 1 : R == 4 ? 2 : R == 8 ? 3 : 4;
+            constexpr int LR = 3;
+            static_assert(R == 8, "stages after the first are radix 8");
             constexpr float inv = 1.0f / (float)(1 << (LNS + LR));
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
@@ -258,10 +240,10 @@ __global__ __launch_bounds__(CW_THREADS) void cw_iter(CwTables tb, RegBufs<float
             v[i] = s[q];
             e[i] = tb.cls_ls[q];
         }
-        // section max and 1/sum of the class's entries; with CW_MASKIN those of
+        // section max and 1/sum of the class's entries; those of
         // class m2 + 1 are gathered before class m2's closing barrier (not with
         // register-held slots: <14> then spills 12 VGPRs)
-        constexpr bool early = CW_MASKIN && KT <= CW_KL;
+        constexpr bool early = KT <= CW_KL;
         float bm[CW_SN], bi[CW_SN];
         auto gather_stats = [&]() {
 #pragma unroll
@@ -275,16 +257,13 @@ __global__ __launch_bounds__(CW_THREADS) void cw_iter(CwTables tb, RegBufs<float
         for (int m2 = 0; m2 < tb.Q; ++m2) {
             const int tl = cw_opaque(tid);
             if (m2 == 2) CW_TP(8);
-            if constexpr (!CW_MASKIN)
-                for (int i = tl; i < CW_P * 8 / 16; i += CW_THREADS) reinterpret_cast<uint4 *>(smem)[i] = uint4{0, 0, 0, 0};
-            if constexpr (!early) gather_stats();
-            if constexpr (!CW_MASKIN) __syncthreads();  // (masked: the previous class's closing barrier)
+            if constexpr (!early) gather_stats();  // (after the previous class's closing barrier)
             if (m2 == 2) CW_TP(9);
 #pragma unroll
             for (int i = 0; i < CW_SN; ++i)
                 if (q0 + tl + i * CW_THREADS < q1)  // beta = eta(s), sparc.py:429-432
                     dr[e[i] & 0xffffu] = __expf((v[i] - bm[i]) * inv_tp) * bi[i];
-            const uint32_t cmk = CW_MASKIN ? tb.cmask[m2 * CW_THREADS + tl] : 0xffffu;  // under the barrier
+            const uint32_t cmk = tb.cmask[m2 * CW_THREADS + tl];  // under the barrier
             __syncthreads();
             if (m2 == 2) CW_TP(10);
             cw_fft_from<false, 0>(d, tl, cmk);
@@ -474,13 +453,10 @@ __global__ __launch_bounds__(CW_THREADS) void cw_iter(CwTables tb, RegBufs<float
         const int tl = cw_opaque(tid);
         if (m2 == 2) CW_TP(16);
         // the rows' image values (the same every class; reloaded, not held across the loop)
-        const uint32_t rmk = CW_MASKIN ? tb.cmask[tb.Q * CW_THREADS + tl] : 0xffffu;
-        if constexpr (!CW_MASKIN)
-            for (int i = tl; i < CW_P * 8 / 16; i += CW_THREADS) reinterpret_cast<uint4 *>(smem)[i] = uint4{0, 0, 0, 0};
+        const uint32_t rmk = tb.cmask[tb.Q * CW_THREADS + tl];
         cx<float> w[KT];
 #pragma unroll
         for (int j = 0; j < KT; ++j) w[j] = cw_w(tb, (uint32_t)m2 * (kt[j] & CW_KMASK));
-        if constexpr (!CW_MASKIN) __syncthreads();  // (masked: the previous class's closing barrier)
         if (m2 == 2) CW_TP(17);
         cw_rows<KT>(Xl, d, Xr, kt, w, tl);
         __syncthreads();

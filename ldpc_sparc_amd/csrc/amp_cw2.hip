@@ -45,29 +45,6 @@ constexpr int C2_SC = 9;   // class entries per thread and chunk
 constexpr int C2_NC = 2;   // chunks: a class holds at most C2_SC * C2_NC * 512 = 9216 entries
 static_assert(C2_EPT == 16, "the transform is written for 16 values per thread");
 
-// Phase ablation for timing studies only (tools/c2_ablate.py on variants built by
-// tools/mk_variant.sh with -DC2_ABL=<mask>; results are garbage, the shipped build has 0):
-// 1 Ab FFT, 2 Ab accumulation, 4 Ab slice loads, 8 Az FFT, 16 Az rows, 32 Az rows' table
-// loads (values from the thread index), 64 Az statistics + class copy, 128 Az slice loads, 256 Ab scatter,
-// 512 Ab beta stores, 1024 Az gathers from the image
-#ifndef C2_ABL
-#define C2_ABL 0
-#endif
-#define C2_SKIP(bit) ((C2_ABL & (bit)) != 0)
-
-// Az rows: the row addresses from the slot's flags instead of the host table wab (A/B)
-#ifndef C2_ROWS_DERIVE
-#define C2_ROWS_DERIVE 1
-#endif
-// Az rows in the polar form (build_cw2): one phase per slot and class from the slot word, z/phi scaled by
-// (|al|, |be|) -- no per-slot complex coefficient table (gf) re-read every class (1), or that table (0) (A/B)
-#ifndef C2_POLAR
-#define C2_POLAR 1
-#endif
-// Az: the gathers' image positions from the packed 16-bit table clsp (1) or the full class words cls2 (0) (A/B)
-#ifndef C2_AZPOS
-#define C2_AZPOS 1
-#endif
 // Wave issue priority during the transforms and outside them.  Two workgroups share a CU and alternate
 // between the transform (VALU and LDS throughput) and phases that are chains of memory round trips and
 // barriers (class loads, rows, gathers, statistics).  At equal priority the older wave wins each issue
@@ -76,70 +53,17 @@ static_assert(C2_EPT == 16, "the transform is written for 16 values per thread")
 // 0.378 ms per launch, C2 probe 11.77 k -> 12.29 k codewords/s same box, identical results (priority 2 or
 // 3 for the chains, 2 for the statistics alone, or Az alone measured the same or less, and the gain is the
 // class-start phase's: with it at 0 and the rest at 1 the iteration is slower than flat;
-// profiles/r05_prio_ab.txt).  Both 0: flat, for the A/B.
-#ifndef C2_PRIO_FFT
-#define C2_PRIO_FFT 0
-#endif
-#ifndef C2_PRIO_REST
-#define C2_PRIO_REST 1
-#endif
-#define C2_SETPRIO(p)                                                       \
-    do {                                                                    \
-        if (C2_PRIO_FFT != 0 || C2_PRIO_REST != 0) __builtin_amdgcn_s_setprio(p); \
-    } while (0)
-// Ab: the accumulation's slot words requested after each transform (1) or at the class start (0) (A/B)
-#ifndef C2_AB_PF
-#define C2_AB_PF 1
-#endif
+// profiles/r05_prio_ab.txt).
+constexpr int C2_PRIO_FFT = 0, C2_PRIO_REST = 1;
+#define C2_SETPRIO(p) __builtin_amdgcn_s_setprio(p)
 
-// Section statistics: in cw2_az (class copy and two-pass scan per class, merged over the classes, then
-// cw2_merge: 0), or in their own full-occupancy launch after cw2_az (cw2_stats: one wavefront per section
-// reading its class segments of s from HBM, then cw2_final: 1), the f64 engine's form (amp_cw2d.hip) (A/B)
-#ifndef C2_STATS_LAUNCH
-#define C2_STATS_LAUNCH 0
-#endif
-// Az rows: every slot writes its pair's running sums at the pair's rows, addresses and factors from the slot
-// word without compares (1), or the last slot of a pair writes them, other slots write the trash slot (0) (A/B)
-#ifndef C2_ROWS_ALWAYS
-#define C2_ROWS_ALWAYS 1
-#endif
-// Polar rows' per-codeword input: z / phi alone, 4 bytes per slot, scaled in cw2_az by (|al|, |be|) from the
-// plan's thread-major table (shared by every codeword: L2-resident) (1), or the scaled pair stored by cw2_ctrl,
-// 8 bytes per slot re-read from the MALL in every class (0) (A/B; at most 12 slots per thread).  With the two
-// switches below, same box: fabric bytes 11.35 -> 9.69 MB per codeword-iteration (cw2_az 6.97 -> 5.34), C2
-// +0.4 % (profiles/r06_c2_vz_half_ab.txt)
-#ifndef C2_VZ_HALF
-#define C2_VZ_HALF 1
-#endif
-// Az statistics: the segment mask from a per-section bit mask, v_bfe + v_bfi per entry (1), or the sign-mask form
-// (0), which the compiler turns into v_cmp + v_cndmask through an SGPR pair with a hazard s_nop per entry (A/B);
-// bit-identical results.  (Pairing (x - max) / tau into v_pk_add / v_pk_mul halves their count but not their
-// issue cycles: a packed f32 instruction issues in 4 cycles, a plain one in 2 -- MI355X_MICROARCH.md.)
-#ifndef C2_ST_BITS
-#define C2_ST_BITS 1
-#endif
-// Az statistics: segment entries read per lane in the first round, the rest in rounds of as many until the
-// wavefront's longest segment is done (segments average LM / (Q L) = 8 entries).  The entries are summed in
-// segment order whatever the round size, so every choice gives bit-identical statistics.  Three calls of three
-// interleaved rounds (profiles/r06_c2_stats_rounds_ab.txt): 12 is 2 % slower than 16 (the round-5 form, one
-// round covering nearly every segment), 2 to 8 are faster; 4: 0.840 -> 0.830 ms per iteration, C2 +1.2 % (default)
-#ifndef C2_RC
-#define C2_RC 4
-#endif
-// Az statistics: every round of reads in the two loops, none held in registers across the maximum (1), or a
-// first round read once for both passes (0) (A/B; bit-identical).  Two same-box calls of three rounds: +0.4 %,
-// +0.2 % (profiles/r06_c2_stats_rounds_ab.txt); the two sections' rounds interleaved in one pair of loops
-// measured 2 % slower
-#ifndef C2_NOFIRST
-#define C2_NOFIRST 1
-#endif
-// workgroups per codeword: tb.np (amp.hpp CW2_NP: at most 8, the largest of 8, 4, 2 dividing Q)
-// Az rows' per-codeword class-invariant input (a thread's scaled z / phi, 24 VGPRs at 12 slots) loaded once per
-// launch and held in registers across the class loop (1; with the statistics launch cw2_az has the registers),
-// or re-read from L2 / MALL every class (0) (A/B); the slot words are the plan's, shared by every codeword
-#ifndef C2_AZ_HOLD
-#define C2_AZ_HOLD 0
-#endif
+// Az statistics: segment entries read per lane and round, in rounds of as many until the wavefront's longest
+// segment is done (segments average LM / (Q L) = 8 entries).  The entries are summed in segment order whatever
+// the round size, so every choice gives bit-identical statistics.  Three calls of three interleaved rounds
+// (profiles/r06_c2_stats_rounds_ab.txt): 12 is 2 % slower than 16 (the round-5 form, one round covering nearly
+// every segment), 2 to 8 are faster; 4: 0.840 -> 0.830 ms per iteration, C2 +1.2 %
+constexpr int C2_RC = 4;
+// workgroups per codeword: tb.np (amp.hpp CW2_NP: at most 4, the largest of 4, 2 dividing Q)
 
 // exp(x / tau) as exp2(x * (log2 e / tau)): __expf lowers to a multiply by log2 e and v_exp_f32, so
 // with log2 e folded into the per-codeword scale every exponential is one instruction
@@ -150,12 +74,6 @@ __device__ __forceinline__ int c2_opaque(int v) {
     asm volatile("" : "+v"(v));
     return v;
 }
-
-// the first transform stage's stale-value masks as v_bfe_i32 + v_and (1), or as the compiler's own
-// compare + select (0) (A/B)
-#ifndef C2_MASK_BFE
-#define C2_MASK_BFE 1
-#endif
 
 // w_N2^j = exp(-2 pi i j / N2) from the hardware sine / cosine (revolutions;
 // (j mod N2) / N2 is exact in f32 for N2 <= 2^19)
@@ -288,11 +206,9 @@ __device__ __forceinline__ void c2_stage0_r32(int tid, uint32_t msk) {
 #pragma unroll
     for (int jj = 0; jj < 16; ++jj) {  // all-ones / zero from the sign-extended bit (v_bfe_i32)
         int mx = __builtin_amdgcn_sbfe((int)msk, 2 * jj, 1), my = __builtin_amdgcn_sbfe((int)msk, 2 * jj + 1, 1);
-#if C2_MASK_BFE
         // (opaque: otherwise the compiler turns bit-extract-and-AND back into a compare and a select per
         // component, serialised on VCC with hazard nops -- 3 VALU and a nop instead of 2 VALU)
         asm volatile("" : "+v"(mx), "+v"(my));
-#endif
         v[jj] = c2f{__uint_as_float(__float_as_uint(v[jj].x) & (uint32_t)mx),
                     __uint_as_float(__float_as_uint(v[jj].y) & (uint32_t)my)};
     }
@@ -478,7 +394,6 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
         c2_ld_slots<OT>(rk, tl, ka);
     };
     auto accumulate = [&](int m, const uint32_t *ka) {
-        if (C2_SKIP(2)) return;
 #pragma unroll
         for (int j = 0; j < OT; ++j) {
             const uint32_t a = ka[j] & CW_KMASK;
@@ -496,26 +411,20 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
     // (at most 12 outputs per thread: the accumulation's slot words are class-invariant, so they are
     // requested after each transform and arrive across the loop edge -- cw2_ab 0.397 -> 0.391 ms per launch,
     // profiles/r05_c2_r13_fix.txt)
-    constexpr bool PF = C2_AB_PF && OT <= 12;
-    uint32_t kapf[PF ? OT : 1];
+    constexpr bool PL = OT <= 12;
+    uint32_t kapf[PL ? OT : 1];
     for (int m2 = h * Qh; m2 < (h + 1) * Qh; ++m2) {
         const int tl = c2_opaque(tid);
         C2_TPC(0);
         const int q0 = c2_uni(cpl[m2]), q1 = c2_uni(cpl[m2 + 1]);
         // (at more than 12 outputs per thread the slice is requested after the accumulation: in flight
         // during it, it spills)
-        constexpr bool PL = OT <= 12;
         if (!PL && m2 > h * Qh) {
             uint32_t ka[OT];
             acc_tables(tl, ka);
             accumulate(m2 - 1, ka);
             __syncthreads();
         }
-        // (the accumulation's table loads first: vector-memory loads complete in order)
-        uint32_t kl[PL && !PF ? OT : 1];
-        if constexpr (PL && !PF)
-            if (m2 > h * Qh) acc_tables(tl, kl);
-        const uint32_t *ka = PF ? kapf : kl;
         float v[C2_SN];
         uint32_t e[C2_SN];
         {  // every load of the class slice in one round trip; past the class's end s reads 0 and the
@@ -524,11 +433,6 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
             const __amdgpu_buffer_rsrc_t re = c2_rsrc(tb.cls2 + (size_t)m2 * CW2_SLICE, 4 * CW2_SLICE);
 #pragma unroll
             for (int i = 0; i < C2_SN; ++i) {
-                if (C2_SKIP(4)) {  // (synthetic entries inside the image, section 0)
-                    v[i] = (float)(tl + i);
-                    e[i] = (uint32_t)(((tl * 37 + i * 4099) & 8191) * 2);
-                    continue;
-                }
                 v[i] = c2_ldf(rs0, 4 * tl + 4 * i * C2_T, 0);
                 e[i] = c2_ldu(re, 4 * tl, 4 * i * C2_T);
             }
@@ -536,7 +440,7 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
         // (requested before the scatter's stores: a later load would wait for them, vmcnt is in order)
         const uint32_t cmk = tb.cmask[m2 * C2_T + tl];
         if (PL && m2 > h * Qh) {
-            accumulate(m2 - 1, ka);
+            accumulate(m2 - 1, kapf);
             __syncthreads();  // the image is read before the scatter overwrites it
         }
         C2_TPC(8);
@@ -549,8 +453,7 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
                 const int sec = e[i] >> 16;
                 const c2f mi = sMI[sec];
                 v[i] = c2_exp2((v[i] - mi.x) * inv_tp) * mi.y;
-                if (!C2_SKIP(256)) dr[e[i] & 0xffffu] = v[i];
-                if (!C2_SKIP(512))
+                dr[e[i] & 0xffffu] = v[i];
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v[i]), rs, 4 * tl + 4 * i * C2_T,
                                                       0, 0);
             }
@@ -559,10 +462,10 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
         __syncthreads();
         C2_TPC(3);
         C2_SETPRIO(C2_PRIO_FFT);
-        if (!C2_SKIP(1)) c2_fft<false>(tl, cmk);
+        c2_fft<false>(tl, cmk);
         C2_SETPRIO(C2_PRIO_REST);
         C2_TPC(6);
-        if constexpr (PF) acc_tables(c2_opaque(tid), kapf);  // class-invariant: in flight across the loop edge
+        if constexpr (PL) acc_tables(c2_opaque(tid), kapf);  // class-invariant: in flight across the loop edge
     }
     {
         uint32_t ka[OT];
@@ -643,7 +546,7 @@ __global__ __launch_bounds__(C2_T) void cw2_ctrl(Cw2Tables tb, RegBufs<float> bf
     }
     const float *xr0 = tb.xr + (size_t)cw * tb.np * OT * C2_T, *xr1 = xr0 + (size_t)OT * C2_T;
     float zr[OT];
-    float2 gmv[C2_POLAR ? OT : 1];
+    float2 gmv[cw2_vz_tm(OT) ? 1 : OT];  // (|al|, |be|) of the slots, where cw2_ctrl scales z / phi (slot-major)
     double acc = 0.0;
     {
         // every load first, in one round trip (the uniform branch outside the slot loops: written per slot,
@@ -653,7 +556,7 @@ __global__ __launch_bounds__(C2_T) void cw2_ctrl(Cw2Tables tb, RegBufs<float> bf
         float *ys = tb.ys + (size_t)cw * OT * C2_T, *zs = tb.zs + (size_t)cw * OT * C2_T;
 #pragma unroll
         for (int j = 0; j < OT; ++j)
-            if constexpr (C2_POLAR != 0) gmv[j] = tb.gm[j * C2_T + tid];
+            if constexpr (!cw2_vz_tm(OT)) gmv[j] = tb.gm[j * C2_T + tid];
         if (have_beta) {  // y, the previous z and the two halves' parts in slot order: coalesced
 #pragma unroll
             for (int j = 0; j < OT; ++j) {
@@ -700,9 +603,8 @@ __global__ __launch_bounds__(C2_T) void cw2_ctrl(Cw2Tables tb, RegBufs<float> bf
     }
     const float iph = (float)(1.0 / phi);
     constexpr int OTP = cw2_otp(OT);
-#if C2_POLAR
-    // z / phi times the slot's (|al|, |be|) (build_cw2 polar form), two floats per slot; padding slots 0
-    if constexpr (cw2_vz_tm(OT) && C2_VZ_HALF) {  // z / phi alone (cw2_az scales it)
+    // the rows' input of cw2_az (build_cw2 polar form); padding slots 0
+    if constexpr (cw2_vz_tm(OT)) {  // z / phi alone, one float per slot (cw2_az scales it by (|al|, |be|))
         float4 *vz4 = reinterpret_cast<float4 *>(tb.vz + ((size_t)cw * C2_T + tid) * OTP);  // thread-major
 #pragma unroll
         for (int q = 0; q < OTP / 4; ++q) {
@@ -711,22 +613,7 @@ __global__ __launch_bounds__(C2_T) void cw2_ctrl(Cw2Tables tb, RegBufs<float> bf
             for (int c = 0; c < 4; ++c) w[c] = 4 * q + c < OT ? zr[4 * q + c] * iph : 0.f;
             vz4[q] = make_float4(w[0], w[1], w[2], w[3]);
         }
-    } else if constexpr (cw2_vz_tm(OT)) {
-        float4 *vz4 = reinterpret_cast<float4 *>(tb.vz + ((size_t)cw * C2_T + tid) * OTP * 2);  // thread-major
-#pragma unroll
-        for (int q = 0; q < OTP / 2; ++q) {
-            float w[4];
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int j = 2 * q + c;
-                const float2 g = j < OT ? gmv[j] : make_float2(0.f, 0.f);
-                const float v = j < OT ? zr[j] * iph : 0.f;
-                w[2 * c] = v * g.x;
-                w[2 * c + 1] = v * g.y;
-            }
-            vz4[q] = make_float4(w[0], w[1], w[2], w[3]);
-        }
-    } else {
+    } else {  // z / phi times the slot's (|al|, |be|), two floats per slot
         float2 *vzs = reinterpret_cast<float2 *>(tb.vz) + (size_t)cw * OT * C2_T;  // slot-major
 #pragma unroll
         for (int j = 0; j < OT; ++j) {
@@ -734,22 +621,6 @@ __global__ __launch_bounds__(C2_T) void cw2_ctrl(Cw2Tables tb, RegBufs<float> bf
             vzs[j * C2_T + tid] = make_float2(v * gmv[j].x, v * gmv[j].y);
         }
     }
-#else
-    if constexpr (cw2_vz_tm(OT)) {
-        float4 *vz4 = reinterpret_cast<float4 *>(tb.vz + ((size_t)cw * C2_T + tid) * OTP);  // thread-major
-#pragma unroll
-        for (int q = 0; q < OTP / 4; ++q) {  // z / phi (sparc.py:972); padding slots 0
-            float w[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) w[c] = 4 * q + c < OT ? zr[4 * q + c] * iph : 0.f;
-            vz4[q] = make_float4(w[0], w[1], w[2], w[3]);
-        }
-    } else {
-        float *vzs = tb.vz + (size_t)cw * OT * C2_T;  // slot-major
-#pragma unroll
-        for (int j = 0; j < OT; ++j) vzs[j * C2_T + tid] = zr[j] * iph;
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------- Az
@@ -766,12 +637,14 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
     const float tau = (float)tv, inv_tau = (float)(C2_LOG2E / tv);  // log2 e / tau (c2_exp2)
     float *s = bf.s + (size_t)cw * tb.LM;
     constexpr int OTP = cw2_otp(OT);
-    // [512][OTP][2] / [OT][512][2] (polar form: (|al|, |be|) z / phi); [512][OTP] / [OT][512] (C2_POLAR 0)
-    constexpr bool VZH = C2_VZ_HALF && C2_POLAR && cw2_vz_tm(OT);
-    const float *vz = tb.vz + (size_t)cw * (cw2_vz_tm(OT) ? OTP : OT) * C2_T * (C2_POLAR && !VZH ? 2 : 1);
+    // z / phi [512][OTP] thread-major (scaled here by (|al|, |be|) from the plan's thread-major table, shared by
+    // every codeword: L2-resident, 4 bytes per slot and codeword instead of the scaled pair's 8 re-read from the
+    // MALL in every class -- fabric bytes 11.35 -> 9.69 MB per codeword-iteration, cw2_az 6.97 -> 5.34, C2 +0.4 %,
+    // profiles/r06_c2_vz_half_ab.txt), or above 12 slots per thread (|al|, |be|) z / phi [OT][512][2] slot-major
+    constexpr bool VZH = cw2_vz_tm(OT);
+    const float *vz = tb.vz + (size_t)cw * (VZH ? OTP : 2 * OT) * C2_T;
     // running statistics of sections tid and tid + 512 over this half's classes
     const int Lb = tb.Lblk;
-#if !C2_STATS_LAUNCH
     float Mr[2] = {-INFINITY, -INFINITY}, R1[2] = {0.f, 0.f}, R2[2] = {0.f, 0.f}, st[2] = {NAN, NAN};
     int jt[2] = {-1, -1};
 #pragma unroll
@@ -779,25 +652,9 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
         const int sec = tid + k * C2_T;
         if (bf.true_idx && sec < Lb) jt[k] = tb.qpos[sec * tb.M + bf.true_idx[lb + sec]];
     }
-#else
-    (void)lb;
-    (void)Lb;
-    (void)inv_tau;
-#endif
     const int Qh = tb.Q / tb.np;
     c2_tw1_init<true>(tid);
     const int *cpl = c2_stage_cp(smem, tb, tid);
-    constexpr bool HOLD = C2_AZ_HOLD && C2_POLAR && OT <= 12;
-    c2f vhold[HOLD ? OT : 1];
-    if constexpr (HOLD) {
-        const __amdgpu_buffer_rsrc_t rv = c2_rsrc(vz, 8 * OTP * C2_T);
-#pragma unroll
-        for (int q = 0; q < OTP / 2; ++q) {
-            const auto w = __builtin_amdgcn_raw_buffer_load_b128(rv, 8 * OTP * tid, 16 * q, 0);
-            if (2 * q < OT) vhold[2 * q] = c2f{__uint_as_float(w[0]), __uint_as_float(w[1])};
-            if (2 * q + 1 < OT) vhold[2 * q + 1] = c2f{__uint_as_float(w[2]), __uint_as_float(w[3])};
-        }
-    }
     __syncthreads();  // the staged statistics
     C2_TP(42);
     for (int m2 = h * Qh; m2 < (h + 1) * Qh; ++m2) {
@@ -813,22 +670,8 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
         // transform: it would spill)
         constexpr bool EARLY = OT <= 12;
         float v[C2_SN];
-        uint32_t e[C2_SN];
-        auto load_v = [&]() {  // beta_prev of the class slice
-#pragma unroll
-            for (int i = 0; i < C2_SN; ++i) {
-                if (C2_SKIP(128)) {  // (synthetic entries inside the image, section 0)
-                    v[i] = (float)(tl + i);
-                    e[i] = (uint32_t)(((tl * 37 + i * 4099) & 8191) * 2);
-                    continue;
-                }
-                v[i] = c2_ldf(rs, 4 * tl + 4 * i * C2_T, 0);  // (t = 0: unused)
-            }
-        };
-        // the entries' positions and (HOLD 0) beta_prev; with the scaled z / phi held in registers (HOLD) beta_prev
-        // is requested after the transform (in flight across it beside the held values, it spills)
-        auto load_slice = [&]() {
-#if C2_AZPOS
+        uint32_t e[C2_SN / 2];
+        auto load_slice = [&]() {  // the entries' positions and beta_prev
             // the entries' image positions two per word (clsp: entries i and i + 9 of the thread), half the
             // table loads and bytes of the full words (the sections are not needed here)
             const __amdgpu_buffer_rsrc_t re = c2_rsrc(tb.clsp + (size_t)m2 * (CW2_SLICE / 2), 2 * CW2_SLICE);
@@ -837,62 +680,39 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
                 const uint32_t w = c2_ldu(re, 4 * tl, 4 * i * C2_T);
                 e[i] = w;  // (packed: entries i and i + 9, unpacked at the gather -- 9 VGPRs across the transform)
             }
-#else
-            const __amdgpu_buffer_rsrc_t re = c2_rsrc(tb.cls2 + (size_t)m2 * CW2_SLICE, 4 * CW2_SLICE);
 #pragma unroll
-            for (int i = 0; i < C2_SN; ++i) e[i] = c2_ldu(re, 4 * tl, 4 * i * C2_T);
-#endif
-            if constexpr (!HOLD) load_v();
+            for (int i = 0; i < C2_SN; ++i) v[i] = c2_ldf(rs, 4 * tl + 4 * i * C2_T, 0);  // (t = 0: unused)
         };
-#if C2_POLAR
-        if (!C2_SKIP(16)) {  // rows r and P - r of each owned pair: sum of al v conj(W) / be v W over its outputs
+        {  // rows r and P - r of each owned pair: sum of al v conj(W) / be v W over its outputs
             // (v = z / phi).  Polar form (build_cw2): al conj(W) = |al| (cos x, sin x) and be W = |be| (sin x,
-            // cos x) with x = ((3 + 8 m2) a + o N/2) / 4N revolutions from the slot word alone, and cw2_ctrl
-            // stores (|al| v, |be| v): per slot and class one phase, two packed FMAs per row, and 12 bytes of
-            // tables instead of 24 (the complex al, be were 16 of them).  Branch-free: every slot accumulates
-            // (NEWROW restarts the sums) and writes both rows -- the pair's rows on its last slot (ENDROW), the
-            // trash slot otherwise (invalid slots: zero scale) -- so the two pairs whose rows coincide (r = 0,
-            // P / 2) write their sum.  (Slot words and v reloaded per class from L1 / L2: held across the
-            // transform, or loaded one class ahead, they spill.)
-            constexpr int CH = OT > 12 ? (OT + 1) / 2 : OT;  // slots per load round (one round at 12 per thread)
-            const __amdgpu_buffer_rsrc_t rv = c2_rsrc(vz, 8 * OTP * C2_T),
-                                         rk = c2_rsrc(cw2_vz_tm(OT) ? tb.kat : tb.ka, 4 * OTP * C2_T);
-            uint32_t kall[CH == OT ? OT : 1];
-            c2f vall[CH == OT ? OT : 1];
-            if constexpr (HOLD) {  // the slot words (shared by every codeword: L2 hits) reloaded per class
-                if (!C2_SKIP(32)) c2_ld_slots<OT>(rk, tl, kall);
+            // cos x) with x = ((3 + 8 m2) a + o N/2) / 4N revolutions from the slot word alone, scaled by
+            // (|al| v, |be| v): per slot and class one phase, two packed FMAs per row, and no per-slot complex
+            // coefficient table re-read every class.  Branch-free: every slot accumulates (NEWROW restarts the
+            // sums) and writes both rows (invalid slots: zero scale).  (Slot words and v reloaded per class from
+            // L1 / L2: held across the transform, or loaded one class ahead, they spill.)
+            constexpr int CH = VZH ? OT : (OT + 1) / 2;  // slots per load round (one round up to 12 per thread)
+            const __amdgpu_buffer_rsrc_t rv2 = c2_rsrc(vz, 8 * OTP * C2_T),  // (the slot-major rounds')
+                                         rk = c2_rsrc(VZH ? tb.kat : tb.ka, 4 * OTP * C2_T);
+            uint32_t kall[VZH ? OT : 1];
+            c2f vall[VZH ? OT : 1];
+            if constexpr (VZH) {  // one load round, 16-byte loads (thread-major): slot words, z / phi (4 B per
+                                  // slot) and the plan's (|al|, |be|)
+                c2_ld_slots<OT>(rk, tl, kall);
+                const __amdgpu_buffer_rsrc_t rv = c2_rsrc(vz, 4 * OTP * C2_T), rg = c2_rsrc(tb.gmt, 8 * OTP * C2_T);
+                float v1[OTP];
 #pragma unroll
-                for (int j = 0; j < OT; ++j) vall[j] = vhold[j];
-            } else if constexpr (VZH) {  // slot words, z / phi (4 B per slot) and the plan's (|al|, |be|)
-                if (!C2_SKIP(32)) {
-                    c2_ld_slots<OT>(rk, tl, kall);
-                    const __amdgpu_buffer_rsrc_t rv1 = c2_rsrc(vz, 4 * OTP * C2_T),
-                                                 rg = c2_rsrc(tb.gmt, 8 * OTP * C2_T);
-                    float v1[OTP];
+                for (int q = 0; q < OTP / 4; ++q) {
+                    const auto w = __builtin_amdgcn_raw_buffer_load_b128(rv, 4 * OTP * tl, 16 * q, 0);
 #pragma unroll
-                    for (int q = 0; q < OTP / 4; ++q) {
-                        const auto w = __builtin_amdgcn_raw_buffer_load_b128(rv1, 4 * OTP * tl, 16 * q, 0);
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) v1[4 * q + c] = __uint_as_float(w[c]);
-                    }
-#pragma unroll
-                    for (int q = 0; q < OTP / 2; ++q) {
-                        const auto w = __builtin_amdgcn_raw_buffer_load_b128(rg, 8 * OTP * tl, 16 * q, 0);
-                        if (2 * q < OT)
-                            vall[2 * q] = c2f{__uint_as_float(w[0]), __uint_as_float(w[1])} * v1[2 * q];
-                        if (2 * q + 1 < OT)
-                            vall[2 * q + 1] = c2f{__uint_as_float(w[2]), __uint_as_float(w[3])} * v1[2 * q + 1];
-                    }
+                    for (int c = 0; c < 4; ++c) v1[4 * q + c] = __uint_as_float(w[c]);
                 }
-            } else if constexpr (CH == OT) {  // one load round: a thread's slot words and scaled z / phi, 16-byte loads
-                if (!C2_SKIP(32)) {
-                    c2_ld_slots<OT>(rk, tl, kall);
 #pragma unroll
-                    for (int q = 0; q < OTP / 2; ++q) {
-                        const auto w = __builtin_amdgcn_raw_buffer_load_b128(rv, 8 * OTP * tl, 16 * q, 0);
-                        if (2 * q < OT) vall[2 * q] = c2f{__uint_as_float(w[0]), __uint_as_float(w[1])};
-                        if (2 * q + 1 < OT) vall[2 * q + 1] = c2f{__uint_as_float(w[2]), __uint_as_float(w[3])};
-                    }
+                for (int q = 0; q < OTP / 2; ++q) {
+                    const auto w = __builtin_amdgcn_raw_buffer_load_b128(rg, 8 * OTP * tl, 16 * q, 0);
+                    if (2 * q < OT)
+                        vall[2 * q] = c2f{__uint_as_float(w[0]), __uint_as_float(w[1])} * v1[2 * q];
+                    if (2 * q + 1 < OT)
+                        vall[2 * q + 1] = c2f{__uint_as_float(w[2]), __uint_as_float(w[3])} * v1[2 * q + 1];
                 }
             }
             const uint32_t cm = 3u + 8u * (uint32_t)m2;
@@ -904,18 +724,12 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
 #pragma unroll
                 for (int i = 0; i < CH; ++i) {
                     const int j = j0 + i < OT ? j0 + i : OT - 1;
-                    if (C2_SKIP(32)) {
-                        const uint32_t r = (uint32_t)(tl * 8 + j) & 4095u;
-                        ka[i] = r | CW_VALID | ((j & 1) ? CW_ENDROW : CW_NEWROW);
-                        vv[i] = c2f{0.5f, (float)j};
-                        continue;
-                    }
-                    if constexpr (CH == OT) {
+                    if constexpr (VZH) {
                         ka[i] = kall[j];
                         vv[i] = vall[j];
                     } else {  // (two load rounds: slot-major, each load a contiguous run of the wavefront)
                         ka[i] = c2_ldu(rk, 4 * tl, 4 * j * C2_T);
-                        const auto w = __builtin_amdgcn_raw_buffer_load_b64(rv, 8 * tl, 8 * j * C2_T, 0);
+                        const auto w = __builtin_amdgcn_raw_buffer_load_b64(rv2, 8 * tl, 8 * j * C2_T, 0);
                         vv[i] = c2f{__uint_as_float(w[0]), __uint_as_float(w[1])};
                     }
                 }
@@ -927,7 +741,6 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
                         (__umul24(cm, k & CW_KMASK) + (((k >> CW_OFFSHIFT) & 7u) << tb.sh_off)) & tb.m4n;
                     const float x = (float)xu * tb.inv_4n;  // (exact: 4N <= 2^24)
                     const c2f cs = c2f{__builtin_amdgcn_cosf(x), __builtin_amdgcn_sinf(x)};
-#if C2_ROWS_ALWAYS
                     // every slot writes its pair's running sums at the pair's rows (one thread owns a pair, so
                     // the pair's last slot writes last: the complete sums), padding slots continue the thread's
                     // last pair with a zero term (build_cw2); row P - r of the r = 0 pair is P, just past the
@@ -947,97 +760,12 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
                     c2lds *pa = (c2lds *)(size_t)(8u * (r + (r >> 5))), *pb = (c2lds *)(size_t)(8u * (rb + (rb >> 5)));
                     *pb = u1;
                     *pa = __builtin_elementwise_fma(u1, c2f{selff, selff}, u0);
-#else
-                    const float keep = (k & CW_NEWROW) ? 0.f : 1.f;
-                    u0 = __builtin_elementwise_fma(cs, vv[j].xx, u0 * keep);
-                    u1 = __builtin_elementwise_fma(cs.yx, vv[j].yy, u1 * keep);
-                    const int r = (int)(k & (uint32_t)(C2_P - 1)), rb = C2_P - r;
-                    const bool end = (k & CW_ENDROW) != 0;
-                    c2lds *pa = (c2lds *)(size_t)(end ? 8u * (uint32_t)c2pos(r) : 4u * CW2_TRASH);
-                    c2lds *pb = (c2lds *)(size_t)((end && !(k & CW_SELF)) ? 8u * (uint32_t)c2pos(rb) : 4u * CW2_TRASH);
-                    *pa = u0;
-                    *pb = u1;
-                    if (k & CW_SELF) *pa = u0 + u1;
-#endif
                 }
             }
         }
-#else
-        if (!C2_SKIP(16)) {  // rows r and P - r of each owned pair: sum of al v conj(W) / be v W over its outputs (v = z / phi),
-           // branch-free: every slot accumulates (NEWROW restarts the sums) and writes both rows -- the
-           // pair's rows on its last slot (ENDROW), the trash slot otherwise (invalid slots: al = be = 0),
-           // addresses derived from the slot word (C2_ROWS_DERIVE; the host table wab is the A/B form) --
-           // the two pairs whose rows coincide (r = 0, P / 2) then write their sum.  (a, al, be, v and the addresses reloaded per class from L1 / L2: held across the transform,
-           // or loaded one class ahead, they spill; al v and be v precomputed per codeword were slower -- four
-           // times the per-codeword bytes re-read from L2 every class.)
-            constexpr int CH = OT > 12 ? (OT + 1) / 2 : OT;  // slots per load round (one round at 12 per thread)
-            const __amdgpu_buffer_rsrc_t rg = c2_rsrc(tb.gf, 16 * OT * C2_T), rv = c2_rsrc(vz, 4 * OTP * C2_T),
-                                         rk = c2_rsrc(cw2_vz_tm(OT) ? tb.kat : tb.ka, 4 * OTP * C2_T),
-                                         rw = c2_rsrc(tb.wab, 8 * OT * C2_T);
-            // one load round (CH == OT): a thread's slot words and z / phi in 16-byte loads (thread-major)
-            uint32_t kall[CH == OT ? OT : 1], vall[CH == OT ? OT : 1];
-            if constexpr (CH == OT) {
-                if (!C2_SKIP(32)) {
-                    c2_ld_slots<OT>(rk, tl, kall);
-                    c2_ld_slots<OT>(rv, tl, vall);
-                }
-            }
-            cx<float> u0{0.f, 0.f}, u1{0.f, 0.f};
-#pragma unroll
-            for (int j0 = 0; j0 < OT; j0 += CH) {
-                uint32_t ka[CH];
-                float4 gc[CH];
-                float vv[CH];
-                uint2 wa[CH];
-#pragma unroll
-                for (int i = 0; i < CH; ++i) {
-                    const int j = j0 + i < OT ? j0 + i : OT - 1;
-                    if (C2_SKIP(32)) {
-                        const uint32_t r = (uint32_t)(tl * 8 + j) & 4095u;
-                        ka[i] = r | CW_VALID | ((j & 1) ? CW_ENDROW : CW_NEWROW);
-                        gc[i] = make_float4(0.5f, 0.25f, 0.125f, 0.75f);
-                        vv[i] = (float)j;
-                        wa[i] = make_uint2(8u * (uint32_t)c2pos((int)r), 8u * (uint32_t)c2pos(8192 - (int)r));
-                        continue;
-                    }
-                    if constexpr (CH == OT) {
-                        ka[i] = kall[j];
-                        vv[i] = __uint_as_float(vall[j]);
-                    } else {  // (two load rounds: slot-major, each load a contiguous run of the wavefront --
-                              // thread-major, every lane of every per-slot load was a cache line of its own)
-                        ka[i] = c2_ldu(rk, 4 * tl, 4 * j * C2_T);
-                        vv[i] = c2_ldf(rv, 4 * tl, 4 * j * C2_T);
-                    }
-                    gc[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rg, 16 * tl, 16 * j * C2_T, 0));
-                    if (!C2_ROWS_DERIVE)
-                        wa[i] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rw, 8 * tl, 8 * j * C2_T, 0));
-                }
-#pragma unroll
-                for (int j = 0; j < CH; ++j) {
-                    if (j0 + j >= OT) break;
-                    const uint32_t k = ka[j];
-                    const cx<float> w = c2_w(tb, __umul24((uint32_t)m2, k & CW_KMASK));  // (a < 2^19, m2 < 2^6)
-                    const float keep = (k & CW_NEWROW) ? 0.f : 1.f;
-                    u0 = cmacc_pk({u0.x * keep, u0.y * keep}, {gc[j].x * vv[j], gc[j].y * vv[j]}, w);
-                    u1 = cmac_pk({u1.x * keep, u1.y * keep}, {gc[j].z * vv[j], gc[j].w * vv[j]}, w);
-                    if (C2_ROWS_DERIVE) {  // the host table wab from the slot's flags: rows on the pair's last slot
-                        const int r = (int)(k & (uint32_t)(C2_P - 1)), rb = C2_P - r;
-                        const bool end = (k & CW_ENDROW) != 0;
-                        wa[j].x = end ? 8u * (uint32_t)c2pos(r) : 4u * CW2_TRASH;
-                        wa[j].y = (end && !(k & CW_SELF)) ? 8u * (uint32_t)c2pos(rb) : 4u * CW2_TRASH;
-                    }
-                    c2lds *pa = (c2lds *)(size_t)wa[j].x, *pb = (c2lds *)(size_t)wa[j].y;
-                    *pa = c2f{u0.x, u0.y};
-                    *pb = c2f{u1.x, u1.y};
-                    if (k & CW_SELF) *pa = c2f{u0.x + u1.x, u0.y + u1.y};
-                }
-            }
-        }
-#endif
         // (requested after the rows' table loads: vector-memory loads complete in order, so a slice
         // requested before them would hold the rows up for its whole HBM latency)
         if constexpr (EARLY) load_slice();
-#if !C2_STATS_LAUNCH
         int sa[2], sb[2];  // the sections' segments of the class (in flight during the transform; sections
                            // past Lb read 0 as their end: empty)
         {
@@ -1049,37 +777,30 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
                 sb[k] = __builtin_amdgcn_raw_buffer_load_b16(rg, 2 * sec + 2, 0, 0);
             }
         }
-#endif
         C2_TPC(33);
         __syncthreads();
         C2_TPC(34);
         C2_SETPRIO(C2_PRIO_FFT);
-        if (!C2_SKIP(8)) c2_fft<true>(tl, rmk);
+        c2_fft<true>(tl, rmk);
         C2_SETPRIO(C2_PRIO_REST);
         C2_TPC(35);
         float snv[C2_SN];
         if constexpr (!EARLY) load_slice();
-        if constexpr (HOLD) load_v();
         {
 #pragma unroll
             for (int i = 0; i < C2_SN; ++i) {  // s = beta_prev + tau u (sparc.py:972); beta_prev stored by cw2_ab
                 const float b = have_beta ? v[i] : 0.f;
-                const uint32_t pos = C2_AZPOS ? (i < C2_SN / 2 ? e[i] & 0xffffu : e[i - C2_SN / 2] >> 16)
-                                              : e[i] & 0xffffu;
-                snv[i] = b + tau * (C2_SKIP(1024) ? (float)i : dr[pos]);
+                const uint32_t pos = i < C2_SN / 2 ? e[i] & 0xffffu : e[i - C2_SN / 2] >> 16;
+                snv[i] = b + tau * dr[pos];
             }
         }
         C2_TPC(36);
-#ifndef C2_DIAG_NO_SSTORE  // (diagnostic builds only: timing without the s stores)
 #pragma unroll
         for (int c = 0; c < C2_SN; ++c)  // s to HBM straight from the registers (class order)
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, snv[c]), rs, 4 * tl + 4 * c * C2_T, 0, 0);
-#endif
         C2_TPC(37);
         __syncthreads();
         C2_TPC(38);
-#if !C2_STATS_LAUNCH
-        if (!C2_SKIP(64)) {
 #pragma unroll
         for (int c = 0; c < C2_SN; ++c) dr[tl + c * C2_T] = snv[c];  // s of the class in class order (past the
                                                                      // end: unread)
@@ -1090,19 +811,23 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
             // partial of the section over its segment: the maximum, then the
             // sums of e and e^2 over every entry but one maximum
             // (e = exp((x - max) / tau)); two passes instead of the online
-            // rescaling (fewer vector instructions).  The first C2_RC entries are
-            // read once for both passes (segments average LM / (Q L) = 8
-            // entries; the rest take the loops below), the reads are
-            // unskewed (every read a base plus a constant; the segment starts
+            // rescaling (fewer vector instructions).  Every round of C2_RC reads
+            // is in the two loops, none held in registers across the maximum
+            // (+0.4 %, +0.2 % in two same-box calls of three rounds,
+            // profiles/r06_c2_stats_rounds_ab.txt; the two sections' rounds
+            // interleaved in one pair of loops measured 2 % slower); the reads
+            // are unskewed (every read a base plus a constant; the segment starts
             // are irregular either way) and entries past the segment are -inf
-            // (exp -> 0).  Same box, every codeword active (tools/c2_ablate.py,
-            // profiles/r05_c2_variants.txt): the statistics were 28 % of
-            // cw2_az; unconditional reads, the fract form below and the rows'
-            // derived addresses took cw2_az 0.588 -> 0.570 ms per launch.
+            // (exp -> 0).  No argmax: in the sums, v_fract_f32 drops the entries
+            // equal to the maximum (e = exp2(0) = 1 exactly, fract 0; below it
+            // e < 1, fract(e) = e) and the entries that tie with it are added back
+            // afterwards from Se - S1 = their count (exact small integers), so
+            // S1 = sum over every entry but one maximum.  Same box, every codeword
+            // active (profiles/r05_c2_variants.txt): the statistics were 28 % of
+            // cw2_az; unconditional reads, the fract form and the rows' derived
+            // addresses took cw2_az 0.588 -> 0.570 ms per launch.
             const int a = sa[k], n = sb[k] - sa[k];
             constexpr int RC = C2_RC;
-#if C2_NOFIRST
-            // every round in the loops (no first round held in registers across the maximum)
             float m = -INFINITY;
             for (int c = 0; c < n; c += RC) {
                 float y[RC];
@@ -1125,73 +850,6 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
                     Se += ex;
                 }
             }
-#else
-            const float *sgp = dr + a;  // inside the LDS image past the segment's end too
-            float x[RC];
-            // every read unconditional, the entries past the segment masked afterwards: written as
-            // `i < n ? sgp[i] : -inf` the compiler put each read in its own exec-masked block (two SALU
-            // mask operations per read, no paired reads)
-#pragma unroll
-            for (int i = 0; i < RC; ++i) x[i] = sgp[i];
-#if C2_ST_BITS
-            {  // -inf past the segment: a lane mask of the segment's first RC entries, then per entry v_bfe_i32
-               // (all ones / zero) and v_bfi -- written as a sign mask the compiler turned it into v_cmp + v_cndmask
-               // through an SGPR pair, with a hazard s_nop per entry
-                uint32_t bits = n >= RC ? 0xffffffffu : ((1u << (n > 0 ? n : 0)) - 1u);
-                const uint32_t ninf = 0xff800000u;
-#pragma unroll
-                for (int i = 0; i < RC; ++i) {
-                    const int mk = __builtin_amdgcn_sbfe((int)bits, i, 1);
-                    uint32_t r;  // (mk & x) | (~mk & -inf) in one v_bfi_b32 (plain VALU, no hazard with its inputs)
-                    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mk), "v"(__float_as_uint(x[i])), "v"(ninf));
-                    x[i] = __uint_as_float(r);
-                }
-            }
-#else
-#pragma unroll
-            for (int i = 0; i < RC; ++i) {  // -inf past the segment by a sign mask and v_bfi
-                const uint32_t mk = (uint32_t)((i - n) >> 31);  // all ones inside the segment
-                x[i] = __uint_as_float((__float_as_uint(x[i]) & mk) | (0xff800000u & ~mk));
-            }
-#endif
-            // no argmax: the maximum by a max3 tree; in the sums, v_fract_f32 drops the entries equal to the
-            // maximum (e = exp2(0) = 1 exactly, fract 0; below it e < 1, fract(e) = e) and the entries that
-            // tie with it are added back afterwards from Se - S1 = their count (exact small integers), so
-            // S1 = sum over every entry but one maximum, as before -- two mask operations fewer per entry
-            float m = x[0];
-#pragma unroll
-            for (int i = 1; i + 1 < RC; i += 2) m = fmaxf(fmaxf(m, x[i]), x[i + 1]);
-            if constexpr (RC % 2 == 0) m = fmaxf(m, x[RC - 1]);
-            for (int c = RC; c < n; c += RC) {
-                float y[RC];
-#pragma unroll
-                for (int i = 0; i < RC; ++i) y[i] = dr[a + c + i];
-#pragma unroll
-                for (int i = 0; i < RC; ++i) m = fmaxf(m, c + i < n ? y[i] : -INFINITY);
-            }
-            float S1 = 0.f, S2 = 0.f, Se = 0.f;
-#pragma unroll
-            for (int i = 0; i < RC; ++i) {
-                const float ex = c2_exp2((x[i] - m) * inv_tau);
-                const float f = __builtin_amdgcn_fractf(ex);
-                S1 += f;
-                S2 += f * f;
-                Se += ex;
-            }
-            for (int c = RC; c < n; c += RC) {
-                float y[RC];
-#pragma unroll
-                for (int i = 0; i < RC; ++i) y[i] = dr[a + c + i];
-#pragma unroll
-                for (int i = 0; i < RC; ++i) {
-                    const float ex = c2_exp2(((c + i < n ? y[i] : -INFINITY) - m) * inv_tau);
-                    const float f = __builtin_amdgcn_fractf(ex);
-                    S1 += f;
-                    S2 += f * f;
-                    Se += ex;
-                }
-            }
-#endif
             {
                 const float ties = rintf(Se - S1) - 1.f;  // entries equal to the maximum, but one (NaN: empty)
                 if (ties > 0.f) {
@@ -1213,116 +871,16 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
             }
             if (jt[k] >= q0 && jt[k] < q1) st[k] = dr[jt[k] - q0];
         }
-        }  // (C2_SKIP(64))
         C2_TPC(40);
         __syncthreads();  // the next class overwrites the image
-#endif
         C2_TPC(41);
     }
     C2_TP(43);
-#if !C2_STATS_LAUNCH
     float4 *part = tb.part + ((size_t)cw * tb.np + h) * Lb;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int sec = tid + k * C2_T;
         if (sec < Lb) part[sec] = make_float4(Mr[k], R1[k], R2[k], st[k]);
-    }
-#endif
-}
-
-// ---------------------------------------------------------------------------- statistics launch
-// (C2_STATS_LAUNCH) After cw2_az: one wavefront per section, lane m its class-m segment of s (class order),
-// the section's entries k = lane + 64 j read in concatenated class order (each entry's class from an owner
-// table the classes' lanes fill); the maximum, then the sums of e = exp((x - max) / tau) and e^2 over every
-// entry but one maximum (the fract form of cw2_az's scan), the section's max and 1 / sum (the next Ab's
-// softmax, sparc.py:429-432, and a hand-over's state), and 1 - sum beta^2 and the squared error per section
-// (sparc.py:973-981) for cw2_final.  Per-lane sums, then a xor tree: a fixed order.
-constexpr int C2_ST_K = 8;  // entries per lane: sections of M <= 512 entries
-__device__ __forceinline__ float c2_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float c2_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-template <int ST_W>
-__global__ __launch_bounds__(64 * ST_W) void cw2_stats(Cw2Tables tb, RegBufs<float> bf) {
-    __shared__ int bas[ST_W][64];
-    __shared__ uint8_t own[ST_W][64 * C2_ST_K];  // the class of each entry of the section
-    const int wpc = tb.Lblk / ST_W;  // workgroups per codeword
-    const int w = (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int cw = blockIdx.x / wpc, l = (blockIdx.x % wpc) * ST_W + w;
-    if (!bf.active[cw]) return;
-    const size_t lb = (size_t)cw * tb.L;
-    const float inv_tau = (float)(C2_LOG2E / bf.tau[cw]);  // log2 e / tau (c2_exp2)
-    const float *s = bf.s + (size_t)cw * tb.LM;
-    int p0 = 0, n = 0;
-    if (lane < tb.Q) {
-        const uint16_t *sg = tb.seg + (size_t)lane * (tb.Lblk + 1);
-        p0 = tb.cls_ptr[lane] + sg[l];
-        n = sg[l + 1] - sg[l];
-    }
-    int inc = n;  // inclusive scan over the lanes
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    const int total = __shfl(inc, 63, 64);  // the section's entries (M)
-    bas[w][lane] = p0 - (inc - n);
-    for (int k = inc - n; k < inc; ++k) own[w][k] = (uint8_t)lane;
-    float st = 0.f;
-    if (bf.true_idx && lane == 0) st = s[tb.qpos[l * tb.M + bf.true_idx[lb + l]]];  // (in flight meanwhile)
-    __syncthreads();
-    float x[C2_ST_K];
-#pragma unroll
-    for (int j = 0; j < C2_ST_K; ++j) {
-        const int k = lane + 64 * j;
-        const bool in = k < total;
-        const int ad = in ? bas[w][own[w][k]] + k : 0;
-        const float v = s[ad];
-        x[j] = in ? v : -INFINITY;
-    }
-    float m = x[0];
-#pragma unroll
-    for (int j = 1; j < C2_ST_K; ++j) m = fmaxf(m, x[j]);
-    m = c2_wave_max(m);
-    float S1 = 0.f, S2 = 0.f, Se = 0.f;
-#pragma unroll
-    for (int j = 0; j < C2_ST_K; ++j) {  // (past the section: exp2(-inf) = 0)
-        const float ex = c2_exp2((x[j] - m) * inv_tau);
-        const float f = __builtin_amdgcn_fractf(ex);
-        S1 += f;
-        S2 += f * f;
-        Se += ex;
-    }
-    S1 = c2_wave_sum(S1);
-    S2 = c2_wave_sum(S2);
-    Se = c2_wave_sum(Se);
-    if (lane == 0) {
-        const float ties = rintf(Se - S1) - 1.f;  // entries equal to the maximum, but one
-        if (ties > 0.f) {
-            S1 += ties;
-            S2 += ties;
-        }
-        const float inv = 1.f / (1.f + S1);
-        bf.stM[lb + l] = m;
-        bf.stI[lb + l] = inv;
-        // 1 - sum beta^2 = (2 R1 + R1^2 - R2) / (1 + R1)^2, no cancellation (as cw2_merge)
-        const double i2 = (double)inv * (double)inv, r1 = S1, r2 = S2;
-        double er = 0.0;
-        if (bf.true_idx) {
-            if (st == m) {
-                er = (r1 * r1 + r2) * i2;
-            } else {
-                const double bt = (double)(c2_exp2((st - m) * inv_tau) * inv);
-                er = (1.0 + r2) * i2 - 2.0 * bt + 1.0;
-            }
-        }
-        reinterpret_cast<double2 *>(tb.part)[lb + l] = make_double2((2.0 * r1 + r1 * r1 - r2) * i2, er);
     }
 }
 
@@ -1336,7 +894,7 @@ __device__ __forceinline__ void c2_psi_stop(const RegBufs<float> &bf, const AmpS
         *psi = pnew;
         nmse[t + 1] = er / denom;
         bool stop = false;
-        if (t > 0 && C2_ABL == 0) {  // (ablation builds never stop early: every launch does the same work)
+        if (t > 0) {
             const double pp = *psi_prev;
             stop = fabs(pnew - pp) <= pr.atol + pr.rtol * fabs(pp);  // sparc.py:984-986
         }
@@ -1405,23 +963,6 @@ __global__ __launch_bounds__(1024) void cw2_merge(Cw2Tables tb, RegBufs<float> b
     c2_psi_stop(bf, sc, pr, cw, t, (double)tb.L, a, er);
 }
 
-// (C2_STATS_LAUNCH) the sections' sums of cw2_stats -> psi, NMSE, stop, in cw2_merge's summation order
-__global__ __launch_bounds__(1024) void cw2_final(Cw2Tables tb, RegBufs<float> bf, AmpScalars sc, AmpParams pr,
-                                                  int t) {
-    __shared__ double red[32];
-    const int cw = blockIdx.x, tid = threadIdx.x;
-    if (!bf.active[cw]) return;
-    const size_t lb = (size_t)cw * tb.L;
-    double a = 0.0, er = 0.0;
-    if (tid < tb.Lblk) {  // (one section per thread, the merge's summation order)
-        const double2 v = reinterpret_cast<const double2 *>(tb.part)[lb + tid];
-        a = v.x;
-        er = v.y;
-    }
-    c2_block_sum2(a, er, red);
-    c2_psi_stop(bf, sc, pr, cw, t, (double)tb.L, a, er);
-}
-
 // z of every codeword in natural order from its slot-order copy (cw2_ctrl keeps z in slot order only): run
 // once, at a hand-over to the staged engine, whose control kernel reads z in natural order
 __global__ __launch_bounds__(C2_T) void cw2_z_natural(Cw2Tables tb, RegBufs<float> bf) {
@@ -1470,15 +1011,7 @@ static int cw2_launch(const Cw2Tables &tb, const RegBufs<float> &bf, const AmpSc
     }
     {
         ProfScope ps(SG_PH_CW2_CTRL, s);
-        if (C2_STATS_LAUNCH) {
-            if (tb.Lblk % 16 == 0)
-                hipLaunchKernelGGL((cw2_stats<16>), dim3(bf.B * (tb.Lblk / 16)), dim3(64 * 16), 0, s, tb, bf);
-            else
-                hipLaunchKernelGGL((cw2_stats<4>), dim3(bf.B * (tb.Lblk / 4)), dim3(64 * 4), 0, s, tb, bf);
-            hipLaunchKernelGGL((cw2_final), gB, dim3(1024), 0, s, tb, bf, sc, pr, t);
-        } else {
-            hipLaunchKernelGGL((cw2_merge), gB, dim3(1024), 0, s, tb, bf, sc, pr, t);
-        }
+        hipLaunchKernelGGL((cw2_merge), gB, dim3(1024), 0, s, tb, bf, sc, pr, t);
     }
     return SG_OK;
 }
@@ -1487,8 +1020,7 @@ int cw2_launch_iter(const Cw2Tables &tb, const RegBufs<float> &bf, const AmpScal
                     hipStream_t s) {
     if (bf.B <= 0) return SG_OK;
     if (tb.Q % 2 || tb.L > 1024 || tb.Lblk > 2 * C2_T || tb.maxcls > C2_NC * C2_SC * C2_T ||
-        fpad(tb.maxcls + 16) >= 2 * C2_P || tb.N2 != C2_P * tb.Q ||
-        (C2_STATS_LAUNCH && (tb.Lblk != tb.L || tb.L % 4 || tb.M > 64 * C2_ST_K || tb.Q > 64)))
+        fpad(tb.maxcls + 16) >= 2 * C2_P || tb.N2 != C2_P * tb.Q)
         return fail(SG_ERR_UNSUPPORTED, "split per-codeword engine: sizes outside its compile-time bounds");
     ProfScope ps(SG_PH_AMP_CW, s);
     switch (tb.OT) {

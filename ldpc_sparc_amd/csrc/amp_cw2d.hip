@@ -48,19 +48,6 @@ namespace sg {
 namespace {
 
 constexpr int D_T = CW2_THREADS;  // 512
-// Phase ablation for timing studies only (tools/mk_variant.sh ... -DD_ABL=<mask>; results are garbage, the
-// shipped build has 0): Ab 1 FFT, 2 accumulation, 4 slice loads, 8 beta exponentials, 16 beta stores,
-// 32 scatter; Az 64 FFT, 128 rows, 256 slice loads, 512 statistics, 1024 s stores, 2048 statistics'
-// exponentials
-#ifndef D_ABL
-#define D_ABL 0
-#endif
-#define D_SKIP(bit) ((D_ABL & (bit)) != 0)
-// Az: the rows' class-invariant tables requested at the end of the previous class (1: 84 loop-carried
-// VGPRs, 68 spilled, Az 1.05 -> 1.93 ms per launch) or at the rows (0)
-#ifndef D_AZPF
-#define D_AZPF 0
-#endif
 constexpr int D_P = 8192;
 constexpr int D_SC = 9, D_NC = 2, D_SN = D_SC * D_NC;  // 18 class entries per thread (CW2_SLICE / 512)
 static_assert(D_SN * D_T == CW2_SLICE, "class slices of 18 entries per thread");
@@ -399,25 +386,20 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_ab(Cw2dTables tb, RegBufs<double>
             const __amdgpu_buffer_rsrc_t re = d_rsrc(tb.cls2 + (size_t)m2 * CW2_SLICE, 4 * CW2_SLICE);
 #pragma unroll
             for (int i = 0; i < D_SN; ++i) {
-                if (D_SKIP(4)) {  // (synthetic entries inside the image, section 0)
-                    v[i] = (double)(tl + i);
-                    e[i] = (uint32_t)(((tl * 37 + i * 4099) & 8191) * 2);
-                    continue;
-                }
                 v[i] = d_ldd(rb, 8 * tl + 8 * i * D_T, 0);
                 e[i] = __builtin_amdgcn_raw_buffer_load_b32(re, 4 * tl, 4 * i * D_T, 0);
             }
         }
         const uint32_t cmk = tb.cmask[m2 * D_T + tl];
-        if (prev && !D_SKIP(2)) {
-            if (prev) accumulate();
+        if (prev) {
+            accumulate();
             __syncthreads();  // the image is read before the scatter overwrites it
         }
 #pragma unroll
         for (int i = 0; i < D_SN; ++i)  // beta scattered into the image (padded entries: the trash slot)
-            if (!D_SKIP(32)) *d_re(e[i] & 0xffffu) = v[i];
+            *d_re(e[i] & 0xffffu) = v[i];
         __syncthreads();
-        if (!D_SKIP(1)) d_fft<false>(tl, cmk, tb.twp);
+        d_fft<false>(tl, cmk, tb.twp);
         acc_tables(d_opaque(tid));
     }
     accumulate();
@@ -559,7 +541,8 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_az(Cw2dTables tb, RegBufs<double>
     __syncthreads();
     const __amdgpu_buffer_rsrc_t rv = d_rsrc(vz, 8 * OT * D_T), rk = d_rsrc(tb.ka, 4 * OT * D_T),
                                  rg = d_rsrc(tb.gf, 32 * OT * D_T);
-    // the rows' slot words, z / phi and S are class-invariant: requested at the end of the previous class
+    // the rows' slot words, z / phi and S are class-invariant, but requested at the rows of every class: held
+    // across the loop they are 84 loop-carried VGPRs, 68 spilled (Az 1.05 -> 1.93 ms per launch)
     uint32_t kall[OT];
     double vall[OT];
     d2 S[OT];
@@ -571,13 +554,12 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_az(Cw2dTables tb, RegBufs<double>
             S[j] = d_ld2(rS, 16 * tl, 16 * j * D_T);
         }
     };
-    if (D_AZPF) rows_tables(tid);
     for (int m2 = mlo; m2 < mhi; ++m2) {
         const int tl = d_opaque(tid);
         const uint32_t rmk = tb.cmask[tb.Q * D_T + tl];
         const int q0 = d_uni(cpl[m2]), q1 = d_uni(cpl[m2 + 1]);
-        if (!D_SKIP(128)) {
-            if (!D_AZPF) rows_tables(tl);
+        {
+            rows_tables(tl);
             // rows r and P - r of each owned pair: sums of al v conj(W) / be v W over its outputs (v = z / phi),
             // branch-free as amp_cw2.hip's rows (NEWROW restarts the sums; both rows written on the pair's last
             // slot, the trash slot otherwise; r = 0, P / 2: the sum at row r)
@@ -618,26 +600,20 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_az(Cw2dTables tb, RegBufs<double>
             const __amdgpu_buffer_rsrc_t re = d_rsrc(tb.cls2 + (size_t)m2 * CW2_SLICE, 4 * CW2_SLICE);
 #pragma unroll
             for (int i = 0; i < D_SN; ++i) {
-                if (D_SKIP(256)) {
-                    v[i] = (double)(tl + i);
-                    e[i] = (uint32_t)(((tl * 37 + i * 4099) & 8191) * 2);
-                    continue;
-                }
                 e[i] = __builtin_amdgcn_raw_buffer_load_b32(re, 4 * tl, 4 * i * D_T, 0);
                 v[i] = have_beta ? d_ldd(rb, 8 * tl + 8 * i * D_T, 0) : 0.0;
             }
         }
         __syncthreads();
-        if (!D_SKIP(64)) d_fft<true>(tl, rmk, tb.twp);
+        d_fft<true>(tl, rmk, tb.twp);
         {
             const __amdgpu_buffer_rsrc_t rs = d_rsrc(s + q0, 8 * (q1 - q0));  // past the class's end: dropped
 #pragma unroll
             for (int i = 0; i < D_SN; ++i) {  // s = beta_prev + tau u (sparc.py:972), class order
                 const double sv = v[i] + tau * *d_re(e[i] & 0xffffu);
-                if (!D_SKIP(1024)) d_std(rs, sv, 8 * tl + 8 * i * D_T, 0);
+                d_std(rs, sv, 8 * tl + 8 * i * D_T, 0);
             }
         }
-        if (D_AZPF && m2 + 1 < mhi) rows_tables(tl);
         __syncthreads();  // the next class overwrites the image
     }
 }
@@ -650,18 +626,12 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_az(Cw2dTables tb, RegBufs<double>
 // One wavefront per section (a segment of it per class: a contiguous run of s in class order, about
 // LM / (Q L) = 8 entries; Q <= 64, M <= 512): every entry read once from HBM, one exponential per
 // entry, sums in a fixed order (per lane, then a xor-shuffle tree).
-// the class of each entry from a per-section owner table each class's lane fills (1), or a binary search
-// over the classes' prefix sums per entry (0) (A/B)
-#ifndef D_ST_OWNER
-#define D_ST_OWNER 1
-#endif
+// The class of each entry comes from a per-section owner table each class's lane fills.
 // sections per workgroup (one wavefront each): the widest of 16, 8, 4 that divides L, at most D_ST_MAXW.  A
 // workgroup's sections are consecutive, so its wavefronts read and write neighbouring segments of every
 // class -- neighbouring cache lines -- together.  Same box, f64 iteration (ms): 4 sections 2.392, 8 2.310,
 // 16 2.198 (2: 2.493), decisions bit-identical (profiles/r05_f64_ablation.txt)
-#ifndef D_ST_MAXW
-#define D_ST_MAXW 16
-#endif
+constexpr int D_ST_MAXW = 16;
 constexpr int ST_WAVES_MIN = 4;
 constexpr int ST_K = 8;      // entries per lane: sections of M <= 512 entries
 __device__ __forceinline__ double d_wave_max(double v) {
@@ -680,9 +650,7 @@ __global__ __launch_bounds__(64 * ST_WAVES) void cw2d_stats(Cw2dTables tb, RegBu
     // (class-order position minus that prefix): entry k of the section lives at base[m] + k, m the last
     // class with prefix[m] <= k
     __shared__ int pre[ST_WAVES][64], bas[ST_WAVES][64];
-#if D_ST_OWNER
     __shared__ uint8_t own[ST_WAVES][64 * ST_K];  // the class of each entry of the section
-#endif
     const int wpc = tb.L / ST_WAVES;  // workgroups per codeword
     const int w = (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int cw = blockIdx.x / wpc, l = (blockIdx.x % wpc) * ST_WAVES + w;
@@ -706,29 +674,17 @@ __global__ __launch_bounds__(64 * ST_WAVES) void cw2d_stats(Cw2dTables tb, RegBu
     const int total = __shfl(inc, 63, 64);  // the section's entries (M)
     pre[w][lane] = inc - n;
     bas[w][lane] = p0 - (inc - n);
-#if D_ST_OWNER
     for (int k = inc - n; k < inc; ++k) own[w][k] = (uint8_t)lane;  // each class marks its segment's entries
-#endif
     __syncthreads();
     // the section's entries k = lane + 64 j in concatenated class order: consecutive lanes read consecutive
     // positions of a segment (coalesced runs), no padding, one exponential per entry
-#if !D_ST_OWNER
-    const int nq = tb.Q;
-#endif
     int ad[ST_K];
     double x[ST_K];
 #pragma unroll
     for (int j = 0; j < ST_K; ++j) {
         const int k = lane + 64 * j;
         const bool in = k < total;
-#if D_ST_OWNER
-        const int lo = in ? (int)own[w][k] : 0;  // (one LDS read instead of a six-step search)
-#else
-        int lo = 0;
-#pragma unroll
-        for (int step = 32; step > 0; step >>= 1)  // last class with pre <= k (empty classes: same pre)
-            if (lo + step < nq && pre[w][lo + step] <= k) lo += step;
-#endif
+        const int lo = in ? (int)own[w][k] : 0;  // (one LDS read instead of a six-step search over the prefix)
         ad[j] = in ? bas[w][lo] + k : 0;
         x[j] = d_keep(s[ad[j]], k, total, 0xfff00000u);  // past the section: -inf
     }
@@ -786,7 +742,7 @@ __global__ __launch_bounds__(1024) void cw2d_final(Cw2dTables tb, RegBufs<double
         *psi = pnew;
         nmse[t + 1] = er / denom;
         bool stop = false;
-        if (t > 0 && D_ABL == 0) {  // (ablation builds never stop early: every launch does the same work)
+        if (t > 0) {
             const double pp = *psi_prev;
             stop = fabs(pnew - pp) <= pr.atol + pr.rtol * fabs(pp);  // sparc.py:984-986
         }

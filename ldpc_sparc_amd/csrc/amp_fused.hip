@@ -24,13 +24,11 @@
 // beta itself never reaches HBM: it is recomputed from s where needed.
 #include "amp.hpp"
 
-// reg_az_stage2 statistics: segment entries per round of LDS reads (entries summed in segment order for any
-// round size: bit-identical results) (A/B)
-#ifndef FUSED_RC
-#define FUSED_RC 16
-#endif
-
 namespace sg {
+
+// reg_az_stage2 statistics: segment entries per round of LDS reads (entries summed in segment order for any
+// round size: bit-identical results)
+constexpr int FUSED_RC = 16;
 
 template <typename T>
 __device__ __forceinline__ T rexp(T x);

@@ -8,7 +8,7 @@
 // Design (DESIGN.md "BP kernel"):
 //   * one workgroup decodes one codeword at a time: one workgroup per codeword
 //     for single-precision min-sum, persistent over the batch otherwise
-//     (grid = occupancy x CUs, codewords pulled by blockIdx stride; BPF_GRID_B);
+//     (grid = occupancy x CUs, codewords pulled by blockIdx stride);
 //   * the whole message state of the codeword lives in LDS for all
 //     iterations: HBM sees only the channel LLRs (read once per iteration
 //     through L2) and the final a-posteriori LLRs;
@@ -29,31 +29,24 @@
 
 #include "bp.hpp"
 
-// table kernels, single-precision min-sum: one workgroup per codeword (1), or a persistent grid of (workgroups
-// per CU) x CUs looping over the batch with the graph tables staged once per workgroup (0) (A/B).  Same box
+namespace sg {
+
+// table kernels, single-precision min-sum: one workgroup per codeword instead of a persistent grid of
+// (workgroups per CU) x CUs looping over the batch with the graph tables staged once per workgroup.  Same box
 // (profiles/r06_bp_grid_ab.txt): 802.11n r5/6 z = 81 (the lean kernel) 6.54 M -> 7.07 M codewords/s; the
 // double-precision sum-product kernels lose 6 % with it (their table staging per codeword), so they stay
 // persistent
-#ifndef BPF_GRID_B
-#define BPF_GRID_B 1
-#endif
+template <typename T, int KIND>
+constexpr bool f32_minsum() { return sizeof(T) == 4 && KIND == SG_MINSUM; }
 
-namespace sg {
-
-// ports per round of the variable pass, and the padding of the LDS port
-// table that lets a round read past the last variable's ports
-#ifndef BP_VU
-#define BP_VU 2
-#endif
+// the variable pass takes two ports per round; the padding of the LDS port
+// table lets a round read past the last variable's ports
 constexpr int BP_PS_PAD = 2;
 
 // Single-precision min-sum: the check pass at issue priority 1 over the variable pass at 0 (the grouped
 // kernel's scheme; three workgroups share a CU): 1.456 -> 1.392 ms per launch on the C3 code (table kernel
 // forced), bit-identical.  Double-precision sumprod2 measured 1 % slower with it, so the other kinds stay
-// flat (profiles/r05_prio_ab.txt).  0: flat for every kind (A/B).
-#ifndef BPF_PRIO
-#define BPF_PRIO 1
-#endif
+// flat (profiles/r05_prio_ab.txt).
 template <typename T>
 __device__ __forceinline__ T dev_log(T x);
 template <>
@@ -295,49 +288,41 @@ __global__ __launch_bounds__(BP_THREADS, (bp_waves_per_simd<T, KIND>())) void bp
                 if (v >= a.nv) continue;
                 const int p0 = (int)(vpd[j] & 0xffffu), d = (int)(vpd[j] >> 16);
                 T acc = chv[j];
-                if constexpr (BP_VU == 2) {
-                    // two ports per round: their table and message reads issued
-                    // together (one LDS round trip per round instead of per port);
-                    // a round may read one padded table entry past d, which is not
-                    // used; acc takes the ports in order (c_ldpc.c:171-178).  The
-                    // check-degree <= 8 kernels at 4 variables a thread take the
-                    // first round's slots from registers (vs01): C3 +10 %, but the
-                    // high-degree (lean) kernels measured slower with it
-                    const int s0 = R0 ? (int)(vs01[R0 ? j : 0] & 0xffffu) : 0;
-                    const int s1 = R0 ? (int)(vs01[R0 ? j : 0] >> 16) : 0;
-                    T m0 = T(0), m1 = T(0);  // (only this thread touches its ports' slots in this pass)
-                    if constexpr (R0) {
-                        m0 = msg[s0];
-                        m1 = msg[s1];
-                        acc = d > 0 ? acc + m0 : acc;
-                        acc = d > 1 ? acc + m1 : acc;
-                    }
-                    for (int k = R0 ? 2 : 0; k < d; k += 2) {
-                        const int sa = ps[p0 + k], sb = ps[p0 + k + 1];
-                        const T ma = msg[sa], mb = msg[sb];
-                        acc += ma;
-                        acc = k + 1 < d ? acc + mb : acc;
-                    }
-                    if constexpr (R0) {
-                        if (d > 0) msg[s0] = acc - m0;
-                        if (d > 1) msg[s1] = acc - m1;
-                    }
-                    for (int k = R0 ? 2 : 0; k < d; k += 2) {
-                        const int sa = ps[p0 + k], sb = ps[p0 + k + 1];
-                        const T ma = msg[sa], mb = msg[sb];
-                        msg[sa] = acc - ma;
-                        if (k + 1 < d) msg[sb] = acc - mb;
-                    }
-                } else {
-                    for (int k = 0; k < d; ++k) acc += msg[ps[p0 + k]];
-                    for (int k = 0; k < d; ++k) {
-                        const int sl = ps[p0 + k];
-                        msg[sl] = acc - msg[sl];
-                    }
+                // two ports per round: their table and message reads issued
+                // together (one LDS round trip per round instead of per port);
+                // a round may read one padded table entry past d, which is not
+                // used; acc takes the ports in order (c_ldpc.c:171-178).  The
+                // check-degree <= 8 kernels at 4 variables a thread take the
+                // first round's slots from registers (vs01): C3 +10 %, but the
+                // high-degree (lean) kernels measured slower with it
+                const int s0 = R0 ? (int)(vs01[R0 ? j : 0] & 0xffffu) : 0;
+                const int s1 = R0 ? (int)(vs01[R0 ? j : 0] >> 16) : 0;
+                T m0 = T(0), m1 = T(0);  // (only this thread touches its ports' slots in this pass)
+                if constexpr (R0) {
+                    m0 = msg[s0];
+                    m1 = msg[s1];
+                    acc = d > 0 ? acc + m0 : acc;
+                    acc = d > 1 ? acc + m1 : acc;
+                }
+                for (int k = R0 ? 2 : 0; k < d; k += 2) {
+                    const int sa = ps[p0 + k], sb = ps[p0 + k + 1];
+                    const T ma = msg[sa], mb = msg[sb];
+                    acc += ma;
+                    acc = k + 1 < d ? acc + mb : acc;
+                }
+                if constexpr (R0) {
+                    if (d > 0) msg[s0] = acc - m0;
+                    if (d > 1) msg[s1] = acc - m1;
+                }
+                for (int k = R0 ? 2 : 0; k < d; k += 2) {
+                    const int sa = ps[p0 + k], sb = ps[p0 + k + 1];
+                    const T ma = msg[sa], mb = msg[sb];
+                    msg[sa] = acc - ma;
+                    if (k + 1 < d) msg[sb] = acc - mb;
                 }
                 apv[j] = acc;
             }
-            if (BPF_PRIO && sizeof(T) == 4 && KIND == SG_MINSUM) __builtin_amdgcn_s_setprio(1);
+            if (f32_minsum<T, KIND>()) __builtin_amdgcn_s_setprio(1);
             __syncthreads();
             // ---- check pass (c_ldpc.c:183-194)
             int unsat = 0;
@@ -360,7 +345,7 @@ __global__ __launch_bounds__(BP_THREADS, (bp_waves_per_simd<T, KIND>())) void bp
                     if (d1 > 0) unsat |= check_update_from<T, KIND, MAXDC>(msg, c1, a.nc, d1, a.factor, L1) ? 1 : 0;
                 }
             }
-            if (BPF_PRIO && sizeof(T) == 4 && KIND == SG_MINSUM) __builtin_amdgcn_s_setprio(0);
+            if (f32_minsum<T, KIND>()) __builtin_amdgcn_s_setprio(0);
             if (!__syncthreads_or(unsat)) break;  // c_ldpc.c:196-197
         }
         T *out = a.app + (size_t)cw * a.nv;
@@ -387,7 +372,7 @@ static int launch_one(const BpArgs<T> &a, size_t lds, hipStream_t s) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, BP_THREADS, lds) != hipSuccess || per_cu < 1)
         per_cu = 1;
     int grid = per_cu * device_cu_count();
-    if ((BPF_GRID_B && sizeof(T) == 4 && KIND == SG_MINSUM) || grid > a.B) grid = a.B;
+    if (f32_minsum<T, KIND>() || grid > a.B) grid = a.B;
     if (lds > 64 * 1024)
         SG_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ProfScope ps(SG_PH_BP, s);

@@ -32,15 +32,6 @@
 // kernel (capi_ldpc.cpp), the device entry point documents it.
 #include "bp.hpp"
 
-// one workgroup per codeword (1: the hardware dispatcher hands each finished workgroup's CU slot to the next
-// codeword; a workgroup's LDS image starts uninitialised, which the first iteration's read-free variable pass
-// and the per-iteration flag words allow), or a persistent grid of (workgroups per CU) x CUs looping over the
-// batch (0) (A/B).  Same box, two calls (profiles/r06_bp_grid_ab.txt): C3 5.91 M -> 6.24 M and 5.94 M -> 6.34 M
-// codewords/s, 0.62-0.63 -> 0.66-0.67 of the LDS bound, bit-identical
-#ifndef BPG_GRID_B
-#define BPG_GRID_B 1
-#endif
-
 namespace sg {
 
 // Channel LLRs are saturated at this magnitude on load (far beyond any LLR a
@@ -48,25 +39,12 @@ namespace sg {
 // terms of it still sum to a finite float, so no inf - inf reaches the
 // variable pass from the input.
 constexpr float GRP_CH_MAX = 1e30f;
-// two check groups of one degree in a wave run together (A/B: -DBPG_CHECK_PAIRS=1; same box within noise,
-// profiles/r05_bp_ab.txt, and it spills a VGPR in the codeword loop: off)
-#ifndef BPG_CHECK_PAIRS
-#define BPG_CHECK_PAIRS 0
-#endif
 // Wave issue priority of the variable and the check pass.  Four workgroups share a CU, each pass a chain
 // of table / LDS round trips between two barriers; the check pass at 1 over the variable pass at 0:
 // 0.694 / 0.701 / 0.685 -> 0.659 / 0.661 / 0.654 ms per launch at 1.0 / 1.5 / 2.0 dB, same box, bit-identical
 // (check pass at 2 or 3, or variable pass at 1 under a check pass at 2, within noise of it:
-// profiles/r05_prio_ab.txt).  Both equal: flat, for the A/B.
-#ifndef BPG_PRIO_V
-#define BPG_PRIO_V 0
-#endif
-#ifndef BPG_PRIO_C
-#define BPG_PRIO_C 1
-#endif
-#ifndef BPG_SETUP_BATCH
-#define BPG_SETUP_BATCH 0
-#endif
+// profiles/r05_prio_ab.txt).
+constexpr int BPG_PRIO_V = 0, BPG_PRIO_C = 1;
 
 // LDS words addressed by their byte address.  The kernel has no static LDS
 // (grouped_one checks), so its dynamic image starts at address 0 and the
@@ -189,56 +167,6 @@ __device__ __forceinline__ uint32_t grp_check(uint32_t addr, float factor, uint3
     return unsat;
 }
 
-// Two check groups of one degree DC together: both groups' LDS reads in flight
-// at once, then both updates (one chain of round trips for the pair).  Each
-// check's update is grp_check's, operation for operation.
-template <int DC>
-__device__ __forceinline__ uint32_t grp_check2(uint32_t addr0, uint32_t addr1, float factor, uint32_t fsign,
-                                               bool valid0, bool valid1) {
-    float L0[DC], L1[DC];
-    lds_f32 *c0 = ldsf(addr0), *c1 = ldsf(addr1);
-#pragma unroll
-    for (int k = 0; k < DC; ++k) {
-        L0[k] = c0[64 * k];
-        L1[k] = c1[64 * k];
-    }
-    uint32_t u = 0u;
-    auto upd = [&](float *L, lds_f32 *c, bool valid) {
-        float m1 = INFINITY, m2 = INFINITY;
-        uint32_t S = 0u;
-#pragma unroll
-        for (int k = 0; k < DC; ++k) {
-            const float a = fabsf(L[k]);
-            m2 = __builtin_amdgcn_fmed3f(a, m1, m2);
-            m1 = fminf(m1, a);
-            S ^= __float_as_uint(L[k]);
-        }
-        const uint32_t unsat = (S >> 31) | (m1 > 0.0f ? 0u : 1u);
-        uint32_t b1 = __float_as_uint(m1 * factor) & 0x7fffffffu, b2 = __float_as_uint(m2 * factor) & 0x7fffffffu;
-        asm volatile("" : "+v"(b1), "+v"(b2));
-        const uint32_t Sf = S ^ fsign;
-#pragma unroll
-        for (int k = 0; k < DC; ++k) {
-            const uint32_t mag = fabsf(L[k]) == m1 ? b2 : b1;
-            c[64 * k] = __uint_as_float(((__float_as_uint(L[k]) ^ Sf) & 0x80000000u) | mag);
-        }
-        u |= valid ? unsat : 0u;
-    };
-    upd(L0, c0, valid0);
-    upd(L1, c1, valid1);
-    return u;
-}
-
-__device__ __forceinline__ uint32_t grp_check2_d(int d, uint32_t a0, uint32_t a1, float f, uint32_t fs, bool v0,
-                                                 bool v1) {
-    switch (d) {
-#define SG_GC2(N) case N: return grp_check2<N>(a0, a1, f, fs, v0, v1);
-        SG_GC2(2) SG_GC2(3) SG_GC2(4) SG_GC2(5) SG_GC2(6) SG_GC2(7)
-#undef SG_GC2
-        default: return 0u;
-    }
-}
-
 // uniform (per-wave) degree dispatch
 template <bool F2>
 __device__ __forceinline__ float grp_var_d(int d, const uint16_t *gtab, float acc, uint32_t first2, bool init) {
@@ -317,33 +245,12 @@ __global__ __launch_bounds__(BP_THREADS, VJ <= 4 ? 8 : 6) void bp_grouped_minsum
             // hoisted out of the codeword loop (live across the decode they would not fit the 64 VGPRs)
             int zo = 0;
             asm volatile("" : "+v"(zo));
-#if BPG_SETUP_BATCH
-            // raw buffer loads, no branch: a padding lane (variable -1) reads past the buffer's end, which the
-            // hardware range check returns as 0
-            const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<int32_t *>(a.vmap + wave * VJ * 64), 0, 4 * 64 * VJ, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ch), 0,
-                                                                                4 * a.nv, 0x00020000);
-            int v[VJ];
-#pragma unroll
-            for (int j = 0; j < VJ; ++j)
-                v[j] = j < a.vj ? (int)__builtin_amdgcn_raw_buffer_load_b32(rm, 4 * (lane + zo), 4 * 64 * j, 0) : -1;
-#pragma unroll
-            for (int j = 0; j < VJ; ++j) {
-                // saturated at +-GRP_CH_MAX (and inf with it): the kernel is built
-                // without NaN semantics, and a sum of saturated inputs stays finite
-                const float x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc, 4 * v[j], 0, 0));
-                chv[j] = __builtin_amdgcn_fmed3f(x, -GRP_CH_MAX, GRP_CH_MAX);
-                apv[j] = 0.0f;
-            }
-#else
 #pragma unroll
             for (int j = 0; j < VJ; ++j) {
                 const int v = j < a.vj ? vmap[64 * j + zo] : -1;
                 chv[j] = v >= 0 ? __builtin_amdgcn_fmed3f(ch[v], -GRP_CH_MAX, GRP_CH_MAX) : 0.0f;
                 apv[j] = 0.0f;
             }
-#endif
         }
         // ---- variable pass (c_ldpc.c:171-178): groups 2i and 2i + 1 as a pair
         // when the host flagged one (pairs sit at even positions)
@@ -369,25 +276,20 @@ __global__ __launch_bounds__(BP_THREADS, VJ <= 4 ? 8 : 6) void bp_grouped_minsum
         // ended it)
         int it = 0;
         for (; it < a.max_it; ++it) {
-            if (BPG_PRIO_V != BPG_PRIO_C) __builtin_amdgcn_s_setprio(BPG_PRIO_V);
+            __builtin_amdgcn_s_setprio(BPG_PRIO_V);
             var_pass(it == 0);  // (the first: zero incoming messages, no reads, no zeroed image)
-            if (BPG_PRIO_V != BPG_PRIO_C) __builtin_amdgcn_s_setprio(BPG_PRIO_C);
+            __builtin_amdgcn_s_setprio(BPG_PRIO_C);
             __syncthreads();
             // ---- check pass (c_ldpc.c:183-194 with the min-sum update)
             uint32_t unsat = 0u;
 #pragma unroll
             for (int q = 0; q < CJ; q += 2) {
                 if (q >= a.cj) continue;
-                if (BPG_CHECK_PAIRS && q + 1 < a.cj && cdg[q + 1] == cdg[q] && cdg[q] <= 7) {  // (uniform; degree 8 pairs spill)
-                    unsat |= grp_check2_d(cdg[q], ca[q] + 4 * lane, ca[q + 1] + 4 * lane, factor, fsign,
-                                          lane < cn[q], lane < cn[q + 1]);
-                } else {
-                    const uint32_t u = grp_check_d(cdg[q], ca[q] + 4 * lane, factor, fsign);
-                    unsat |= lane < cn[q] ? u : 0u;
-                    if (q + 1 < a.cj) {
-                        const uint32_t u1 = grp_check_d(cdg[q + 1], ca[q + 1] + 4 * lane, factor, fsign);
-                        unsat |= lane < cn[q + 1] ? u1 : 0u;
-                    }
+                const uint32_t u = grp_check_d(cdg[q], ca[q] + 4 * lane, factor, fsign);
+                unsat |= lane < cn[q] ? u : 0u;
+                if (q + 1 < a.cj) {
+                    const uint32_t u1 = grp_check_d(cdg[q + 1], ca[q + 1] + 4 * lane, factor, fsign);
+                    unsat |= lane < cn[q + 1] ? u1 : 0u;
                 }
             }
             // ---- stop when every check is satisfied (c_ldpc.c:196-197): one
@@ -424,15 +326,15 @@ static int grouped_one(const BpGrpArgs &a, hipStream_t s) {
     }();
     if (static_lds != 0)  // the slot addresses assume the dynamic image at LDS address 0
         return fail(SG_ERR_UNSUPPORTED, "grouped BP kernel has static LDS (%zu B)", static_lds);
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, BP_THREADS, lds) != hipSuccess || per_cu < 1)
-        per_cu = 1;
-    int grid = per_cu * device_cu_count();
-    if (BPG_GRID_B || grid > a.B) grid = a.B;
+    // One workgroup per codeword: the hardware dispatcher hands each finished workgroup's CU slot to the next
+    // codeword (a workgroup's LDS image starts uninitialised, which the first iteration's read-free variable pass
+    // and the per-iteration flag words allow).  Against a persistent grid of (workgroups per CU) x CUs looping
+    // over the batch, same box, two calls (profiles/r06_bp_grid_ab.txt): C3 5.91 M -> 6.24 M and 5.94 M -> 6.34 M
+    // codewords/s, 0.62-0.63 -> 0.66-0.67 of the LDS bound, bit-identical
     if (lds > 64 * 1024)
         SG_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ProfScope ps(SG_PH_BP, s);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(BP_THREADS), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(a.B), dim3(BP_THREADS), lds, s, a);
     SG_HIP(hipGetLastError());
     return SG_OK;
 }

@@ -77,8 +77,7 @@ struct sg_amp_plan {
     int c2_np = 2;                // f32 split engine: workgroups per codeword for the next launches (decode_regular)
     uint32_t *c2_ka = nullptr, *c2_kat = nullptr, *c2_cmask = nullptr, *c2_cls = nullptr, *c2_clsp = nullptr;
     int32_t *c2_oi = nullptr;
-    uint32_t *c2_wab = nullptr, *c2_rab = nullptr;
-    void *c2_cf = nullptr, *c2_gf = nullptr;
+    void *c2_cf = nullptr;
     float *c2_gm = nullptr;  // [OT][512][2] (|al|, |be|) of the polar row form (build_cw2)
     float *c2_gmt = nullptr; // [512][OTP][2] the same, thread-major
     int c2_shoff = 0;        // log2(N / 2): unit of the slot's phase offset
@@ -95,7 +94,7 @@ struct sg_amp_plan {
     int b2_log2p = 0;            // classes of 2^13 points (two workgroups per CU); class size P = 2^b2_log2p
     int32_t *b_gk = nullptr;
     uint16_t *b_gloc = nullptr;
-    uint32_t *b_pos2 = nullptr, *b_pos1 = nullptr, *b_oab = nullptr;
+    uint32_t *b_pos2 = nullptr, *b_oab = nullptr;
     int32_t *b_gptr = nullptr, *b_gi = nullptr, *b_grow = nullptr;
     int b_ngs = 0;
     void *ws_gbuf = nullptr;  // [B][b_ngs] G slots (block engine)
@@ -281,7 +280,7 @@ static AmpTables<T> tables(const sg_amp_plan *p) {
     return tb;
 }
 
-// Phase ablation for timing studies (tools/ablate3.sh): compiled only into a
+// Phase ablation for timing studies: compiled only into a
 // diagnostic build (make DIAG=1), because the results are wrong when a phase
 // is skipped.  The product library ignores SG_AMP_SKIP.
 static int diag_skip() {
@@ -298,7 +297,7 @@ static BlkTables btables(const sg_amp_plan *p) {
     tb.nT = p->nT; tb.L = p->L; tb.M = p->M; tb.LM = p->LM; tb.n = p->n; tb.Lr = p->Lr; tb.Lc = p->Lc;
     tb.Mr = p->Mr; tb.Mc = p->Mc;
     tb.col_ptr = p->col_ptr; tb.col_t = p->col_t; tb.t_row = p->t_row;
-    tb.pos2 = p->b_pos2; tb.pos1 = p->b_pos1; tb.oab = p->b_oab; tb.oc = (const cx<float> *)p->b_oc;
+    tb.pos2 = p->b_pos2; tb.oab = p->b_oab; tb.oc = (const cx<float> *)p->b_oc;
     tb.ngs = p->b_ngs; tb.gptr = p->b_gptr; tb.grow = p->b_grow; tb.gloc = p->b_gloc; tb.gi = p->b_gi; tb.gc = (const cx<float> *)p->b_gc;
     tb.gk = p->b_gk;
     tb.stw = (const cx<float> *)p->b_stw;
@@ -326,9 +325,6 @@ static AmpBufs<T> bufs(const sg_amp_plan *p, int B, const void *y) {
 // threads in different lane groups when the summed worst bank multiplicity
 // of the cells they touch does not grow.  Deterministic (fixed seed); the
 // slot structure of every thread is unchanged.
-#ifndef CW_BANKBAL
-#define CW_BANKBAL 1
-#endif
 static void cw_bank_balance(std::vector<std::vector<int>> &own, const std::vector<int32_t> &row_k1,
                             const std::vector<int32_t> &kptr, int KT) {
     const int T = CW_THREADS;
@@ -411,9 +407,7 @@ static int build_cw(sg_amp_plan *p, const std::vector<int32_t> &row_k1, const st
     }
     if (KT > 14) return SG_OK;  // the staged engine only
     KT = KT <= 12 ? 12 : 14;   // kernel instances (cw_iter<12>: all slots in LDS; <14>: two in registers)
-#if CW_BANKBAL
     cw_bank_balance(own, row_k1, kptr, KT);
-#endif
     const int P = p->rP, n = p->n;
     std::vector<uint32_t> kt((size_t)KT * CW_THREADS, 0u);
     std::vector<int32_t> cmap(nk, 0);
@@ -499,16 +493,6 @@ static int build_cw(sg_amp_plan *p, const std::vector<int32_t> &row_k1, const st
 // of the cells they touch does not grow.  Every output keeps its arithmetic (same slot structure per
 // thread, same class order); only the order of cw2_ctrl's sum of z^2 (phi) follows the placement.
 // Deterministic (fixed seed).
-// f32 split engine: four workgroups per codeword once codewords have stopped (1), always two (0) (A/B)
-#ifndef C2_PARTS_ADAPT
-#define C2_PARTS_ADAPT 1
-#endif
-#ifndef CW2_BANKBAL
-#define CW2_BANKBAL 1
-#endif
-#ifndef CW2_BANKW
-#define CW2_BANKW 0
-#endif
 static void cw2_bank_balance(std::vector<std::vector<int>> &own, const std::vector<std::vector<int>> &pair_of,
                              int OT, int P) {
     const int T = CW2_THREADS;
@@ -524,15 +508,7 @@ static void cw2_bank_balance(std::vector<std::vector<int>> &own, const std::vect
             }
         }
     }
-    // the lanes of a group hold distinct pairs at a slot, so distinct rows; empty slots all read row 0.
-    // CW2_BANKW: cw2_az's row writes counted too -- ds_write_b64 serves 16-lane groups on 32 banks, so two
-    // lanes of one 16-lane half collide when their rows' slots agree mod 16 (padding slots write the
-    // thread's last pair again: C2_ROWS_ALWAYS)
-    auto last_row = [&](int t, int j) {
-        for (int q = j; q >= 0; --q)
-            if (at[(size_t)t * OT + q] >= 0) return at[(size_t)t * OT + q];
-        return 0;
-    };
+    // the lanes of a group hold distinct pairs at a slot, so distinct rows; empty slots all read row 0
     auto cell = [&](int g, int j) {
         int ca[32] = {0}, cb[32] = {0}, wa = 0, wb = 0;
         bool empty = false;
@@ -546,19 +522,7 @@ static void cw2_bank_balance(std::vector<std::vector<int>> &own, const std::vect
             wa = std::max(wa, ++ca[c2pos(ra) & 31]);
             if (rb != ra) wb = std::max(wb, ++cb[c2pos(rb) & 31]);
         }
-        int w = wa + wb;
-        if (CW2_BANKW) {
-            for (int hf = 0; hf < 2; ++hf) {
-                int sa[16] = {0}, sb[16] = {0}, xa = 0, xb = 0;
-                for (int l = 16 * hf; l < 16 * hf + 16; ++l) {
-                    const int ra = last_row(g * 32 + l, j), rb = (P - ra) % P;
-                    xa = std::max(xa, ++sa[c2pos(ra) & 15]);
-                    xb = std::max(xb, ++sb[c2pos(rb) & 15]);
-                }
-                w += xa + xb;
-            }
-        }
-        return w;
+        return wa + wb;
     };
     std::vector<std::vector<int>> by((size_t)OT * (OT + 1));
     for (int t = 0; t < T; ++t)
@@ -654,15 +618,14 @@ static int build_cw2(sg_amp_plan *p, const uint32_t *o0, double sc, const std::v
     }
     if (OT > 16) return SG_OK;  // kernel instances for 12, 13, 14 and 16 outputs per thread
     OT = OT <= 12 ? 12 : OT <= 14 ? OT : 16;
-    if (CW2_BANKBAL) cw2_bank_balance(own, pair_of, OT, P);
+    cw2_bank_balance(own, pair_of, OT, P);
     std::vector<uint32_t> ka((size_t)OT * T, 0u);
     std::vector<int32_t> oi((size_t)OT * T, 0);
-    std::vector<float> cf((size_t)OT * T * 4, 0.f), gf((size_t)OT * T * 4, 0.f);
+    std::vector<float> cf((size_t)OT * T * 4, 0.f);
     const bool f64 = p->precision == SG_F64;
     std::vector<double> cfd(f64 ? (size_t)OT * T * 4 : 0, 0.0), gfd(f64 ? (size_t)OT * T * 4 : 0, 0.0),
         sad(f64 ? (size_t)OT * T * 2 : 0, 0.0);
     for (size_t i = 0; i < sad.size(); i += 2) sad[i] = 1.0;  // invalid slots: S = 1
-    std::vector<uint32_t> wab((size_t)OT * T * 2, 4u * CW2_TRASH), rab((size_t)OT * T * 2, 0u);
     // Polar form of the inverse coefficients (amp_cw2.hip Az rows): with U = 1 / (4N) revolutions,
     // inv_contrib's al and be are real multiples of unit phasors, al = |al| e^(2 pi i A U) and
     // be = |be| e^(2 pi i (N - A) U), A = 3a + o N/2 (o in {0, 1, 6, 7} by the output's case: q below or
@@ -714,18 +677,10 @@ static int build_cw2(sg_amp_plan *p, const uint32_t *o0, double sc, const std::v
                     gm[2 * c + 1] = (float)mb;
                 }
                 ka[c] = e;
-                rab[2 * c] = 8u * (uint32_t)c2pos(r);
-                rab[2 * c + 1] = 8u * (uint32_t)c2pos((P - r) % P);
-                if (q + 1 == lst.size()) {  // the pair's row writes (amp_cw2.hip Az rows)
-                    wab[2 * c] = 8u * (uint32_t)c2pos(r);
-                    wab[2 * c + 1] = (e & CW_SELF) ? 4u * CW2_TRASH : 8u * (uint32_t)c2pos(P - r);
-                }
                 oi[c] = i;
                 last_word[tid] = e & ~(CW_VALID | CW_NEWROW);  // (the padding slots below)
-                const float v[8] = {(float)o.c1.real(), (float)o.c1.imag(), (float)o.c2.real(), (float)o.c2.imag(),
-                                    (float)o.al.real(), (float)o.al.imag(), (float)o.be.real(), (float)o.be.imag()};
+                const float v[4] = {(float)o.c1.real(), (float)o.c1.imag(), (float)o.c2.real(), (float)o.c2.imag()};
                 std::copy(v, v + 4, cf.begin() + 4 * c);
-                std::copy(v + 4, v + 8, gf.begin() + 4 * c);
                 if (f64) {
                     const double d[8] = {o.c1.real(), o.c1.imag(), o.c2.real(), o.c2.imag(),
                                          o.al.real(), o.al.imag(), o.be.real(), o.be.imag()};
@@ -739,7 +694,7 @@ static int build_cw2(sg_amp_plan *p, const uint32_t *o0, double sc, const std::v
         }
     }
     // Padding slots (after a thread's pairs; zero coefficients, zero z/phi scale, not VALID) carry the word of
-    // the thread's last output without CW_NEWROW: the f32 rows (amp_cw2.hip, C2_ROWS_ALWAYS) write every
+    // the thread's last output without CW_NEWROW: the f32 rows (amp_cw2.hip cw2_az) write every
     // slot's running sum at its pair's rows, so a padding slot adds 0 to the last pair's sums and writes them
     // again -- never a row of another thread's pair
     if (p->precision != SG_F64)
@@ -799,13 +754,9 @@ static int build_cw2(sg_amp_plan *p, const uint32_t *o0, double sc, const std::v
         SG_TRY(upload(p, &p->c2_kat, kat));
     }
     SG_TRY(upload(p, &p->c2_oi, oi));
-    SG_TRY(upload(p, &p->c2_wab, wab));
-    SG_TRY(upload(p, &p->c2_rab, rab));
-    float *dcf = nullptr, *dgf = nullptr;
+    float *dcf = nullptr;
     SG_TRY(upload(p, &dcf, cf));
-    SG_TRY(upload(p, &dgf, gf));
     p->c2_cf = dcf;
-    p->c2_gf = dgf;
     SG_TRY(upload(p, &p->c2_gm, gm));
     {  // thread-major copy of (|al|, |be|): thread tid's slots at [tid][OTP][2] (16-byte loads of two slots)
         const int OTP = cw2_otp(OT);
@@ -1128,11 +1079,11 @@ static Cw2Tables c2tables(const sg_amp_plan *p, int B) {
     tb.np = p->c2_np >= 4 && CW2_NP >= 4 && p->rQ % 4 == 0 ? 4 : 2;
     tb.inv_n2 = 1.0f / (float)p->N2;
     tb.cmask = p->c2_cmask; tb.ka = p->c2_ka; tb.kat = p->c2_kat; tb.oi = p->c2_oi;
-    tb.cf = (const float4 *)p->c2_cf; tb.gf = (const float4 *)p->c2_gf; tb.gm = (const float2 *)p->c2_gm;
+    tb.cf = (const float4 *)p->c2_cf; tb.gm = (const float2 *)p->c2_gm;
     tb.gmt = (const float4 *)p->c2_gmt;
     tb.sh_off = p->c2_shoff; tb.m4n = (uint32_t)(4 * p->w - 1); tb.inv_4n = (float)(1.0 / (4.0 * (double)p->w));
     tb.cls_ptr = p->r_cls_ptr; tb.cls_ls = p->r_cls_ls; tb.cls2 = p->c2_cls; tb.clsp = p->c2_clsp; tb.qpos = p->r_qpos; tb.seg = p->r_seg;
-    tb.xr = (float *)p->ws_c2xp; tb.vz = (float *)p->ws_c2vz; tb.ys = (float *)p->ws_c2ys; tb.zs = (float *)p->ws_c2zs; tb.wab = (const uint2 *)p->c2_wab; tb.rab = (const uint2 *)p->c2_rab; tb.part = (float4 *)p->ws_c2part;
+    tb.xr = (float *)p->ws_c2xp; tb.vz = (float *)p->ws_c2vz; tb.ys = (float *)p->ws_c2ys; tb.zs = (float *)p->ws_c2zs; tb.part = (float4 *)p->ws_c2part;
     // [2 B][64] stamps, only when the diagnostics buffer holds them (build_cw2
     // accepts any even Q, and B * Q * 20 < 128 B for Q < 7)
     tb.tprof = (p->tprof && p->tprof_items * 20 >= (size_t)128 * B) ? p->tprof : nullptr;
@@ -1299,7 +1250,6 @@ static int build_block2(sg_amp_plan *p, const uint32_t *order0, const uint32_t *
     constexpr uint32_t TRASH = 2 * 32;
     static_assert(ppos(32) == 33, "complex position 32 is a padding slot");
     std::vector<uint32_t> pos2((size_t)nT * 2 * (J / 2) * T, TRASH | (TRASH << 16));
-    std::vector<uint32_t> pos1((size_t)nT * (J / 2) * T, 0u);  // one-table form (amp_block2.hip B2_ONETABLE)
     std::vector<uint32_t> oab((size_t)nT * Mr);
     std::vector<cd> oc((size_t)nT * 2 * Mr * 8), gc;
     std::vector<int32_t> gptr(nT + 1, 0), gi, grow, gk;
@@ -1316,9 +1266,6 @@ static int build_block2(sg_amp_plan *p, const uint32_t *order0, const uint32_t *
             const int tid = (l / spw) * 64 + rr / eps, i = (l % spw) * eps + rr % eps;
             uint32_t &w = pos2[(((size_t)t * 2 + (m & 1)) * (J / 2) + i / 2) * T + tid];
             w = (w & ~(0xffffu << (16 * (i & 1)))) | (lds << (16 * (i & 1)));
-            const uint32_t e1 = (uint32_t)((m >> 1) << 2) | (uint32_t)((sl & 1) << 1) | (uint32_t)(m & 1);
-            SG_CHECK_ARG((m >> 1) < (1LL << 14), "internal: one-table entry beyond 16 bits");
-            pos1[((size_t)t * (J / 2) + i / 2) * T + tid] |= e1 << (16 * (i & 1));
         }
         std::vector<std::vector<std::pair<int, cd>>> gcon(N2);
         for (int i = 0; i < Mr; ++i) {
@@ -1362,7 +1309,6 @@ static int build_block2(sg_amp_plan *p, const uint32_t *order0, const uint32_t *
         }
     }
     SG_TRY(upload(p, &p->b_pos2, pos2));
-    SG_TRY(upload(p, &p->b_pos1, pos1));
     SG_TRY(upload(p, &p->b_oab, oab));
     SG_TRY(upload_cx(p, &p->b_oc, oc));
     SG_TRY(upload(p, &p->b_gptr, gptr));
@@ -1669,7 +1615,7 @@ static int decode_regular(sg_amp_plan *p, const void *d_y, int B, const int32_t 
         int na = -1;
         SG_TRY(poll.collect(&na));  // the flags after iteration t - 1
         if (na == 0) break;
-        if (na > 0 && na < B && C2_PARTS_ADAPT) p->c2_np = 4;
+        if (na > 0 && na < B) p->c2_np = 4;
         if (na > 0 && cw && !cw_forced && na < handover * B) {
             cw = false;
             p->last_handover = t + 1;  // first iteration on the staged engine

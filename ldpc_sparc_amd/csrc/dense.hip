@@ -38,29 +38,21 @@ constexpr int GBN = 128, GBK = 32, GPAD = GBK + 1;
 
 // The design-matrix operand (Y) is streamed once per launch; its loads can be
 // non-temporal so that its lines leave the XCD's L2 first and the batch
-// operand, which every N tile re-reads, stays resident (-DGEMM_Y_NT=0 for the A/B; on by default: 19.04 -> 18.91 ms per C5 GEMM launch same box, bit-identical).
-#ifndef GEMM_Y_NT
-#define GEMM_Y_NT 1
-#endif
+// operand, which every N tile re-reads, stays resident (19.04 -> 18.91 ms per
+// C5 GEMM launch same box, bit-identical).
 __device__ __forceinline__ float4 gemm_ld_y(const float *p) {
-    if (GEMM_Y_NT) {
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
-    }
-    return *reinterpret_cast<const float4 *>(p);
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
 }
 template <int MT>
 constexpr int gbm() { return 64 * MT; }
-// Issue priority of a wave's MFMA loop (0: flat, for the A/B).  Two workgroups share a CU, so each SIMD
+// Issue priority of a wave's MFMA loop.  Two workgroups share a CU, so each SIMD
 // runs one wave of each; at equal priority the older wave wins the issue arbitration, and a wave in its
 // staging phase (LDS stores, barriers, next loads) held the MFMA pipe of the other one back.  The MFMA
 // loop at 1 over a staging phase at 0: 18.88 -> 18.24 ms per C5 GEMM launch (0.833 -> 0.862 of the f32
 // MFMA peak) same box, bit-identical; 2 and 3 measure the same (profiles/r05_prio_ab.txt).  Without the
 // staging phase at all (barriers and LDS stores dropped, garbage results) the loop runs at 0.96.
-#ifndef GEMM_PRIO
-#define GEMM_PRIO 1
-#endif
 
 template <bool NT, int MT>
 __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void gemm_f32_mfma(GemmF32 g) {  // (MT 4: 2 waves per SIMD)
@@ -108,7 +100,7 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void gemm_f32_mfma(GemmF32 g)
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
     if (nk > 0) load(kb);
     for (int kt = 0; kt < nk; ++kt) {
-        if (GEMM_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         __syncthreads();
 #pragma unroll
         for (int p = 0; p < XL; ++p) {
@@ -131,7 +123,7 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void gemm_f32_mfma(GemmF32 g)
         }
         __syncthreads();
         if (kt + 1 < nk) load(kb + (kt + 1) * GBK);  // next tile in flight during the MFMAs
-        if (GEMM_PRIO) __builtin_amdgcn_s_setprio(GEMM_PRIO);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int kk = 0; kk < GBK / 2; ++kk) {
             const int kx = 2 * kk + (lane >> 5);
@@ -192,31 +184,23 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void gemm_f32_mfma(GemmF32 g)
 // Needs tiles without ragged K (the K chunk a multiple of 16) and, for NN, N a multiple of 128; rows past M
 // or past yrows read a clamped row (their products land in unstored outputs, or meet z's zero padding).
 constexpr int GBK2 = 16;
-// the LDS-DMA kernel where its tiles are whole (1), or the register-staged kernel everywhere (0) (A/B): C5 GEMM
-// 0.864 -> 0.868 / 0.871 of the f32 MFMA peak same box, the C5 and dense tests green
-// (profiles/r06_gemm_glds_ab.txt)
-#ifndef GEMM_GLDS
-#define GEMM_GLDS 1
-#endif
+// The LDS-DMA kernel runs where its tiles are whole, the register-staged kernel elsewhere: C5 GEMM
+// 0.864 -> 0.868 / 0.871 of the f32 MFMA peak same box against the register-staged kernel everywhere, the C5 and
+// dense tests green (profiles/r06_gemm_glds_ab.txt)
 template <int MT>
 constexpr int glds_buf_floats() { return 64 * MT * GBK2 + GBN * GBK2; }  // one buffer: the X and Y tiles
 typedef __attribute__((address_space(3))) void lds_void;
 // one 16-byte-per-lane DMA global -> LDS (buffer_load_dwordx4 ... lds): lane i's 16 bytes land at lds + 16 i
 // (a non-template device function: the builtin inside the kernel template kept the host pass from emitting its
 // launch stubs)
-template <int AUX>
+// The design matrix's DMAs keep the default cache policy, unlike gemm_ld_y's non-temporal loads.  Same box:
+// default 0.873 / 0.872 of the f32 MFMA peak, non-temporal 0.866 / 0.865 (the register-staged kernel 0.866 /
+// 0.865); fabric bytes per NT launch 37.5 GB (default) / 41.0 GB (nt): the batch operand is re-read past L2 either
+// way, and the GEMM is MFMA-bound (A once is 19.3 GB, 2.4 ms of an 18 ms launch at 8 TB/s)
+// (profiles/r06_gemm_glds_ab.txt)
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, float *lds, int vo, int so) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void *)lds, 16, vo, so, 0, AUX);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void *)lds, 16, vo, so, 0, 0);
 }
-// the design matrix's DMAs non-temporal (aux 2: nt), as gemm_ld_y's loads, so the streamed A leaves the XCD's L2
-// before the batch operand every N tile re-reads (1), or default policy (0) (A/B).  Same box: default 0.873 / 0.872
-// of the f32 MFMA peak, nt 0.866 / 0.865 (the register-staged kernel 0.866 / 0.865); fabric bytes per NT launch
-// 37.5 GB (default) / 41.0 GB (nt): the batch operand is re-read past L2 either way, and the GEMM is MFMA-bound
-// (A once is 19.3 GB, 2.4 ms of an 18 ms launch at 8 TB/s) (profiles/r06_gemm_glds_ab.txt)
-#ifndef GEMM_GLDS_YNT
-#define GEMM_GLDS_YNT 0
-#endif
-constexpr int GLDS_YAUX = GEMM_GLDS_YNT ? 2 : 0;
 template <bool NT, int MT>
 __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void gemm_f32_glds(GemmF32 g) {
     constexpr int BM = gbm<MT>(), BUF = glds_buf_floats<MT>();
@@ -259,18 +243,18 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void gemm_f32_glds(GemmF32 g)
         // X: BM rows x 4 slots = BM / 16 wave-instructions of 16 rows
 #pragma unroll
         for (int i = 0; i < BM / 64; ++i)
-            dma16<0>(rx, bx + 256 * (i * 4 + wid), ox[i], 4 * k0);
+            dma16(rx, bx + 256 * (i * 4 + wid), ox[i], 4 * k0);
         if (NT) {  // 128 n-rows x 4 slots
 #pragma unroll
             for (int i = 0; i < 2; ++i)
-                dma16<GLDS_YAUX>(ry, by + 256 * (i * 4 + wid), oy[i], 4 * k0);
+                dma16(ry, by + 256 * (i * 4 + wid), oy[i], 4 * k0);
         } else {  // 16 k-rows x 128 n, two k-rows per wave-instruction (A is 19 GB at C5: a resource per tile)
             const int nrk = __builtin_amdgcn_readfirstlane(4 * ldy * max(0, min(GBK2, g.yrows - k0)));
             const __amdgpu_buffer_rsrc_t rk =
                 __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.Y + (long)k0 * ldy + n0), 0, nrk, 0x00020000);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
-                dma16<GLDS_YAUX>(rk, by + 256 * (i * 4 + wid), oy[i], 0);
+                dma16(rk, by + 256 * (i * 4 + wid), oy[i], 0);
         }
     };
     f32x16 acc[MT][2];
@@ -337,14 +321,14 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void gemm_f32_glds(GemmF32 g)
     for (int kt = 0; kt < nk; ++kt) {
         // tile kt landed (the barrier's fence waits for this wave's DMAs), and every wave has read its fragments
         // of tile kt - 1, so the other buffer is free
-        if (GEMM_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         __syncthreads();
         // the whole tile's fragments first, THEN the next tile's DMA: with a DMA in flight the compiler waits
         // vmcnt(0) before any LDS read of the same object
         Frag f;
         read_frag(lds + (kt & 1) * BUF, f);
         if (kt + 1 < nk) stage((kt + 1) & 1, kb + (kt + 1) * GBK2);
-        if (GEMM_PRIO) __builtin_amdgcn_s_setprio(GEMM_PRIO);
+        __builtin_amdgcn_s_setprio(1);
         mma(f, 0);
         mma(f, 1);
     }
@@ -375,11 +359,11 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void gemm_f32_glds(GemmF32 g)
         }
 }
 
-// the LDS-DMA kernel (1) or the register-staged one (0) (A/B); the DMA kernel only where its tiles are whole
+// the LDS-DMA kernel only where its tiles are whole, the register-staged one elsewhere
 static bool glds_ok(const GemmF32 &g, bool nt) {
     // whole K tiles, 16-byte aligned rows (aligned bases, row strides of 4 floats), whole NN column tiles,
     // 32-bit per-block offsets
-    return GEMM_GLDS && g.K % GBK2 == 0 && g.kchunk % GBK2 == 0 && g.ldx % 4 == 0 && g.ldy % 4 == 0 &&
+    return g.K % GBK2 == 0 && g.kchunk % GBK2 == 0 && g.ldx % 4 == 0 && g.ldy % 4 == 0 &&
            ((uintptr_t)g.X % 16 == 0) && ((uintptr_t)g.Y % 16 == 0) &&
            (nt || g.N % GBN == 0) && g.M > 0 && g.yrows > 0 && 4.0 * g.ldx * gbm<4>() < 2147483647.0 &&
            4.0 * g.ldy * GBN < 2147483647.0;
