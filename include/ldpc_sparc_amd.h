@@ -379,9 +379,13 @@ typedef struct sg_camp_plan sg_camp_plan;
 /* Design of a complex SPARC with sub-sampled FFT operator (sparc.py:593-646,
  * 703-880 with csparc=True): W, L, M, n and the transforms as sg_amp_plan_create;
  * order0[t][Mr] / order1[t][Mc] index the bins of a w-point FFT,
- * w = 2^ceil(log2(max(Mr+2, Mc+2))), 16 <= w <= 2^16 (SG_ERR_UNSUPPORTED
+ * w = 2^ceil(log2(max(Mr+2, Mc+2))), 16 <= w <= 2^20 (SG_ERR_UNSUPPORTED
  * otherwise).  Double precision only.  Complex arrays cross this ABI as
- * interleaved double[2] (re, im). */
+ * interleaved double[2] (re, im).  The workspace holds two buffers of
+ * 16 nT w bytes per codeword (32 MB per transform at w = 2^20).
+ * sg_camp_plan_info: P and Q are the two factors of the transform's
+ * four-step split, w = P Q: P = 2^floor(log2 w / 2) up to w = 2^16, P = 256
+ * above. */
 int sg_camp_plan_create(int ndim, const double *W, int Lr, int Lc, int L, int M, int n,
                         const uint32_t *order0, const uint32_t *order1, sg_camp_plan **out);
 int sg_camp_plan_destroy(sg_camp_plan *p);

@@ -14,6 +14,13 @@
 //   pass A  (per tile of CT columns m2): scatter the input into h[m1][m2],
 //           P-point FFTs over m1, twiddle w_w^{m2 k1}, store T[k1][m2]
 //   pass B  (per tile of RT rows k1): Q-point FFTs over m2, store X[k1][k2]
+// 16 <= w <= 2^16: P = 2^floor(log2 w / 2), both passes 2048 values in at most
+// 256 threads.  2^17 <= w <= 2^20: P = 256 and Q = w / 256 = 512 ... 4096, so
+// pass A keeps its shape and its 8-wide runs, and pass B (cfft_passB_long)
+// takes tiles of 4096 values -- rows are contiguous in buf0, so a long row
+// costs nothing in coalescing -- in 512 threads and 64 KB of LDS.  The stage
+// twiddles come from the Q-entry host table, the inter-pass ones from the
+// w-entry host table (16 MB at 2^20); nothing uses device sincos.
 // The needed outputs are single bins, read where they are used (the residual
 // of the control kernel, the s update of eta) from X at (k mod P) Q + k / P.
 //   eta     (one wavefront per section): s = beta + tau u, the K-PSK MMSE
@@ -87,7 +94,7 @@ __global__ __launch_bounds__(256) void cfft_passA(CampTables tb, CampBufs bf) {
 
 // ------------------------------------------------------------------ pass B
 template <bool INV>
-__global__ __launch_bounds__(256) void cfft_passB(CampTables tb, CampBufs bf) {
+__device__ __forceinline__ void passB_tile(const CampTables &tb, const CampBufs &bf) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cxd *d = reinterpret_cast<cxd *>(smem_raw);
     const int cw = blockIdx.z, t = blockIdx.y;
@@ -99,6 +106,16 @@ __global__ __launch_bounds__(256) void cfft_passB(CampTables tb, CampBufs bf) {
     __syncthreads();
     lds_fft<double, INV, CAMP_EPT, false>(d, tb.log2Q, tb.RT, 1, tb.Q, tb.twQ, tid, nthr);
     for (int idx = tid; idx < total; idx += nthr) bf.buf1[off + idx] = d[idx];
+}
+template <bool INV>
+__global__ __launch_bounds__(256) void cfft_passB(CampTables tb, CampBufs bf) {
+    passB_tile<INV>(tb, bf);
+}
+// Long rows (w >= 2^17: P = 256, Q = 512 ... 4096): tiles of 4096 values, one
+// row of Q = 4096 or several shorter ones, in 512 threads and 64 KB of LDS.
+template <bool INV>
+__global__ __launch_bounds__(512) void cfft_passB_long(CampTables tb, CampBufs bf) {
+    passB_tile<INV>(tb, bf);
 }
 
 // (A beta)_i of row block r summed over the row's transforms in table order
@@ -441,13 +458,39 @@ __global__ __launch_bounds__(256) void psk_map_kernel(const cxd *__restrict__ sv
 }  // namespace
 
 // ------------------------------------------------------------------ launchers
-int camp_launch_fft(const CampTables &tb, const CampBufs &bf, bool inverse, hipStream_t s) {
-    if (bf.B <= 0) return SG_OK;
+// Pass B runs in at most 256 threads (w <= 2^16), or in the long-row shape:
+// tiles of exactly CAMP_LONG_TILE values in 512 threads, P = 256.
+static bool camp_long_b(const CampTables &tb) {
+    return tb.RT * tb.Q == CAMP_LONG_TILE && tb.P == 256 && tb.Q >= 512;
+}
+static int camp_check_geometry(const CampTables &tb) {
     const int totA = tb.P * tb.CT, totB = tb.RT * tb.Q;
-    if (totA % CAMP_EPT || totB % CAMP_EPT || totA / CAMP_EPT > 256 || totB / CAMP_EPT > 256 || tb.Q % tb.CT ||
-        tb.P % tb.RT)
+    if (tb.P <= 0 || tb.Q <= 0 || tb.CT <= 0 || tb.RT <= 0 || (long long)tb.P * tb.Q != tb.w ||
+        tb.P != (1 << tb.log2P) || tb.Q != (1 << tb.log2Q) || totA % CAMP_EPT || totB % CAMP_EPT ||
+        totA / CAMP_EPT > 256 || (!camp_long_b(tb) && totB / CAMP_EPT > 256) || tb.Q % tb.CT || tb.P % tb.RT)
         return fail(SG_ERR_UNSUPPORTED, "complex FFT geometry P=%d Q=%d CT=%d RT=%d unsupported", tb.P, tb.Q, tb.CT,
                     tb.RT);
+    return SG_OK;
+}
+
+// Once per plan, on the plan's device: the long-row pass B takes 64 KB of
+// dynamic LDS, so its kernels' limit is raised here and not between launches.
+int camp_prepare_fft(const CampTables &tb) {
+    SG_TRY(camp_check_geometry(tb));
+    if (!camp_long_b(tb)) return SG_OK;
+    const int lds = (int)(sizeof(cxd) * CAMP_LONG_TILE);
+    SG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&cfft_passB_long<false>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    SG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&cfft_passB_long<true>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    return SG_OK;
+}
+
+int camp_launch_fft(const CampTables &tb, const CampBufs &bf, bool inverse, hipStream_t s) {
+    if (bf.B <= 0) return SG_OK;
+    SG_TRY(camp_check_geometry(tb));
+    const int totA = tb.P * tb.CT, totB = tb.RT * tb.Q;
+    const bool longB = camp_long_b(tb);
     const dim3 gA(tb.Q / tb.CT, tb.nT, bf.B), gB(tb.P / tb.RT, tb.nT, bf.B);
     const size_t ldsA = sizeof(cxd) * totA, ldsB = sizeof(cxd) * totB;
     {
@@ -458,7 +501,10 @@ int camp_launch_fft(const CampTables &tb, const CampBufs &bf, bool inverse, hipS
     SG_HIP(hipGetLastError());
     {
         ProfScope ps(inverse ? SG_PH_AZ_B : SG_PH_AB_B, s);
-        if (inverse) hipLaunchKernelGGL(cfft_passB<true>, gB, dim3(totB / CAMP_EPT), ldsB, s, tb, bf);
+        if (longB) {
+            if (inverse) hipLaunchKernelGGL(cfft_passB_long<true>, gB, dim3(totB / CAMP_EPT), ldsB, s, tb, bf);
+            else hipLaunchKernelGGL(cfft_passB_long<false>, gB, dim3(totB / CAMP_EPT), ldsB, s, tb, bf);
+        } else if (inverse) hipLaunchKernelGGL(cfft_passB<true>, gB, dim3(totB / CAMP_EPT), ldsB, s, tb, bf);
         else hipLaunchKernelGGL(cfft_passB<false>, gB, dim3(totB / CAMP_EPT), ldsB, s, tb, bf);
     }
     SG_HIP(hipGetLastError());

@@ -11,13 +11,20 @@ typedef cx<double> cxd;
 
 constexpr int CAMP_MAX_K = 64;     // largest PSK constellation
 constexpr int CAMP_EPT = 8;        // FFT elements per thread of every pass
-constexpr int CAMP_MIN_LOG2W = 4;  // w = 16 ... 2^16
-constexpr int CAMP_MAX_LOG2W = 16;
+constexpr int CAMP_MIN_LOG2W = 4;  // w = 16 ... 2^20
+constexpr int CAMP_MAX_LOG2W = 20;
+constexpr int CAMP_SQUARE_MAX_LOG2W = 16;  // up to here w = P Q with P = 2^floor(lg / 2); above, P = 256
+constexpr int CAMP_LONG_TILE = 4096;       // values per pass-B workgroup of the long-row shape (512 threads, 64 KB)
 
 // Design tables of one complex design, device pointers.  A "transform" is one
 // nonzero block (r, c) of the base matrix W: a w-point complex FFT, w = P Q,
 // with its own orders.  Bin k = k1 + P k2 of a transform's output sits at
-// position k1 Q + k2 of the pass-B layout.
+// position k1 Q + k2 of the pass-B layout.  Up to w = 2^16 the split is the
+// square one, P = 2^floor(log2 w / 2), and both passes run 2048 values in at
+// most 256 threads.  For w = 2^17 ... 2^20 the split is asymmetric: P = 256,
+// so pass A keeps its shape (CT = 8 columns), and Q = w / 256 = 512 ... 4096;
+// pass B then runs tiles of CAMP_LONG_TILE values (RT = 4096 / Q whole rows,
+// contiguous in buf0) in 512 threads.
 struct CampTables {
     int nT, w, P, Q, log2P, log2Q;
     int CT, RT;  // pass A: columns m2 per workgroup; pass B: rows k1 per workgroup
@@ -53,6 +60,7 @@ struct CampBufs {
     const int32_t *true_idx, *true_sym;  // [B][L] or null
 };
 
+int camp_prepare_fft(const CampTables &tb);  // once per plan: geometry check, LDS limit of the long-row pass B
 int camp_launch_fft(const CampTables &tb, const CampBufs &bf, bool inverse, hipStream_t s);  // beta (or z/phi) -> buf1
 int camp_launch_eta(const CampTables &tb, const CampBufs &bf, hipStream_t s);
 int camp_launch_control(const CampTables &tb, const CampBufs &bf, const AmpScalars &sc, const AmpParams &pr, int phase,

@@ -176,10 +176,12 @@ int sg_camp_plan_create(int ndim, const double *W, int Lr_in, int Lc_in, int L, 
     p->ndim = ndim; p->L = L; p->M = M; p->LM = (int)LM; p->n = n; p->Lr = Lr; p->Lc = Lc; p->Mr = Mr; p->Mc = Mc;
     const int w = 1 << lg;
     p->w = w;
-    p->log2P = lg / 2; p->log2Q = lg - p->log2P;
+    // square split up to 2^16; above, P stays 256 and pass B takes long rows (amp_cfft.hpp)
+    p->log2P = lg <= CAMP_SQUARE_MAX_LOG2W ? lg / 2 : 8;
+    p->log2Q = lg - p->log2P;
     p->P = 1 << p->log2P; p->Q = 1 << p->log2Q;
     p->CT = std::min(8, p->Q);
-    p->RT = std::min(8, p->P);
+    p->RT = lg <= CAMP_SQUARE_MAX_LOG2W ? std::min(8, p->P) : CAMP_LONG_TILE / p->Q;
     std::vector<double> Wv(W, W + (ndim == 0 ? 1 : (size_t)Lr * Lc));
     // transforms = nonzero blocks in row-major order (sparc.py:758-771)
     std::vector<int32_t> t_row, t_col;
@@ -233,6 +235,7 @@ int sg_camp_plan_create(int ndim, const double *W, int Lr_in, int Lc_in, int L, 
     SG_TRY(upload(q, &q->twP, twiddles(P))); SG_TRY(upload(q, &q->twQ, twiddles(Q)));
     SG_TRY(upload(q, &q->twW, twiddles(w)));
     SG_TRY(upload(q, &q->constel, std::vector<cxd>(CAMP_MAX_K, cxd{1.0, 0.0})));
+    SG_TRY(camp_prepare_fft(tables(q)));
     *out = p.release();
     return SG_OK;
 }
