@@ -31,6 +31,7 @@ extern "C" {
 enum sg_status {
     SG_OK = 0,
     SG_ERR_INVALID = -2,   /* bad argument (shape, degree, enum) */
+    SG_ERR_BAD_ARG = SG_ERR_INVALID, /* the same code under its other name */
     SG_ERR_NO_DEVICE = -3, /* no usable GPU */
     SG_ERR_HIP = -4,       /* HIP runtime failure */
     SG_ERR_NOMEM = -5,     /* allocation failure (the reference returns -1 here, c_ldpc.c:41) */
@@ -342,6 +343,26 @@ int sg_amp_decode_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *
                          double awgn_var, int t_max, double rtol, int phi_method,
                          int32_t *d_map_idx, int32_t *d_t_final, double *d_nmse, double *d_psi,
                          void *stream);
+/* Soft output of the last decode through this plan (sg_amp_decode_device or
+ * sg_amp_decode), in the plan precision: for sections [l0, l0 + nl) of each of
+ * the B codewords, P(bit = 0) of the log2 M section bits, MSB first, from the
+ * final beta = softmax(s / tau) (beta_estimate_to_bp_probs,
+ * sparc_new.py:1118-1138), clipped to [1e-15, 1 - 1e-15] and written as
+ * log p - log(1 - p) (ldpc_bp, :1167-1169) to d_llr[b * llr_ld + (l - l0) * log2 M + i];
+ * probs_only: the unclipped probabilities themselves.  Enqueued on the
+ * stream; reads the state the decode left in the plan (of the sub-plan that
+ * ran, a codeword that stopped early with the tau of its last iteration) and
+ * allocates nothing.  SG_ERR_BAD_ARG: no decode yet (every decode call resets
+ * the state; sg_amp_apply*, sg_amp_encode_device overwrite it and clear it
+ * too), B different from the decode's batch, a section range outside [0, L],
+ * llr_ld < nl log2 M, M < 2 or not a power of two.  SG_ERR_UNSUPPORTED: plans
+ * of the single-precision block engines (amp_block.hip, amp_block2.hip;
+ * spatially coupled designs give soft output in double precision), M > 2048. */
+int sg_amp_llr_device(sg_amp_plan *p, int B, int l0, int nl, int llr_ld, int probs_only, void *d_llr,
+                      void *stream);
+/* Host variant: out [B][nl * log2 M] as double, blocking.  A decode enqueued on a
+ * caller's stream must have completed. */
+int sg_amp_llr(sg_amp_plan *p, int B, int l0, int nl, int probs_only, double *out);
 /* Design operators (the Ab / Az closures of sparc_transforms, sparc.py:786-875):
  * transpose 0: in[B][L*M] -> out[B][n];  transpose 1: in[B][n] -> out[B][L*M]. */
 int sg_amp_apply(sg_amp_plan *p, int transpose, const double *in, int B, double *out);

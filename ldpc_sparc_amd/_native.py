@@ -13,6 +13,9 @@ LIB_PATH = os.environ.get("LDPC_SPARC_AMD_LIB", os.path.join(_HERE, "_lib", "lib
 
 SG_SUMPROD, SG_SUMPROD2, SG_MINSUM = 0, 1, 2
 SG_F64, SG_F32 = 0, 1
+# enum sg_status (SG_ERR_BAD_ARG is the header's other name of SG_ERR_INVALID)
+SG_OK, SG_ERR_INVALID, SG_ERR_NO_DEVICE, SG_ERR_HIP, SG_ERR_NOMEM, SG_ERR_UNSUPPORTED, SG_ERR_COMM = 0, -2, -3, -4, -5, -6, -7
+SG_ERR_BAD_ARG = SG_ERR_INVALID
 DECTYPES = {"sumprod": SG_SUMPROD, "sumprod2": SG_SUMPROD2, "minsum": SG_MINSUM}
 
 _lib = None
@@ -79,6 +82,8 @@ SIGNATURES = [
                                  vp, vp, vp, vp]),
     ("sg_amp_decode_device", ct.c_int, [vp, vp, ct.c_int, vp, ct.c_double, ct.c_int, ct.c_double,
                                         ct.c_int, vp, vp, vp, vp, vp]),
+    ("sg_amp_llr_device", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp, vp]),
+    ("sg_amp_llr", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp]),
     ("sg_amp_apply", ct.c_int, [vp, ct.c_int, vp, ct.c_int, vp]),
     ("sg_amp_apply_device", ct.c_int, [vp, ct.c_int, vp, ct.c_int, vp, vp]),
     ("sg_amp_count_errors_device", ct.c_int, [vp, vp, vp, ct.c_int, ct.c_int, ct.c_int, vp, vp]),

@@ -295,6 +295,11 @@ template <typename T>
 int reg_launch_map(const RegTables<T> &tb, const RegBufs<T> &bf, hipStream_t s);
 template <typename T>
 int reg_launch_ab_finish(const RegTables<T> &tb, const RegBufs<T> &bf, hipStream_t s);
+// bit LLRs (or bit-0 probabilities) of sections [l0, l0 + nl) from a finished decode's s (class order) and tau
+// (amp_llr.hip); llr row b starts at b * llr_ld
+template <typename T>
+int reg_launch_llr(const RegTables<T> &tb, const T *s, const double *tau, int B, int l0, int nl, int llr_ld,
+                   int probs_only, T *llr, hipStream_t st);
 size_t reg_stage1_lds(int img, int P, int Lblk, size_t real_bytes);
 // stage-1 elements per thread: f32 at P >= 8192 uses 16 (P = 8192 -> 512-thread
 // workgroups, two per CU); otherwise P/1024 threads' worth, at least 8

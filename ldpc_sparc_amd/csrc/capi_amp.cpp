@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "amp.hpp"
+#include "dense.hpp"
 
 using cd = std::complex<double>;
 
@@ -21,6 +22,9 @@ struct sg_amp_plan {
     // at which the per-codeword engine handed over to the staged one (-1: none)
     sg_amp_plan *last_ran = nullptr;
     int last_engine = -1, last_handover = -1;
+    // batch size of the last decode through this handle whose final state (s / beta, tau) the sub-plan
+    // last_ran still holds (sg_amp_llr_device); 0: none
+    int last_B = 0;
     int device = 0;
     int ndim = 0, L = 0, M = 0, LM = 0, n = 0, Lr = 1, Lc = 1, Mr = 0, Mc = 0, nT = 0;
     int w = 0, N2 = 0, P = 0, Q = 0, log2P = 0, log2Q = 0, npairs = 0;
@@ -1859,6 +1863,7 @@ static void reset_last(sg_amp_plan *p) {
         q->last_ran = nullptr;
         q->last_engine = -1;
         q->last_handover = -1;
+        q->last_B = 0;
     }
 }
 
@@ -1874,15 +1879,18 @@ int sg_amp_decode_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *
     SG_CHECK_ARG(B >= 0, "negative batch");
     if (B == 0) return SG_OK;
     SG_CHECK_ARG(d_y, "d_y is NULL");
+    sg_amp_plan *const handle = p;
     p = p->last_ran = sg::decode_plan(p, B);
     SG_TRY(ensure_device());
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = pick_stream(stream);
-    if (p->precision == SG_F64)
-        return decode_impl<double>(p, d_y, B, d_true_idx, awgn_var, t_max, rtol, phi_method, d_map_idx, d_t_final,
-                                   d_nmse, d_psi, s);
-    return decode_impl<float>(p, d_y, B, d_true_idx, awgn_var, t_max, rtol, phi_method, d_map_idx, d_t_final, d_nmse,
-                              d_psi, s);
+    SG_TRY(p->precision == SG_F64
+               ? decode_impl<double>(p, d_y, B, d_true_idx, awgn_var, t_max, rtol, phi_method, d_map_idx, d_t_final,
+                                     d_nmse, d_psi, s)
+               : decode_impl<float>(p, d_y, B, d_true_idx, awgn_var, t_max, rtol, phi_method, d_map_idx, d_t_final,
+                                    d_nmse, d_psi, s));
+    handle->last_B = B;
+    return SG_OK;
 }
 
 int sg_amp_decode(sg_amp_plan *p, const double *y, int B, const int32_t *true_idx, double awgn_var, int t_max,
@@ -1893,6 +1901,7 @@ int sg_amp_decode(sg_amp_plan *p, const double *y, int B, const int32_t *true_id
     if (B == 0) return SG_OK;
     SG_CHECK_ARG(y && map_idx && t_final && nmse && psi, "null host buffer");
     SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
+    sg_amp_plan *const handle = p;
     p = p->last_ran = sg::decode_plan(p, B);
     SG_TRY(ensure_device());
     SG_HIP(hipSetDevice(p->device));
@@ -1925,6 +1934,7 @@ int sg_amp_decode(sg_amp_plan *p, const double *y, int B, const int32_t *true_id
     SG_HIP(hipMemcpyAsync(nmse, p->ws_nmse, sizeof(double) * B * t_max * p->Lc, hipMemcpyDeviceToHost, s));
     SG_HIP(hipMemcpyAsync(psi, p->ws_psi, sizeof(double) * B * p->Lc, hipMemcpyDeviceToHost, s));
     SG_HIP(hipStreamSynchronize(s));
+    handle->last_B = B;
     return SG_OK;
 }
 
@@ -1932,6 +1942,7 @@ int sg_amp_apply(sg_amp_plan *p, int transpose, const double *in, int B, double 
     SG_CHECK_ARG(p && in && out, "null argument");
     SG_CHECK_ARG(B >= 0, "negative batch");
     if (B == 0) return SG_OK;
+    p->last_B = 0;  // (the operators run in the workspace that holds a decode's final state)
     SG_TRY(ensure_device());
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = lib_stream();
@@ -1951,6 +1962,7 @@ int sg_amp_apply(sg_amp_plan *p, int transpose, const double *in, int B, double 
 int sg_amp_encode_device(sg_amp_plan *p, const int32_t *d_idx, int B, void *d_x, void *stream) {
     SG_CHECK_ARG(p && d_idx && d_x, "null argument");
     if (B <= 0) return SG_OK;
+    p->last_B = 0;
     SG_TRY(ensure_device());
     hipStream_t s = pick_stream(stream);
     return p->precision == SG_F64 ? encode_impl<double>(p, d_idx, B, (double *)d_x, s)
@@ -2003,10 +2015,80 @@ int sg_amp_stage_raw(sg_amp_plan *p, int kernel, uint64_t *out, size_t *items) {
 int sg_amp_apply_device(sg_amp_plan *p, int transpose, const void *d_in, int B, void *d_out, void *stream) {
     SG_CHECK_ARG(p && d_in && d_out, "null argument");
     if (B <= 0) return SG_OK;
+    p->last_B = 0;
     SG_TRY(ensure_device());
     hipStream_t s = pick_stream(stream);
     if (p->precision == SG_F64) return apply_impl<double>(p, transpose, d_in, 1, B, d_out, 0, s);
     return apply_impl<float>(p, transpose, d_in, 0, B, d_out, 0, s);
+}
+
+}  // extern "C"
+
+// Soft output of the last decode.  Final-state contract of the engines (DESIGN.md "Soft output of the DCT
+// engines"): every regular engine -- staged, per-codeword, split f32 / f64, with or without a hand-over -- leaves
+// s in class order in ws_s (reg_launch_map reads it there) and, per codeword, the tau of the iteration that wrote
+// that s in ws_tau: their kernels return at once for a stopped codeword, so later iterations of the others move
+// neither (ws_tau_prev is the iteration before).  The general engine leaves beta in natural order in ws_beta.
+static int llr_checks(sg_amp_plan *p, int B, int l0, int nl, int llr_ld, int *logM_out) {
+    if ((p->block || p->block2) && p->precision == SG_F32)
+        return fail(SG_ERR_UNSUPPORTED, "no soft output from the single-precision block engine (%s): decode the "
+                    "spatially coupled design in double precision", p->block2 ? "amp_block2.hip" : "amp_block.hip");
+    SG_CHECK_ARG(p->M >= 2 && (p->M & (p->M - 1)) == 0, "section size M = %d must be a power of two >= 2", p->M);
+    SG_CHECK_ARG(p->last_ran && p->last_B > 0, "no decode through this plan yet (or its state was overwritten)");
+    SG_CHECK_ARG(B == p->last_B, "B = %d, but the last decode held %d codewords", B, p->last_B);
+    SG_CHECK_ARG(l0 >= 0 && nl >= 0 && l0 <= p->L && nl <= p->L - l0, "sections [%d, %d + %d) outside [0, %d]", l0, l0,
+                 nl, p->L);
+    const int logM = ilog2(p->M);
+    SG_CHECK_ARG((long long)llr_ld >= (long long)nl * logM, "llr_ld = %d < nl log2 M = %lld", llr_ld,
+                 (long long)nl * logM);
+    *logM_out = logM;
+    return SG_OK;
+}
+
+template <typename T>
+static int llr_impl(const sg_amp_plan *r, int B, int l0, int nl, int llr_ld, int probs_only, T *d_llr, hipStream_t s) {
+    if (r->regular)
+        return reg_launch_llr<T>(rtables<T>(r), (const T *)r->ws_s, r->ws_tau, B, l0, nl, llr_ld, probs_only, d_llr, s);
+    return glue_launch_llr<T>((const T *)r->ws_beta, B, r->L, r->M, l0, nl, 1.0, llr_ld, d_llr, probs_only, s);
+}
+
+extern "C" {
+
+int sg_amp_llr_device(sg_amp_plan *p, int B, int l0, int nl, int llr_ld, int probs_only, void *d_llr, void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p && d_llr, "null argument");
+    int logM = 0;
+    SG_TRY(llr_checks(p, B, l0, nl, llr_ld, &logM));
+    const sg_amp_plan *r = p->last_ran;
+    SG_HIP(hipSetDevice(r->device));
+    hipStream_t s = pick_stream(stream);
+    return r->precision == SG_F64 ? llr_impl<double>(r, B, l0, nl, llr_ld, probs_only, (double *)d_llr, s)
+                                  : llr_impl<float>(r, B, l0, nl, llr_ld, probs_only, (float *)d_llr, s);
+}
+
+int sg_amp_llr(sg_amp_plan *p, int B, int l0, int nl, int probs_only, double *out) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p && out, "null argument");
+    int logM = 0;
+    SG_TRY(llr_checks(p, B, l0, nl, INT32_MAX, &logM));
+    const size_t ld = (size_t)nl * logM, nv = (size_t)B * ld;
+    if (nv == 0) return SG_OK;
+    const sg_amp_plan *r = p->last_ran;
+    SG_HIP(hipSetDevice(r->device));
+    hipStream_t s = lib_stream();
+    // staging in the handle's own I/O buffer (not part of the decode state): doubles, then the plan's reals
+    SG_TRY(ensure_io(p, nv * 16));
+    double *dd = (double *)p->ws_io;
+    if (r->precision == SG_F64) {
+        SG_TRY(llr_impl<double>(r, B, l0, nl, (int)ld, probs_only, dd, s));
+    } else {
+        float *df = (float *)(dd + nv);
+        SG_TRY(llr_impl<float>(r, B, l0, nl, (int)ld, probs_only, df, s));
+        SG_TRY(amp_launch_uncast<float>(df, dd, nv, s));
+    }
+    SG_HIP(hipMemcpyAsync(out, dd, nv * sizeof(double), hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    return SG_OK;
 }
 
 int sg_amp_count_errors_device(const int32_t *d_map_idx, const int32_t *d_true_idx, const int32_t *d_t_final, int B,

@@ -474,10 +474,15 @@ class ConcatTrial:
         return tot
 
 
+def concat_checkpoint_tag(L, M, n, design="dense"):
+    """Checkpoint tag of a concat_ber_sweep: concat_L.. (dense), concat_dct_L.. (DCT design)."""
+    return f"concat_L{L}_M{M}_n{n}" if design == "dense" else f"concat_{design}_L{L}_M{M}_n{n}"
+
+
 def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, block=256, blocks_per_round=None,
                      rank=0, world=1, agg=None, design_seed=0, seed=0, t_max=25, bp_its=200, precision="f32",
                      ldpc=("802.11n", "1/2", 81), min_errors=None, checkpoint_dir=None, npz_file=None, rng="device",
-                     trial=None, max_rounds=None, on_point=None):
+                     trial=None, max_rounds=None, on_point=None, design="dense"):
     """BER / FER of concatenated SPARC + LDPC against Eb/N0 (the experiment of
     ldpc_sparc/performance_plots_general.py:100-138 for the plain concatenated
     decoder), `codewords` per point sharded over the ranks.  Eb/N0 to noise as
@@ -490,17 +495,25 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
     `trial(point, first_block, n_blocks, block)` (counters as ConcatTrial's)
     replaces the GPU pipeline (CPU rehearsals: tools/c5_sweep.py --rehearsal); `max_rounds`
     interrupts every point after that many rounds (run_point); `on_point(dict)`
-    is called with each point's result as soon as it is done."""
+    is called with each point's result as soon as it is done.  `design`:
+    "dense" is the reference's Gaussian matrix (pipeline.ConcatPipeline), "dct"
+    the sub-sampled DCT design drawn from `design_seed`, decoded by the public
+    AMP with early stopping (pipeline.DctConcatPipeline).  A DCT sweep keeps
+    its checkpoints under its own tag and parameters, so neither kind resumes
+    the other."""
     from .ldpc import code
+    if design not in ("dense", "dct"):
+        raise ValueError(f"design must be 'dense' or 'dct', not {design!r}")
     agg = agg or Aggregator()
     logM = int(np.log2(M))
     user_bits = L_unprotected * logM + mults * code(*ldpc).K
     r_overall = user_bits / n
     vars_ = [P / (2 * r_overall * 10 ** (e / 10)) for e in ebn0_db]
     if trial is None:
-        from .pipeline import ConcatPipeline
-        pipe = ConcatPipeline(L, M, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed,
-                              precision=precision, t_max=t_max, bp_its=bp_its)
+        from .pipeline import ConcatPipeline, DctConcatPipeline
+        make = DctConcatPipeline if design == "dct" else ConcatPipeline
+        pipe = make(L, M, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed, precision=precision,
+                    t_max=t_max, bp_its=bp_its)
         assert pipe.L_unp * pipe.logM + pipe.mults * pipe.c.K == user_bits
         trial = ConcatTrial(pipe, vars_, seed, rng)
     bpr = blocks_per_round or max(1, world)
@@ -515,9 +528,11 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
             # the round size is part of the experiment (without one the point
             # ends at `codewords`, a multiple of the block, at any round size)
             params["blocks_per_round"] = bpr
+        if design != "dense":  # (dense sweeps keep the parameters their checkpoints were written with)
+            params["design"] = design
         tot = run_point(trial, point, block=block, blocks_per_round=bpr, rank=rank, world=world, agg=agg,
                         min_errors=min_errors, max_units=codewords, checkpoint_dir=checkpoint_dir,
-                        tag=f"concat_L{L}_M{M}_n{n}", params=params, max_rounds=max_rounds)
+                        tag=concat_checkpoint_tag(L, M, n, design), params=params, max_rounds=max_rounds)
         out.append({"ebn0_db": float(e), "awgn_var": vars_[point], "codewords": int(tot[0]),
                     "ber": float(tot[1]) / (tot[0] * user_bits) if tot[0] else None,
                     "fer": float(tot[2]) / tot[0] if tot[0] else None,

@@ -51,6 +51,10 @@ class ConcatPipeline:
         self.d_cnt = _native.DeviceBuffer(5 * 8)
         self._cap = B
 
+    def _encode(self, B):
+        """x = A beta0 [B, n] on the device for the section indices in d_true."""
+        _native.check(_native.lib().sg_dense_encode_device(self.plan, self.d_true.ptr, B, self.d_x.ptr, None))
+
     def make_batch(self, B, awgn_var, rng):
         """Random user bits -> LDPC blocks -> section indices; x = A beta0 on
         the GPU; y = x + AWGN (host RNG).  Leaves y, the true indices and the
@@ -64,12 +68,11 @@ class ConcatPipeline:
         idx = (bits.astype(np.int64) @ (1 << np.arange(logM)[::-1])).astype(np.int32)
         self.d_true.upload(idx)
         self.d_info.upload(info.reshape(B, -1).astype(np.uint8))
-        lib = _native.lib()
-        _native.check(lib.sg_dense_encode_device(self.plan, self.d_true.ptr, B, self.d_x.ptr, None))
+        self._encode(B)
         x = self.d_x.download(np.empty((B, self.n), self.dt))
         y = (x + np.sqrt(awgn_var) * rng.standard_normal(x.shape)).astype(self.dt)
         self.d_y.upload(y)
-        self.B = B
+        self.B, self.awgn_var = B, float(awgn_var)
         return idx, info
 
     # distinct Philox keys of the parts of a device batch
@@ -96,10 +99,10 @@ class ConcatPipeline:
         c.encode_device(self.d_info.ptr, B * self.mults, self.d_cw.ptr)
         _native.check(lib.sg_bits_to_sections_strided_device(self.d_cw.ptr, self.mults * c.N, B, self.L - self.L_unp,
                                                              logM, off(self.d_true.ptr, 4 * self.L_unp), self.L, None))
-        _native.check(lib.sg_dense_encode_device(self.plan, self.d_true.ptr, B, self.d_x.ptr, None))
+        self._encode(B)
         _native.check(lib.sg_awgn_device(self.prec, seed, stream_id, self.d_x.ptr, B, self.n,
                                          float(np.sqrt(awgn_var)), self.d_y.ptr, None))
-        self.B = B
+        self.B, self.awgn_var = B, float(awgn_var)
 
     def decode(self):
         """One batch: returns nothing; counters accumulate in d_cnt."""
@@ -124,3 +127,70 @@ class ConcatPipeline:
     def counts(self):
         _native.synchronize()
         return self.d_cnt.download(np.zeros(5, np.int64))
+
+
+class DctConcatPipeline(ConcatPipeline):
+    """The same concatenated scheme on the sub-sampled DCT design (sparc.py
+    :703-880) instead of the dense Gaussian matrix: statistically the same
+    code, decoded by the DCT-design AMP engines.  Same methods, device buffers
+    and counter layout as ConcatPipeline, so montecarlo.ConcatTrial takes it
+    unchanged.
+
+    `op` is a sparc.DesignOperator over (L, M, n): flat, power-allocated, or
+    spatially coupled in double precision (the single-precision block engines
+    give no soft output).  By default it is the flat design W = P with the
+    orders sparc_transforms draws from `design_seed`.
+
+    decode() per batch, nothing returning to the host but the five counters:
+    sg_amp_decode_device (its map_idx gives the unprotected bits) ->
+    sg_amp_llr_device over the protected sections (the bit LLRs from the
+    engine's final s and tau) -> sg_ldpc_decode_device ->
+    sg_concat_count_errors_device.
+
+    The AMP here is the public decoder (sparc.py:883-999): known noise variance
+    or the residual estimate (`phi_method` = phi_est_method 1 / 2) and early
+    stopping at `rtol`, up to t_max - 1 iterations per codeword -- not the
+    dense pipeline's fixed t_max iterations with the empirical tau^2
+    (sparc_new.py:885-912).  Error rates of the two pipelines agree
+    statistically, not codeword by codeword."""
+
+    def __init__(self, L, M, n, P, L_unprotected, mults, ldpc=("802.11n", "1/2", 81), design_seed=0,
+                 precision="f32", t_max=25, rtol=1e-6, phi_method=1, bp_dectype="sumprod2", bp_its=200, op=None):
+        from . import sparc
+        self.L, self.M, self.n, self.P = int(L), int(M), int(n), float(P)
+        self.logM = int(np.log2(M))
+        self.L_unp, self.mults = int(L_unprotected), int(mults)
+        self.c = code(*ldpc)
+        assert (self.L - self.L_unp) * self.logM == self.mults * self.c.N, "protected sections must hold the blocks"
+        self.prec = {"f64": _native.SG_F64, "f32": _native.SG_F32}[precision]
+        self.dt = np.float64 if self.prec == _native.SG_F64 else np.float32
+        self.t_max, self.bp_dectype, self.bp_its = int(t_max), bp_dectype, int(bp_its)
+        self.rtol, self.phi_method = float(rtol), int(phi_method)
+        if op is None:
+            W = np.array(float(P))
+            o0, o1 = sparc.generate_ordering(W, self.n, self.L * self.M, design_seed)
+            op = sparc.DesignOperator(W, self.L, self.M, self.n, o0, o1)
+        if op.csparc or (op.L, op.M, op.n) != (self.L, self.M, self.n):
+            raise ValueError(f"op must be a real DesignOperator with L = {self.L}, M = {self.M}, n = {self.n}")
+        self.op = op
+        self.plan = op.plan(self.prec)
+        self.graph = self.c._device_graph()
+        self._cap = 0
+
+    def _encode(self, B):
+        _native.check(_native.lib().sg_amp_encode_device(self.plan, self.d_true.ptr, B, self.d_x.ptr, None))
+
+    def decode(self):
+        """One batch: returns nothing; counters accumulate in d_cnt."""
+        lib, c, B = _native.lib(), self.c, self.B
+        _native.check(lib.sg_amp_decode_device(self.plan, self.d_y.ptr, B, None, self.awgn_var, self.t_max,
+                                               self.rtol, self.phi_method, self.d_idx.ptr, None, None, None, None))
+        ld = self.mults * c.N
+        _native.check(lib.sg_amp_llr_device(self.plan, B, self.L_unp, self.L - self.L_unp, ld, 0, self.d_llr.ptr,
+                                            None))
+        _native.check(lib.sg_ldpc_decode_device(self.graph, _native.DECTYPES[self.bp_dectype], self.prec,
+                                                self.d_llr.ptr, B * self.mults, self.bp_its, 0.7, self.d_app.ptr,
+                                                self.d_it.ptr, None))
+        _native.check(lib.sg_concat_count_errors_device(self.prec, self.d_idx.ptr, self.d_true.ptr, B, self.L,
+                                                        self.L_unp, self.logM, self.d_app.ptr, self.d_info.ptr,
+                                                        self.mults, c.N, c.K, self.d_cnt.ptr, None))

@@ -670,6 +670,22 @@ def amp_decode_batch(Y, op, awgn_var, t_max, rtol=1e-6, phi_est_method=1, true_i
     return map_idx, t_final, nmse, psi
 
 
+def amp_llr(op, B, l0, nl, probs_only=False, precision=_native.SG_F64):
+    """Soft output of the last amp_decode_batch of B codewords through `op` at
+    this precision: for sections [l0, l0 + nl), the LLRs log p - log(1 - p) of
+    the section bits (MSB first), p = P(bit = 0) under the decoder's final
+    beta clipped to [1e-15, 1 - 1e-15] (beta_estimate_to_bp_probs and ldpc_bp's
+    clip, sparc_new.py:1118-1138, 1167-1169), or with probs_only the unclipped
+    p.  Returns float64 [B, nl * log2 M] (computed in the plan's precision)."""
+    if op.csparc:
+        raise NotImplementedError("soft output is implemented for real (DCT design) SPARCs only")
+    logM = int(np.log2(op.M))
+    out = np.empty((int(B), int(nl) * logM))
+    _native.check(_native.lib().sg_amp_llr(op.plan(precision), int(B), int(l0), int(nl), int(bool(probs_only)),
+                                           _native.ptr(out)))
+    return out
+
+
 def camp_decode_batch(Y, op, awgn_var, t_max, rtol=1e-6, phi_est_method=1, K=1, true_idx=None, true_sym=None):
     """Batched AMP on the GPU for complex codewords sharing one complex design.
 
