@@ -311,7 +311,10 @@ typedef struct sg_amp_plan sg_amp_plan;
  * double arithmetic; SG_F32 is the throughput path.  A plan eligible for the
  * per-codeword engine also holds a staged-engine plan at P = 16384, which
  * decodes batches too small for the per-codeword engine (sg_amp_plan_info
- * reports the per-codeword plan's P). */
+ * reports the per-codeword plan's P).  Section sizes: the regular engine
+ * (ndim 0 or 1) takes any power of two M; a design that runs the general
+ * engine (ndim 2 outside the block engines' geometries) with M > 2048 is
+ * SG_ERR_UNSUPPORTED here, with no plan returned, never at decode time. */
 int sg_amp_plan_create(int ndim, const double *W, int Lr, int Lc, int L, int M, int n,
                        const uint32_t *order0, const uint32_t *order1, int precision,
                        sg_amp_plan **out);

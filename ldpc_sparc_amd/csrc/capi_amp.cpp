@@ -1403,6 +1403,11 @@ static int build_plan(int ndim, const double *W, int Lr_in, int Lc_in, int L, in
                     M <= 2048 && Mr <= 1024 && !no_blk;
     p->block2 = (c4 && !single && M <= 2048 && Mr <= 512) || nb;
     p->b2_log2p = p->block2 ? (nb ? 14 : 13) : 0;
+    // the general engine's section kernel (amp_dct.hip eta_kernel) holds at most 32 entries per lane: a larger
+    // section is refused here, before anything is uploaded, never in the middle of a decode (amp_launch_eta
+    // keeps its own check as a guard).  The regular engine has no bound on M (DESIGN.md "Section sizes").
+    if (!p->regular && !p->block && !p->block2 && M > 2048)
+        return fail(SG_ERR_UNSUPPORTED, "section size M=%d > 2048 unsupported by the general engine", M);
     const int N = w, N2 = p->N2, P = p->P, Q = p->Q, np1 = p->npairs + 1;
     auto slot_of = [&](long long pos) -> long long {  // w-space slot of position pos
         return (pos % 2 == 0) ? pos / 2 : (long long)N - 1 - (pos - 1) / 2;
@@ -2049,7 +2054,7 @@ template <typename T>
 static int llr_impl(const sg_amp_plan *r, int B, int l0, int nl, int llr_ld, int probs_only, T *d_llr, hipStream_t s) {
     if (r->regular)
         return reg_launch_llr<T>(rtables<T>(r), (const T *)r->ws_s, r->ws_tau, B, l0, nl, llr_ld, probs_only, d_llr, s);
-    return glue_launch_llr<T>((const T *)r->ws_beta, B, r->L, r->M, l0, nl, 1.0, llr_ld, d_llr, probs_only, s);
+    return glue_launch_llr<T>((const T *)r->ws_beta, B, r->L, r->M, l0, nl, 1.0, llr_ld, d_llr, probs_only, 1, s);
 }
 
 extern "C" {

@@ -257,7 +257,7 @@ static int integ_impl(sg_dense_plan *p, sg_graph *g, int mode, int N, int K, con
         if (d_tau_hist)
             SG_HIP(hipMemcpy2DAsync(d_tau_hist + t, (size_t)t_max * 8, p->ws_tau2, 8, 8, B, hipMemcpyDeviceToDevice, s));
         SG_TRY(dense_launch_eta<T>(da, s));
-        SG_TRY(glue_launch_llr<T>(alpha_w, B, p->L, p->M, 0, p->L, 1.0 / snp, nbits, vk0, 1, s));  // P(bit = 0)
+        SG_TRY(glue_launch_llr<T>(alpha_w, B, p->L, p->M, 0, p->L, 1.0 / snp, nbits, vk0, 1, 0, s));  // P(bit = 0)
         SG_TRY(integ_launch_llr<T>(vk0, nb, llr, s));
         if (t == t_max - 1) {
             SG_TRY(sg_ldpc_decode_device(g, SG_SUMPROD2, prec, llr, B * nblk, its_final, 0.7, app, p->wi_it, s));
@@ -536,9 +536,9 @@ int sg_beta_to_llr_device(int precision, const void *d_beta, int B, int L, int M
     const double inv = 1.0 / sqrt_nPl;
     return precision == SG_F64
                ? glue_launch_llr<double>((const double *)d_beta, B, L, M, l0, nl, inv, llr_ld, (double *)d_llr,
-                                         probs_only, s)
+                                         probs_only, 0, s)
                : glue_launch_llr<float>((const float *)d_beta, B, L, M, l0, nl, inv, llr_ld, (float *)d_llr,
-                                        probs_only, s);
+                                        probs_only, 0, s);
 }
 
 int sg_concat_count_errors_device(int precision, const int32_t *d_map_idx, const int32_t *d_true_idx, int B, int L,

@@ -593,7 +593,8 @@ __global__ __launch_bounds__(256) void dense_map_kernel(const T *s, int B, int L
 // clipped to [1e-15, 1 - 1e-15], LLR = log p0 - log(1 - p0) (positive => 0).
 template <typename T>
 __global__ __launch_bounds__(256) void glue_llr_kernel(const T *beta, int B, int L, int M, int l0, int nl,
-                                                       double inv_snp, int llr_ld, T *llr, int probs_only) {
+                                                       double inv_snp, int llr_ld, T *llr, int probs_only,
+                                                       int round_p) {
     const int lane = threadIdx.x & 63;
     const int li = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int b = blockIdx.y;
@@ -609,7 +610,10 @@ __global__ __launch_bounds__(256) void glue_llr_kernel(const T *beta, int B, int
         for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
         if (lane == 0) {
             const double eps = 1e-15;
-            const double pc = fmin(fmax(p, eps), 1.0 - eps);  // ldpc_bp's clip (sparc_new.py:1167)
+            // round_p (the DCT engines' soft output): the LLR of the probability as probs_only returns it, as
+            // reg_llr_kernel (amp_llr.hip); the dense pipeline clips the double sum
+            const double pr = round_p ? (double)(T)p : p;
+            const double pc = fmin(fmax(pr, eps), 1.0 - eps);  // ldpc_bp's clip (sparc_new.py:1167)
             llr[(long)b * llr_ld + (long)li * logM + pos] = probs_only ? (T)p : (T)(log(pc) - log(1.0 - pc));
         }
     }
@@ -765,10 +769,10 @@ int dense_launch_map(const T *sv, int B, int L, int M, int32_t *idx, hipStream_t
 
 template <typename T>
 int glue_launch_llr(const T *beta, int B, int L, int M, int l0, int nl, double inv_snp, int llr_ld, T *llr,
-                    int probs_only, hipStream_t s) {
+                    int probs_only, int round_p, hipStream_t s) {
     if (B <= 0 || nl <= 0) return SG_OK;
     hipLaunchKernelGGL((glue_llr_kernel<T>), dim3((nl + 3) / 4, B), dim3(256), 0, s, beta, B, L, M, l0, nl, inv_snp,
-                       llr_ld, llr, probs_only);
+                       llr_ld, llr, probs_only, round_p);
     SG_HIP(hipGetLastError());
     return SG_OK;
 }
@@ -781,7 +785,7 @@ int glue_launch_llr(const T *beta, int B, int L, int M, int l0, int nl, double i
     template int dense_launch_eta<T>(const DenseBufs<T> &, hipStream_t);                                       \
     template int dense_launch_gen_A<T>(T *, int, int, uint64_t, hipStream_t);                                  \
     template int dense_launch_map<T>(const T *, int, int, int, int32_t *, hipStream_t);                        \
-    template int glue_launch_llr<T>(const T *, int, int, int, int, int, double, int, T *, int, hipStream_t);
+    template int glue_launch_llr<T>(const T *, int, int, int, int, int, double, int, T *, int, int, hipStream_t);
 SG_DENSE_INST(float)
 SG_DENSE_INST(double)
 

@@ -46,7 +46,7 @@ template <typename T>
 int dense_launch_map(const T *s, int B, int L, int M, int32_t *idx, hipStream_t st);
 template <typename T>
 int glue_launch_llr(const T *beta, int B, int L, int M, int l0, int nl, double inv_sqrt_nPl, int llr_ld, T *llr,
-                    int probs_only, hipStream_t s);
+                    int probs_only, int round_p, hipStream_t s);
 
 // integrated decoders (integrated.hip)
 template <typename T>
