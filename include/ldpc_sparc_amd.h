@@ -79,7 +79,10 @@ int sg_device_synchronize(void);
 enum sg_phase {
     SG_PH_AB_A = 0, SG_PH_AB_B = 1, SG_PH_AZ_A = 2, SG_PH_AZ_B = 3, SG_PH_ETA = 4,
     SG_PH_CONTROL = 5, SG_PH_BP = 6, SG_PH_DENSE = 7, SG_PH_AMP_CW = 8, SG_PH_CW2_AB = 9, SG_PH_CW2_AZ = 10,
-    SG_PH_CW2_CTRL = 11, SG_PH_COUNT = 12
+    SG_PH_CW2_CTRL = 11,
+    /* integrated decoders on the DCT design: BP output -> beta (probabilities, bp_to_beta, update, ||beta||^2)
+     * and the differentiated eta */
+    SG_PH_INT_GLUE = 12, SG_PH_INT_DETA = 13, SG_PH_COUNT = 14
 };
 int sg_profile_enable(int on);
 int sg_profile_collect(double *total_ms, int64_t *launches);
@@ -389,6 +392,27 @@ int sg_amp_apply_device(sg_amp_plan *p, int transpose, const void *d_in, int B, 
 int sg_amp_count_errors_device(const int32_t *d_map_idx, const int32_t *d_true_idx,
                                const int32_t *d_t_final, int B, int L, int logM, int64_t *d_counts,
                                void *stream);
+
+/* The four integrated AMP <-> BP decoders (enum sg_integrated_mode) on a sub-sampled DCT design plan
+ * (integrated_dct.hip): the mathematics of
+ * sg_integrated_decode with the design matrix replaced by the plan's operator, A beta -> Ab(beta) / snp and
+ * A^T z -> Az(z) / snp, snp = sqrt(n P / L), P the plan's scalar W (that matrix is
+ * A[i][j] = sqrt(2 / n) cos(pi (2 order1[j] + 1) order0[i] / (2 w))).  d_y in the plan precision; d_bits
+ * [B][(L log2 M / N) K]; d_tau2 [B][t_max] optional; d_app optional: the final BP output [B L log2 M / N][N]
+ * in the plan precision (for sg_concat_count_errors_device).  Intermediate and final BP run sumprod2.
+ * Every check precedes any launch or allocation: SG_ERR_UNSUPPORTED for a plan that is not flat (W of ndim 1
+ * or 2: the fork's decoders know one P_l and one tau^2) and for M not a power of two in [2, 2048] (the section
+ * kernel's width); SG_ERR_INVALID for L log2 M not a multiple of N, K outside (0, N], bad iteration counts;
+ * B <= 0 returns SG_OK with nothing done.  Works in the plan's workspace: clears the last-decode state (a
+ * following sg_amp_llr* answers SG_ERR_BAD_ARG, as after sg_amp_apply*) and leaves the plan fit for
+ * sg_amp_decode*.  The integrated buffers are allocated once per (plan, B) and freed with the plan; the loop
+ * itself enqueues on the stream without synchronising. */
+int sg_amp_integrated_decode_device(sg_amp_plan *p, sg_graph *g, int mode, int K, const void *d_y, int B,
+                                    int t_max, int bp_its, int bp_its_final, uint8_t *d_bits, void *d_app,
+                                    double *d_tau2, void *stream);
+/* Host variant: y [B][n], bits and tau2 (optional) as sg_integrated_decode; blocking. */
+int sg_amp_integrated_decode(sg_amp_plan *p, sg_graph *g, int mode, int K, const double *y, int B, int t_max,
+                             int bp_its, int bp_its_final, uint8_t *bits, double *tau2);
 
 /* Stand-alone section estimators, double precision on the GPU:
  * out[l*M+j] = scale * softmax_j(x[l*M : (l+1)*M])  (msg_vector_mmse_estimator,

@@ -103,6 +103,14 @@ struct sg_amp_plan {
     int b_ngs = 0;
     void *ws_gbuf = nullptr;  // [B][b_ngs] G slots (block engine)
     void *b_oc = nullptr, *b_gc = nullptr, *b_stw = nullptr;
+    // integrated AMP <-> BP decoders (integrated_dct.hip), grow-only per (plan, B): u = Az(z) / weighted alpha
+    // and gamma [B][LM]; xhat = Ab(beta) [B][n]; vk0, vk, LLRs, app [B][L log M]; BP iteration counts;
+    // per-section sums (differentiated eta, or beta^2 of the naive decoders) and their per-codeword sum
+    int cap_Bi = 0;
+    void *wi_alpha = nullptr, *wi_gamma = nullptr, *wi_x = nullptr, *wi_vk0 = nullptr, *wi_vk = nullptr,
+         *wi_llr = nullptr, *wi_app = nullptr;
+    int32_t *wi_it = nullptr;
+    double *wi_part = nullptr, *wi_ons = nullptr;
 };
 
 extern "C" int sg_amp_plan_destroy(sg_amp_plan *p);
@@ -188,6 +196,34 @@ static void inv_contrib(long long q, long long N, long long N2, double sc, F &&a
 
 static long long slot_of_pos(long long pos, long long N) {  // w-space slot of DCT position pos
     return (pos % 2 == 0) ? pos / 2 : N - 1 - (pos - 1) / 2;
+}
+
+static void integ_free_ws(sg_amp_plan *p) {
+    void **ws[] = {&p->wi_alpha, &p->wi_gamma, &p->wi_x, &p->wi_vk0, &p->wi_vk, &p->wi_llr, &p->wi_app,
+                   (void **)&p->wi_it, (void **)&p->wi_part, (void **)&p->wi_ons};
+    for (void **x : ws) {
+        if (*x) hipFree(*x);
+        *x = nullptr;
+    }
+    p->cap_Bi = 0;
+}
+
+static int integ_ensure_ws(sg_amp_plan *p, int B, int nbits) {
+    if (B <= p->cap_Bi) return SG_OK;
+    integ_free_ws(p);
+    const size_t rs = p->precision == SG_F64 ? 8 : 4, Bz = (size_t)B;
+    SG_HIP(hipMalloc(&p->wi_alpha, Bz * p->LM * rs));
+    SG_HIP(hipMalloc(&p->wi_gamma, Bz * p->LM * rs));
+    SG_HIP(hipMalloc(&p->wi_x, Bz * p->n * rs));
+    SG_HIP(hipMalloc(&p->wi_vk0, Bz * nbits * rs));
+    SG_HIP(hipMalloc(&p->wi_vk, Bz * nbits * rs));
+    SG_HIP(hipMalloc(&p->wi_llr, Bz * nbits * rs));
+    SG_HIP(hipMalloc(&p->wi_app, Bz * nbits * rs));
+    SG_HIP(hipMalloc((void **)&p->wi_it, Bz * nbits * sizeof(int32_t)));
+    SG_HIP(hipMalloc((void **)&p->wi_part, Bz * p->L * sizeof(double)));
+    SG_HIP(hipMalloc((void **)&p->wi_ons, Bz * sizeof(double)));
+    p->cap_Bi = B;
+    return SG_OK;
 }
 
 static int plan_free_ws(sg_amp_plan *p) {
@@ -1703,52 +1739,138 @@ static int decode_impl(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_
     return SG_OK;
 }
 
+// The enqueue part of the design operators: in and out are device vectors of the plan precision in natural
+// order (transpose 0: in [B][LM] -> out [B][n]; 1: in [B][n] -> out [B][LM]).  Launches only -- no stream
+// synchronisation, no host-to-device copy -- in the workspace ensure_ws(p, B, 2) holds.  The general engine reads
+// its input from ws_beta / ws_z (copied there unless it already is) and needs every codeword active and phi = 1
+// on the device before (apply_impl uploads them, the integrated loop sets them once before its first iteration).
+template <typename T>
+static int apply_enqueue(sg_amp_plan *p, int transpose, const T *in, int B, T *out, hipStream_t s) {
+    if (p->regular) {
+        RegTables<T> rt = rtables<T>(p);
+        RegBufs<T> rf = rbufs<T>(p, B, nullptr);
+        rf.mode = 1;
+        rf.ext_in = in;
+        rf.ext_out = out;
+        if (!transpose) {
+            SG_TRY(reg_launch_ab<T>(rt, rf, s));
+            SG_TRY(reg_launch_ab_finish<T>(rt, rf, s));
+        } else {
+            SG_TRY(reg_launch_az<T>(rt, rf, 0, s));
+        }
+        return SG_OK;
+    }
+    AmpTables<T> tb = tables<T>(p);
+    AmpBufs<T> bf = bufs<T>(p, B, nullptr);
+    if (!transpose) {
+        if (in != (const T *)p->ws_beta)
+            SG_HIP(hipMemcpyAsync(p->ws_beta, in, (size_t)B * p->LM * sizeof(T), hipMemcpyDeviceToDevice, s));
+        SG_TRY(amp_launch_ab<T>(tb, bf, s));
+        SG_TRY(amp_launch_rowsum<T>(tb, bf, out, s));
+    } else {
+        if (in != (const T *)p->ws_z)
+            SG_HIP(hipMemcpyAsync(p->ws_z, in, (size_t)B * p->n * sizeof(T), hipMemcpyDeviceToDevice, s));
+        SG_TRY(amp_launch_az<T>(tb, bf, s));
+        SG_TRY(amp_launch_colgather<T>(tb, bf, out, s));
+    }
+    return SG_OK;
+}
+
 template <typename T>
 static int apply_impl(sg_amp_plan *p, int transpose, const void *d_in, int in_is_double, int B, void *d_out,
                       int out_double, hipStream_t s) {
     SG_TRY(ensure_ws(p, B, 2));
     if (p->regular) {
-        RegTables<T> rt = rtables<T>(p);
-        RegBufs<T> rf = rbufs<T>(p, B, nullptr);
-        rf.mode = 1;
         if (!transpose) {
             SG_TRY(amp_launch_cast<T>(d_in, in_is_double, (T *)p->ws_s, (size_t)B * p->LM, s));
-            rf.ext_in = (const T *)p->ws_s;
-            rf.ext_out = out_double ? (T *)p->ws_z : (T *)d_out;
-            SG_TRY(reg_launch_ab<T>(rt, rf, s));
-            SG_TRY(reg_launch_ab_finish<T>(rt, rf, s));
-            if (out_double) SG_TRY(amp_launch_uncast<T>((T *)p->ws_z, (double *)d_out, (size_t)B * p->n, s));
+            T *out = out_double ? (T *)p->ws_z : (T *)d_out;
+            SG_TRY(apply_enqueue<T>(p, 0, (const T *)p->ws_s, B, out, s));
+            if (out_double) SG_TRY(amp_launch_uncast<T>(out, (double *)d_out, (size_t)B * p->n, s));
         } else {
             SG_TRY(amp_launch_cast<T>(d_in, in_is_double, (T *)p->ws_y, (size_t)B * p->n, s));
-            rf.ext_in = (const T *)p->ws_y;
-            rf.ext_out = out_double ? (T *)p->ws_s : (T *)d_out;
-            SG_TRY(reg_launch_az<T>(rt, rf, 0, s));
-            if (out_double) SG_TRY(amp_launch_uncast<T>((T *)p->ws_s, (double *)d_out, (size_t)B * p->LM, s));
+            T *out = out_double ? (T *)p->ws_s : (T *)d_out;
+            SG_TRY(apply_enqueue<T>(p, 1, (const T *)p->ws_y, B, out, s));
+            if (out_double) SG_TRY(amp_launch_uncast<T>(out, (double *)d_out, (size_t)B * p->LM, s));
         }
         SG_HIP(hipStreamSynchronize(s));
         return SG_OK;
     }
-    AmpTables<T> tb = tables<T>(p);
-    AmpBufs<T> bf = bufs<T>(p, B, nullptr);
     // all codewords active
     std::vector<int32_t> ones(B, 1);
     SG_HIP(hipMemcpyAsync(p->ws_active, ones.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, s));
+    std::vector<double> ph;
     if (!transpose) {
         SG_TRY(amp_launch_cast<T>(d_in, in_is_double, (T *)p->ws_beta, (size_t)B * p->LM, s));
-        SG_TRY(amp_launch_ab<T>(tb, bf, s));
         T *out = out_double ? (T *)p->ws_z : (T *)d_out;
-        SG_TRY(amp_launch_rowsum<T>(tb, bf, out, s));
+        SG_TRY(apply_enqueue<T>(p, 0, (const T *)p->ws_beta, B, out, s));
         if (out_double) SG_TRY(amp_launch_uncast<T>(out, (double *)d_out, (size_t)B * p->n, s));
     } else {
         SG_TRY(amp_launch_cast<T>(d_in, in_is_double, (T *)p->ws_z, (size_t)B * p->n, s));
-        std::vector<double> ph((size_t)B * p->Lr, 1.0);
+        ph.assign((size_t)B * p->Lr, 1.0);
         SG_HIP(hipMemcpyAsync(p->ws_phi, ph.data(), sizeof(double) * ph.size(), hipMemcpyHostToDevice, s));
-        SG_TRY(amp_launch_az<T>(tb, bf, s));
         T *out = out_double ? (T *)p->ws_beta : (T *)d_out;
-        SG_TRY(amp_launch_colgather<T>(tb, bf, out, s));
+        SG_TRY(apply_enqueue<T>(p, 1, (const T *)p->ws_z, B, out, s));
         if (out_double) SG_TRY(amp_launch_uncast<T>(out, (double *)d_out, (size_t)B * p->LM, s));
     }
     SG_HIP(hipStreamSynchronize(s));
+    return SG_OK;
+}
+
+// The AMP <-> BP integrated decoders on a flat plan: integ_impl of capi_dense.cpp with the two GEMMs replaced by
+// the plan's operators on natural-order vectors and the three passes eta / bit probabilities / LLRs by one
+// section kernel (integrated_dct.hip).  beta lives in the plan's [B][LM] workspace (ws_s of a regular plan, ws_beta
+// of a general one), z in ws_z; u = Az(z) is written into the alpha buffer, where the section kernel turns it into
+// the weighted alpha.  Nothing but launches and device-to-device copies inside the loop.
+template <typename T>
+static int integ_dct_impl(sg_amp_plan *p, sg_graph *g, int mode, int N, int K, const void *d_y, int B, int t_max,
+                          int its, int its_final, uint8_t *d_bits, void *d_app, double *d_tau_hist, hipStream_t s) {
+    const int logM = ilog2(p->M);
+    const int nbits = p->L * logM, nblk = nbits / N;
+    SG_TRY(ensure_ws(p, B, 2));
+    SG_TRY(integ_ensure_ws(p, B, nbits));
+    const double P = p->W[0], snp = std::sqrt((double)p->n * (P / p->L));
+    const bool naive = mode == SG_INT_NAIVE || mode == SG_INT_NAIVE_POST;
+    const bool post = mode == SG_INT_NAIVE_POST || mode == SG_INT_DIFF_POST;
+    const int ons_mode = naive ? 0 : (mode == SG_INT_DIFF ? 1 : 2);
+    T *beta = p->regular ? (T *)p->ws_s : (T *)p->ws_beta, *z = (T *)p->ws_z, *xhat = (T *)p->wi_x;
+    T *alpha_w = (T *)p->wi_alpha, *gamma = (T *)p->wi_gamma, *vk0 = (T *)p->wi_vk0, *vk = (T *)p->wi_vk;
+    T *llr = (T *)p->wi_llr, *app = (T *)p->wi_app;
+    const T *y = (const T *)d_y;
+    double *tau = p->ws_tau;  // [B] (Lc = 1): the plan's tau^2 slot
+    const size_t nb = (size_t)B * nbits;
+    const int prec = sizeof(T) == 8 ? SG_F64 : SG_F32;
+    DenseBufs<T> db{};  // dense_launch_bsq reads beta, the shape and sec_bsq only
+    db.L = p->L; db.M = p->M; db.LM = p->LM; db.B = B; db.beta = beta; db.sec_bsq = p->wi_part;
+    SG_HIP(hipMemsetAsync(beta, 0, (size_t)B * p->LM * sizeof(T), s));
+    if (!p->regular) SG_TRY(idct_launch_ones(p->ws_active, B, p->ws_phi, B * p->Lr, s));
+    for (int t = 0; t < t_max; ++t) {
+        if (!naive && t > 0) {  // sum of the differentiated eta with the previous tau^2
+            ProfScope ps(SG_PH_INT_DETA, s);
+            SG_TRY(integ_launch_deta<T>(post ? 1 : 0, beta, gamma, alpha_w, snp, vk, vk0, tau, B, p->L, p->M, snp,
+                                        p->wi_part, p->wi_ons, (T *)nullptr, s));
+        }
+        if (t > 0) SG_TRY(apply_enqueue<T>(p, 0, beta, B, xhat, s));  // xhat = Ab(beta) = snp A beta
+        SG_TRY(idct_launch_residual<T>(y, xhat, z, B, p->n, p->L, snp, P, ons_mode, p->wi_ons, p->wi_part, t, tau,
+                                       d_tau_hist, t_max, s));
+        SG_TRY(apply_enqueue<T>(p, 1, z, B, alpha_w, s));  // u = Az(z) = snp A^T z
+        SG_TRY(idct_launch_section<T>(alpha_w, beta, tau, B, p->L, p->M, snp, vk0, llr, s));
+        if (t == t_max - 1) {
+            T *app_out = d_app ? (T *)d_app : app;
+            SG_TRY(sg_ldpc_decode_device(g, SG_SUMPROD2, prec, llr, B * nblk, its_final, 0.7, app_out, p->wi_it, s));
+            SG_TRY(integ_launch_hard_bits<T>(app_out, B * nblk, N, K, d_bits, s));
+            break;
+        }
+        SG_TRY(sg_ldpc_decode_device(g, SG_SUMPROD2, prec, llr, B * nblk, its, 0.7, app, p->wi_it, s));
+        ProfScope ps(SG_PH_INT_GLUE, s);
+        SG_TRY(idct_launch_probs<T>(app, nb, vk, s));
+        if (!post) {
+            SG_TRY(integ_launch_bp_to_beta<T>(vk, B, p->L, p->M, snp, 0, beta, s));
+        } else {
+            SG_TRY(integ_launch_bp_to_beta<T>(vk, B, p->L, p->M, snp, 1, gamma, s));
+            SG_TRY(integ_launch_update<T>(gamma, alpha_w, snp, B, p->L, p->M, snp, beta, s));
+        }
+        if (naive) SG_TRY(dense_launch_bsq<T>(db, s));  // ||beta||^2 of the BP-derived beta for the Onsager term
+    }
     return SG_OK;
 }
 
@@ -1822,6 +1944,7 @@ int sg_amp_plan_destroy(sg_amp_plan *p) {
     if (!p) return SG_OK;
     sg_amp_plan_destroy(p->alt);
     plan_free_ws(p);
+    integ_free_ws(p);
     for (void *a : p->allocs) hipFree(a);
     if (p->tprof) hipFree(p->tprof);
     if (p->poll_ev) {
@@ -2092,6 +2215,73 @@ int sg_amp_llr(sg_amp_plan *p, int B, int l0, int nl, int probs_only, double *ou
         SG_TRY(amp_launch_uncast<float>(df, dd, nv, s));
     }
     SG_HIP(hipMemcpyAsync(out, dd, nv * sizeof(double), hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    return SG_OK;
+}
+
+// Every refusal of the integrated decoders, before anything is launched or allocated (header, sg_amp_integrated_decode_device)
+static int integ_dct_checks(const sg_amp_plan *p, sg_graph *g, int mode, int K, int t_max, int bp_its, int bp_its_final,
+                            int *N_out) {
+    SG_CHECK_ARG(mode >= SG_INT_NAIVE && mode <= SG_INT_DIFF_POST, "unknown integrated decoder %d", mode);
+    if (p->ndim != 0)
+        return fail(SG_ERR_UNSUPPORTED, "integrated decoders need a flat design (scalar W), not W.ndim = %d: they "
+                    "know one P_l and one tau^2 per codeword", p->ndim);
+    if (p->block || p->block2) return fail(SG_ERR_UNSUPPORTED, "no integrated decoder on the block engines");
+    if (p->M < 2 || (p->M & (p->M - 1)) != 0 || p->M > 2048)
+        return fail(SG_ERR_UNSUPPORTED, "section size M = %d: the integrated section kernel takes a power of two in "
+                    "[2, 2048]", p->M);
+    int N = 0;
+    SG_TRY(sg_ldpc_graph_info(g, &N, nullptr, nullptr, nullptr, nullptr));
+    const int logM = ilog2(p->M);
+    SG_CHECK_ARG(N > 0 && (p->L * logM) % N == 0, "L log2 M = %d bits must be a multiple of the block length %d",
+                 p->L * logM, N);  // ldpc_bp's assert (sparc_new.py:1171)
+    SG_CHECK_ARG(K > 0 && K <= N, "bad information length %d", K);
+    SG_CHECK_ARG(t_max >= 1 && bp_its >= 0 && bp_its_final >= 0, "bad iteration counts");
+    *N_out = N;
+    return SG_OK;
+}
+
+int sg_amp_integrated_decode_device(sg_amp_plan *p, sg_graph *g, int mode, int K, const void *d_y, int B, int t_max,
+                                    int bp_its, int bp_its_final, uint8_t *d_bits, void *d_app, double *d_tau2,
+                                    void *stream) {
+    SG_CHECK_ARG(p && g && d_y && d_bits, "null argument");
+    reset_last(p);  // (the loop runs in the workspace that holds a decode's final state)
+    int N = 0;
+    SG_TRY(integ_dct_checks(p, g, mode, K, t_max, bp_its, bp_its_final, &N));
+    if (B <= 0) return SG_OK;
+    SG_TRY(ensure_device());
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = pick_stream(stream);
+    return p->precision == SG_F64
+               ? integ_dct_impl<double>(p, g, mode, N, K, d_y, B, t_max, bp_its, bp_its_final, d_bits, d_app, d_tau2, s)
+               : integ_dct_impl<float>(p, g, mode, N, K, d_y, B, t_max, bp_its, bp_its_final, d_bits, d_app, d_tau2, s);
+}
+
+int sg_amp_integrated_decode(sg_amp_plan *p, sg_graph *g, int mode, int K, const double *y, int B, int t_max,
+                             int bp_its, int bp_its_final, uint8_t *bits, double *tau2) {
+    SG_CHECK_ARG(p && g && y && bits, "null argument");
+    reset_last(p);
+    int N = 0;
+    SG_TRY(integ_dct_checks(p, g, mode, K, t_max, bp_its, bp_its_final, &N));
+    if (B <= 0) return SG_OK;
+    SG_TRY(ensure_device());
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = lib_stream();
+    const size_t rs = p->precision == SG_F64 ? 8 : 4, ny = (size_t)B * p->n, nt = (size_t)B * t_max;
+    const size_t nbits = (size_t)B * (p->L * ilog2(p->M) / N) * K;
+    SG_TRY(ensure_ws(p, B, 2));  // (before the staging buffer: growing the workspace frees ws_io too)
+    // staging: y as doubles, the tau^2 history, y in the plan precision, the bits
+    SG_TRY(ensure_io(p, (ny + nt) * 8 + ny * rs + nbits));
+    double *dy = (double *)p->ws_io, *dtau = dy + ny;
+    void *dyt = dtau + nt;
+    uint8_t *dbits = (uint8_t *)dyt + ny * rs;
+    SG_HIP(hipMemcpyAsync(dy, y, ny * 8, hipMemcpyHostToDevice, s));
+    if (p->precision == SG_F64) SG_TRY(amp_launch_cast<double>(dy, 1, (double *)dyt, ny, s));
+    else SG_TRY(amp_launch_cast<float>(dy, 1, (float *)dyt, ny, s));
+    SG_TRY(sg_amp_integrated_decode_device(p, g, mode, K, dyt, B, t_max, bp_its, bp_its_final, dbits, nullptr,
+                                           tau2 ? dtau : nullptr, s));
+    SG_HIP(hipMemcpyAsync(bits, dbits, nbits, hipMemcpyDeviceToHost, s));
+    if (tau2) SG_HIP(hipMemcpyAsync(tau2, dtau, nt * 8, hipMemcpyDeviceToHost, s));
     SG_HIP(hipStreamSynchronize(s));
     return SG_OK;
 }

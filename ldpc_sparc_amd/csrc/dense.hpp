@@ -65,6 +65,21 @@ int integ_launch_deta(int post, const T *beta, const T *gamma, const T *alpha_w,
 template <typename T>
 int integ_launch_hard_bits(const T *app, int nblocks, int N, int K, uint8_t *bits, hipStream_t s);
 
+// integrated decoders on the sub-sampled DCT design (integrated_dct.hip), natural-order vectors:
+// z <- y - xhat / snp + c_b z and tau^2 = ||z||^2 / n (ons_mode as DenseBufs; sec_bsq [B][L] for mode 0)
+template <typename T>
+int idct_launch_residual(const T *y, const T *xhat, T *z, int B, int n, int L, double snp, double P, int ons_mode,
+                         const double *ons, const double *sec_bsq, int t, double *tau, double *tau_hist, int t_max,
+                         hipStream_t s);
+// ua: u = Az(z) in, weighted alpha out; vk0 and llr [B][L log2 M]
+template <typename T>
+int idct_launch_section(T *ua, const T *beta, const double *tau, int B, int L, int M, double snp, T *vk0, T *llr,
+                        hipStream_t s);
+// P(bit = 0) from the BP output, finite for every app (integ_launch_probs overflows in single precision)
+template <typename T>
+int idct_launch_probs(const T *app, size_t nn, T *p, hipStream_t s);
+int idct_launch_ones(int32_t *active, int B, double *phi, int nphi, hipStream_t s);
+
 template <typename T>
 int concat_launch_count(const int32_t *map_idx, const int32_t *true_idx, int B, int L, int L_unp, int logM,
                         const T *app, const uint8_t *info, int mults, int N, int K, int64_t *counts, hipStream_t s);

@@ -194,3 +194,43 @@ class DctConcatPipeline(ConcatPipeline):
         _native.check(lib.sg_concat_count_errors_device(self.prec, self.d_idx.ptr, self.d_true.ptr, B, self.L,
                                                         self.L_unp, self.logM, self.d_app.ptr, self.d_info.ptr,
                                                         self.mults, c.N, c.K, self.d_cnt.ptr, None))
+
+
+class DctIntegratedPipeline(DctConcatPipeline):
+    """The AMP <-> BP integrated decoders (sparc_new.py:257-282, :411-439, :472-502, :675-705) on the flat
+    sub-sampled DCT design: `bp_its` BP iterations inside each of the t_max AMP iterations and a final
+    `bp_its_final`-iteration decode (sg_amp_integrated_decode_device), counted on the device from its final BP
+    output.  Every section is LDPC protected (L_unprotected = 0, ldpc_bp's assert :1171).  Same methods, device
+    buffers and counter layout as ConcatPipeline, so montecarlo.ConcatTrial takes it unchanged."""
+
+    def __init__(self, L, M, n, P, L_unprotected=0, mults=None, ldpc=("802.11n", "1/2", 81), design_seed=0,
+                 precision="f32", t_max=25, mode="integrated", bp_its=6, bp_its_final=200, op=None):
+        if L_unprotected != 0:
+            raise ValueError("the integrated decoders protect every section: L_unprotected must be 0")
+        if mode not in _native.INTEGRATED_MODES:
+            raise ValueError(f"mode must be one of {sorted(_native.INTEGRATED_MODES)}")
+        c = code(*ldpc)
+        if mults is None:
+            mults = int(L) * int(np.log2(M)) // c.N
+        super().__init__(L, M, n, P, 0, mults, ldpc=ldpc, design_seed=design_seed, precision=precision, t_max=t_max,
+                         bp_dectype="sumprod2", bp_its=bp_its_final, op=op)
+        if self.op.W.ndim != 0:
+            raise ValueError("the integrated decoders need a flat design (scalar W)")
+        self.mode, self.bp_its_inner, self.bp_its_final = mode, int(bp_its), int(bp_its_final)
+
+    def _ensure(self, B):
+        if B <= self._cap:
+            return
+        super()._ensure(B)
+        self.d_bits = _native.DeviceBuffer(B * self.mults * self.c.K)
+
+    def decode(self):
+        """One batch: returns nothing; counters accumulate in d_cnt."""
+        lib, c, B = _native.lib(), self.c, self.B
+        _native.check(lib.sg_amp_integrated_decode_device(
+            self.plan, self.graph, _native.INTEGRATED_MODES[self.mode], c.K, self.d_y.ptr, B, self.t_max,
+            self.bp_its_inner, self.bp_its_final, self.d_bits.ptr, self.d_app.ptr, None, None))
+        # no unprotected section: the section-index arguments carry no bits (valid buffers all the same)
+        _native.check(lib.sg_concat_count_errors_device(self.prec, self.d_true.ptr, self.d_true.ptr, B, self.L, 0,
+                                                        self.logM, self.d_app.ptr, self.d_info.ptr, self.mults, c.N,
+                                                        c.K, self.d_cnt.ptr, None))

@@ -71,6 +71,38 @@ class DenseDesign:
         self.release()
 
 
+class DctDesign:
+    """A flat sub-sampled DCT design (sparc.DesignOperator with scalar W = P) for the integrated decoders:
+    the matrix A[i, j] = sqrt(2 / n) cos(pi (2 order1[j] + 1) order0[i] / (2 w)) applied through the operator's
+    transforms instead of stored.  Mirrors DenseDesign (P, L, M, n, plan, release)."""
+
+    def __init__(self, op):
+        if getattr(op, "csparc", False) or op.W.ndim != 0:
+            raise ValueError("DctDesign needs a real flat DesignOperator (scalar W): the integrated decoders know "
+                             "one P_l and one tau^2 per codeword")
+        self.op = op
+        self.P, self.L, self.M, self.n = float(op.W), op.L, op.M, op.n
+
+    @classmethod
+    def from_seed(cls, L, M, n, P, seed):
+        """The flat design whose orders sparc.generate_ordering draws from `seed`."""
+        from . import sparc
+        W = np.array(float(P))
+        o0, o1 = sparc.generate_ordering(W, int(n), int(L) * int(M), seed)
+        return cls(sparc.DesignOperator(W, int(L), int(M), int(n), o0, o1))
+
+    def plan(self, precision=_native.SG_F64):
+        return self.op.plan(precision)
+
+    def release(self):
+        for h in self.op._plans.values():
+            try:
+                _native.lib().sg_amp_plan_destroy(h)
+            except Exception:
+                pass
+        self.op._plans = {}
+
+
 _design_cache = {"key": None, "design": None}
 
 
@@ -346,7 +378,8 @@ def bit_err_rate(bits_in, bits_out):
 
 
 def integrated_decode_batch(Y, design, c, mode, t_max, num_its=6, num_its_final=200, precision=_native.SG_F64):
-    """Batched integrated decoding of received words sharing one design.
+    """Batched integrated decoding of received words sharing one design: a DenseDesign (sg_integrated_decode)
+    or a DctDesign (sg_amp_integrated_decode, the same decoders on the sub-sampled DCT operator).
     mode: 'naive' | 'naive_posteriors' | 'integrated' | 'integrated_posteriors'.
     Returns (information bits uint8 [B, blocks*K], tau^2 [B, t_max])."""
     Y = np.ascontiguousarray(Y, dtype=np.float64)
@@ -357,7 +390,9 @@ def integrated_decode_batch(Y, design, c, mode, t_max, num_its=6, num_its_final=
     B = Y.shape[0]
     bits = np.zeros((B, design.L * logM // c.N * c.K), dtype=np.uint8)
     tau2 = np.zeros((B, int(t_max)))
-    _native.check(_native.lib().sg_integrated_decode(
+    lib = _native.lib()
+    decode = lib.sg_amp_integrated_decode if isinstance(design, DctDesign) else lib.sg_integrated_decode
+    _native.check(decode(
         design.plan(precision), c._device_graph(), _native.INTEGRATED_MODES[mode], int(c.K), _native.ptr(Y), B,
         int(t_max), int(num_its), int(num_its_final), _native.ptr(bits), _native.ptr(tau2)))
     return bits, tau2
