@@ -1,5 +1,5 @@
 // Declarations shared by the AMP decoder kernels (amp_dct.hip) and the host
-// plan / C ABI (capi_amp.cpp).
+// plan / C ABI (amp_plan.hpp, capi_amp.cpp).
 #pragma once
 #include "common.hpp"
 #include "fft.hpp"

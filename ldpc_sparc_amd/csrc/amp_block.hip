@@ -73,7 +73,7 @@ __device__ __forceinline__ int bk_opaque(int v) {
 // Column entry i (< 16) of thread tid: wavefront w owns sections
 // w spw .. w spw + spw - 1 of the column block (spw = 1024 / M), lane l holds
 // entries l eps .. l eps + eps - 1 of each (eps = M / 64).  Needs Mc = 16384
-// and 64 <= M <= 1024 (host mirror in capi_amp.cpp build_block).
+// and 64 <= M <= 1024 (host mirror in amp_plan_block.cpp build_block).
 template <int EPS>
 __device__ __forceinline__ int bk_j(int tid, int i) {
     constexpr int M = 64 * EPS, SPW = 1024 / M;

@@ -47,7 +47,7 @@ constexpr int B2_J = 32;  // column entries per thread (Mc = 2 P = 32 threads), 
 // a padding slot -- never written by the rows or the FFT stages, so zero after
 // b2_clear -- is the trash slot of the position tables
 constexpr int B2_TRASH = 2 * 32;  // real index of the padding slot at complex position 32
-static_assert(ppos(B2_TRASH / 2) == B2_TRASH / 2 + 1, "the trash slot is a padding slot (capi_amp.cpp build_block2)");
+static_assert(ppos(B2_TRASH / 2) == B2_TRASH / 2 + 1, "the trash slot is a padding slot (amp_plan_block.cpp build_block2)");
 
 namespace {
 
@@ -85,7 +85,7 @@ __device__ __forceinline__ void b2_clear(unsigned char *smem, int tid) {
 // Column entry i (< 32) of thread tid: wavefront w owns sections
 // w spw .. w spw + spw - 1 of the column block (spw = 2048 / M), lane l holds
 // entries l eps .. l eps + eps - 1 of each (eps = M / 64).  Host mirror in
-// capi_amp.cpp build_block2.
+// amp_plan_block.cpp build_block2.
 template <int EPS>
 __device__ __forceinline__ int b2_j(int tid, int i) {
     constexpr int M = 64 * EPS, SPW = 2048 / M;

@@ -83,7 +83,7 @@ __device__ __forceinline__ void cw_swap32(cx<float> &a, cx<float> &b) {
 // j 16 + 2 q + H like stockham1_stage_ct's.  The image is not
 // zeroed before the class scatter / row writes: bit 2 jj + c of msk says
 // whether component c of value jj was written for this transform (host
-// table, capi_amp.cpp build_cw), and the stale ones read as zero.
+// table, amp_plan_cw.cpp build_cw), and the stale ones read as zero.
 template <bool INV>
 __device__ __forceinline__ void cw_stage0_r16(cx<float> *d, int tid, uint32_t msk) {
     const int l = tid & 63, H = l >> 5, j = ((tid >> 6) << 5) | (l & 31);

@@ -1,4 +1,4 @@
-"""The polar form of the split engine's inverse coefficients (capi_amp.cpp
+"""The polar form of the split engine's inverse coefficients (amp_plan_cw.cpp
 build_cw2, amp_cw2.hip cw2_az rows), restated in numpy and checked on every
 output of the C2 design and of a w = 2^19 design (CPU; the GPU suite runs the
 engine built from the same fit: tests/test_amp_cw2_gpu.py).
