@@ -2,6 +2,7 @@
 // plan / C ABI (amp_plan.hpp, capi_amp.cpp).
 #pragma once
 #include "common.hpp"
+#include "device_util.hpp"
 #include "fft.hpp"
 
 namespace sg {
@@ -209,6 +210,18 @@ constexpr uint32_t CW_SELF = 1u << 23;  // the pair's two rows coincide (r = 0 o
 constexpr int CW_OFFSHIFT = 24;
 // a thread's slots padded to a multiple of four (thread-major tables: 16-byte loads)
 __host__ __device__ constexpr int cw2_otp(int ot) { return (ot + 3) & ~3; }
+// a thread's OT slot words of a thread-major [512][OTP] table, 16 bytes per load
+template <int OT>
+__device__ __forceinline__ void ld_slots(__amdgpu_buffer_rsrc_t r, int tl, uint32_t *out) {
+    constexpr int OTP = cw2_otp(OT);
+#pragma unroll
+    for (int q = 0; q < OTP / 4; ++q) {
+        const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, 4 * OTP * tl, 16 * q, 0);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (4 * q + c < OT) out[4 * q + c] = v[c];
+    }
+}
 // z / phi thread-major (one load round of 16-byte loads in cw2_az) up to 12 slots per thread; above, cw2_az
 // loads the slots in two rounds of single words, slot-major
 __host__ __device__ constexpr bool cw2_vz_tm(int ot) { return ot <= 12; }

@@ -23,7 +23,7 @@
 //            reads beta once per iteration.
 // Versus the general four-step path (amp_dct.hip) no transform intermediate
 // reaches HBM and the random-order gather of u happens in LDS.
-#include "amp.hpp"
+#include "amp_block_common.hpp"
 
 namespace sg {
 
@@ -31,64 +31,18 @@ constexpr int BK_THREADS = 1024;
 constexpr int BK_LOG2N = 14;
 constexpr int BK_J = 16;  // column entries per thread (Mc = 16384)
 
-template <typename T>
-__device__ __forceinline__ T bk_wave_max(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T bk_wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int bk_wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // LDS: the FFT image in the padded layout (element i at ppos(i) = i + i/32:
 // every FFT stage access a per-thread base plus a constant, no swizzle
 // arithmetic)
 constexpr int BK_IMG = ppos(1 << BK_LOG2N);  // complex slots
 size_t blk_lds_bytes(int Mc) { return (size_t)BK_IMG * sizeof(cx<float>); }
 
-__device__ __forceinline__ void bk_clear(unsigned char *smem, int tid) {
-    constexpr int N16 = BK_IMG * (int)sizeof(cx<float>) / 16;  // (8448: 8 per thread and a quarter)
-#pragma unroll
-    for (int i = 0; i < (N16 + BK_THREADS - 1) / BK_THREADS; ++i)
-        if (tid + i * BK_THREADS < N16) reinterpret_cast<uint4 *>(smem)[tid + i * BK_THREADS] = uint4{0, 0, 0, 0};
-}
-
-// The thread index as a value the compiler cannot see through: the FFT's LDS
-// addresses are then recomputed inside the loop over a column's transforms
-// instead of being hoisted out of it and held (and spilled) across the loop.
-__device__ __forceinline__ int bk_opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-// Column entry i (< 16) of thread tid: wavefront w owns sections
-// w spw .. w spw + spw - 1 of the column block (spw = 1024 / M), lane l holds
-// entries l eps .. l eps + eps - 1 of each (eps = M / 64).  Needs Mc = 16384
-// and 64 <= M <= 1024 (host mirror in amp_plan_block.cpp build_block).
-template <int EPS>
-__device__ __forceinline__ int bk_j(int tid, int i) {
-    constexpr int M = 64 * EPS, SPW = 1024 / M;
-    const int sq = i / EPS, e = i - sq * EPS;
-    return ((tid >> 6) * SPW + sq) * M + (tid & 63) * EPS + e;
-}
-
-// LDS positions of the thread's column entries bk_j(tid, i) of transform t,
-// packed in pairs (i = 2 i2, 2 i2 + 1) in thread order
+// The column layout is blk_j<EPS, BK_J> (amp_block_common.hpp; Mc = 16384,
+// 64 <= M <= 1024, host mirror in amp_plan_block.cpp build_block); the
+// position table holds one image per transform
 __device__ __forceinline__ void bk_pos_load(const BlkTables &tb, int t, int tid, uint32_t *pv) {
-    const uint32_t *p2 = tb.pos2 + (size_t)t * (BK_J / 2) * BK_THREADS;
-#pragma unroll
-    for (int i = 0; i < BK_J / 2; ++i) pv[i] = p2[i * BK_THREADS + tid];
+    blk_pos_load<BK_THREADS, BK_J>(tb, (size_t)t, tid, pv);
 }
-__device__ __forceinline__ uint32_t bk_pos(const uint32_t *pv, int i) { return (pv[i >> 1] >> (16 * (i & 1))) & 0xffffu; }
 
 // The first three stages of the 2^14-point FFT of fft.hpp (radix 16, 16, 16,
 // then 4): the forward transform stops before the radix-4 stage, which Ab
@@ -111,22 +65,22 @@ __device__ __forceinline__ void bk_fwd_stage2(cx<float> *d, int tid, const cx<fl
 
 // ------------------------------------------------------------------ Ab
 // The omega forward transforms of column block c from beta_c in registers
-// (bv[i] = beta_c[bk_j(tid, i)])
+// (bv[i] = beta_c[blk_j<EPS, BK_J>(tid, i)])
 __device__ __forceinline__ void bk_ab_column(const BlkTables &tb, const AmpBufs<float> &bf, int c, int cw, int tid,
                                              const float *bv, unsigned char *smem) {
     cx<float> *d = reinterpret_cast<cx<float> *>(smem);
     float *dr = reinterpret_cast<float *>(smem);
     for (int q = tb.col_ptr[c]; q < tb.col_ptr[c + 1]; ++q) {
         const int t = tb.col_t[q];
-        const int tl = bk_opaque(tid);
+        const int tl = opaque(tid);
         // the positions of this transform, in flight while the image clears
         uint32_t pv[BK_J / 2];
         bk_pos_load(tb, t, tl, pv);
-        bk_clear(smem, tl);
+        blk_clear<BK_THREADS, BK_IMG>(smem, tl);
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < BK_J; ++i)
-            dr[bk_pos(pv, i)] = bv[i];
+            dr[blk_pos(pv, i)] = bv[i];
         __syncthreads();
         cx<float> w2[6];
         bk_fwd_stages01(d, tb.stw, tl, w2);
@@ -259,7 +213,7 @@ __global__ __launch_bounds__(BK_THREADS) void blk_az(BlkTables tb, AmpBufs<float
     // the order of gather_u (amp_dct.hip)
     for (int q = tb.col_ptr[c]; q < tb.col_ptr[c + 1]; ++q) {
         const int t = tb.col_t[q];
-        const int tl = bk_opaque(tid);
+        const int tl = opaque(tid);
         // G slots (from z / phi, <= 4 terms), in flight while the image clears
         const int g0 = tb.gptr[t], ng = tb.gptr[t + 1] - g0;
         cx<float> gv[2];
@@ -272,7 +226,7 @@ __global__ __launch_bounds__(BK_THREADS) void blk_az(BlkTables tb, AmpBufs<float
                 gl[k] = tb.gloc[g0 + g];
             }
         }
-        bk_clear(smem, tl);
+        blk_clear<BK_THREADS, BK_IMG>(smem, tl);
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < 2; ++k)
@@ -287,13 +241,13 @@ __global__ __launch_bounds__(BK_THREADS) void blk_az(BlkTables tb, AmpBufs<float
         bk_pos_load(tb, t, tl, pv);
         if (!(tb.skip & 2)) lds_fft1_sincos<true, 16, BK_LOG2N, 3, 4, true>(d, tl);
 #pragma unroll
-        for (int i = 0; i < BK_J; ++i) u[i] += dr[bk_pos(pv, i)];
+        for (int i = 0; i < BK_J; ++i) u[i] += dr[blk_pos(pv, i)];
         __syncthreads();
     }
     if (tb.skip & 1) return;  // timing ablation only
     // ---- sections of the column block (sparc.py:972, :429-432, :485-487):
     // s = beta + tau u, x = s / tau, beta = exp(x - max) / sum, MAP = first
-    // index of max s.  A wavefront owns whole sections (bk_j): each lane
+    // index of max s.  A wavefront owns whole sections (blk_j): each lane
     // reduces its EPS entries, then one butterfly over the lanes -- no LDS, no
     // workgroup barrier.
     const int lane = tid & 63, wv = tid >> 6;
@@ -306,7 +260,7 @@ __global__ __launch_bounds__(BK_THREADS) void blk_az(BlkTables tb, AmpBufs<float
     float s[BK_J], x[BK_J], bv[BK_J];
 #pragma unroll
     for (int i = 0; i < BK_J; ++i) {
-        const int j = bk_j<EPS>(tid, i);
+        const int j = blk_j<EPS, BK_J>(tid, i);
         s[i] = beta[j] + tau * u[i];  // sparc.py:972
         x[i] = s[i] * itau;           // sparc.py:430, scaled by log2 e
     }
@@ -326,16 +280,16 @@ __global__ __launch_bounds__(BK_THREADS) void blk_az(BlkTables tb, AmpBufs<float
                 arg = lane * eps + e;
             }
         }
-        xm = bk_wave_max(xm);
-        const float gm = bk_wave_max(sm);
-        arg = bk_wave_min(sm == gm ? arg : 0x7fffffff);
+        xm = wave_max(xm);
+        const float gm = wave_max(sm);
+        arg = wave_min(sm == gm ? arg : 0x7fffffff);
         float dn = 0.f;
 #pragma unroll
         for (int e = 0; e < eps; ++e) {
             x[i0 + e] = __builtin_amdgcn_exp2f(x[i0 + e] - xm);
             dn += x[i0 + e];
         }
-        dn = bk_wave_sum(dn);
+        dn = wave_sum(dn);
         const float idn = 1.0f / dn;
         const int truth = bf.true_idx ? bf.true_idx[(size_t)cw * tb.L + l0 + ls] : -1;
         float ss = 0.f, se = 0.f;
@@ -348,8 +302,8 @@ __global__ __launch_bounds__(BK_THREADS) void blk_az(BlkTables tb, AmpBufs<float
             ss += b * b;
             se += dl * dl;
         }
-        ss = bk_wave_sum(ss);
-        se = bk_wave_sum(se);
+        ss = wave_sum(ss);
+        se = wave_sum(se);
         if (lane == 0) {
             const size_t o = (size_t)cw * tb.L + l0 + ls;
             bf.sec_sumsq[o] = (double)ss;
@@ -361,15 +315,6 @@ __global__ __launch_bounds__(BK_THREADS) void blk_az(BlkTables tb, AmpBufs<float
         __syncthreads();
         bk_ab_column(tb, bf, c, cw, tid, bv, smem);
     }
-}
-
-template <int EPS>
-static int blk_set_attrs(size_t lds) {
-    static size_t done = 0;
-    if (done >= lds) return SG_OK;
-    SG_HIP(hipFuncSetAttribute((const void *)blk_az<EPS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    done = lds;
-    return SG_OK;
 }
 
 // section size M = 64 EPS, 64 <= M <= 1024 (compile-time, so the per-lane
@@ -387,7 +332,8 @@ static int blk_set_attrs(size_t lds) {
 template <int EPS>
 static void bk_launch_az(const BlkTables &tb, const AmpBufs<float> &bf, int do_ab, size_t lds, hipStream_t s,
                          int *rc) {
-    *rc = blk_set_attrs<EPS>(lds);
+    static size_t done = 0;
+    *rc = set_max_lds((const void *)blk_az<EPS>, lds, &done);
     if (*rc == SG_OK) hipLaunchKernelGGL(blk_az<EPS>, dim3(tb.Lc, bf.B), dim3(BK_THREADS), lds, s, tb, bf, do_ab);
 }
 

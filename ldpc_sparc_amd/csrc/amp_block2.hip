@@ -22,7 +22,7 @@
 //            slots per row, k1 and k1 + P) -> inverse FFT -> the class's column
 //            entries gathered into u (registers); then the column's sections:
 //            s = beta + tau_c u, softmax, MAP, section statistics (amp_block.hip)
-#include "amp.hpp"
+#include "amp_block_common.hpp"
 
 namespace sg {
 
@@ -45,65 +45,20 @@ struct B2G {
 };
 constexpr int B2_J = 32;  // column entries per thread (Mc = 2 P = 32 threads), all held in registers
 // a padding slot -- never written by the rows or the FFT stages, so zero after
-// b2_clear -- is the trash slot of the position tables
+// blk_clear -- is the trash slot of the position tables
 constexpr int B2_TRASH = 2 * 32;  // real index of the padding slot at complex position 32
 static_assert(ppos(B2_TRASH / 2) == B2_TRASH / 2 + 1, "the trash slot is a padding slot (amp_plan_block.cpp build_block2)");
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ T b2_wave_max(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T b2_wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int b2_wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ int b2_opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-template <int LP>
-__device__ __forceinline__ void b2_clear(unsigned char *smem, int tid) {
-    constexpr int T = B2G<LP>::THREADS, N16 = B2G<LP>::IMG * (int)sizeof(cx<float>) / 16;  // (8 per thread and a quarter)
-#pragma unroll
-    for (int i = 0; i < (N16 + T - 1) / T; ++i)
-        if (tid + i * T < N16) reinterpret_cast<uint4 *>(smem)[tid + i * T] = uint4{0, 0, 0, 0};
-}
-
-// Column entry i (< 32) of thread tid: wavefront w owns sections
-// w spw .. w spw + spw - 1 of the column block (spw = 2048 / M), lane l holds
-// entries l eps .. l eps + eps - 1 of each (eps = M / 64).  Host mirror in
-// amp_plan_block.cpp build_block2.
-template <int EPS>
-__device__ __forceinline__ int b2_j(int tid, int i) {
-    constexpr int M = 64 * EPS, SPW = 2048 / M;
-    const int sq = i / EPS, e = i - sq * EPS;
-    return ((tid >> 6) * SPW + sq) * M + (tid & 63) * EPS + e;
-}
-
-// real LDS index in the image of class m2 (2 ppos(m1) + component; B2_TRASH
-// for the entries of the other class) of the thread's column entries of
-// transform t, packed in pairs
+// The column layout is blk_j<EPS, B2_J> (amp_block_common.hpp; spw = 2048 / M).
+// The position table holds, per transform t and class m2 (image 2 t + m2 of
+// blk_pos_load), the real LDS index 2 ppos(m1) + component of the thread's
+// column entries in the class image, B2_TRASH for the other class's entries.
 template <int LP>
 __device__ __forceinline__ void b2_pos_load(const BlkTables &tb, int t, int m2, int tid, uint32_t *pv) {
-    constexpr int T = B2G<LP>::THREADS;
-    const uint32_t *p2 = tb.pos2 + ((size_t)t * 2 + m2) * (B2_J / 2) * T;
-#pragma unroll
-    for (int i = 0; i < B2_J / 2; ++i) pv[i] = p2[i * T + tid];
+    blk_pos_load<B2G<LP>::THREADS, B2_J>(tb, (size_t)t * 2 + m2, tid, pv);
 }
-__device__ __forceinline__ uint32_t b2_pos(const uint32_t *pv, int i) { return (pv[i >> 1] >> (16 * (i & 1))) & 0xffffu; }
 // (Wave issue priority stays flat here: the split C2 engine's scheme -- transforms 0, the rest 1 -- measured
 // 1000 -> 945 codewords/s, profiles/r05_prio_ab.txt)
 
@@ -123,7 +78,7 @@ size_t blk2_lds_bytes(int log2p) {
 
 // ------------------------------------------------------------------ Ab
 // The column's forward transforms from beta_c in registers (bv[i] = beta_c at
-// b2_j(tid, i)): for each transform and class, scatter -> three radix-16
+// blk_j<EPS, B2_J>(tid, i)): for each transform and class, scatter -> three radix-16
 // stages -> the needed outputs (last radix-RF stage and class factor folded into
 // the coefficients), summed over the classes in registers -> rbuf[t]
 template <int LP>
@@ -135,15 +90,15 @@ __device__ __forceinline__ void b2_ab_column(const BlkTables &tb, const AmpBufs<
         const int t = tb.col_t[q];
         float acc = 0.f;  // output tid (Mr <= THREADS), summed over the two classes
         for (int m2 = 0; m2 < 2; ++m2) {
-            const int tl = b2_opaque(tid);
+            const int tl = opaque(tid);
             // the positions, in flight while the image clears
             uint32_t pv[B2_J / 2];
             b2_pos_load<LP>(tb, t, m2, tl, pv);
-            b2_clear<LP>(smem, tl);
+            blk_clear<B2G<LP>::THREADS, B2G<LP>::IMG>(smem, tl);
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < B2_J; ++i)  // (the other class's entries: trash slot)
-                dr[b2_pos(pv, i)] = bv[i];
+                dr[blk_pos(pv, i)] = bv[i];
             // the output's bins and coefficients, requested before the transform (their L2 round trip
             // hides behind it; requested after it, one workgroup per CU waited for it every class)
             constexpr int RF = B2G<LP>::RF;
@@ -185,7 +140,7 @@ __global__ __launch_bounds__(B2G<LP>::THREADS, 4) void blk2_ab(BlkTables tb, Amp
     const float *beta = bf.beta + (size_t)cw * tb.LM + (size_t)c * tb.Mc;
     float bv[B2_J];
 #pragma unroll
-    for (int i = 0; i < B2_J; ++i) bv[i] = beta[b2_j<EPS>(tid, i)];
+    for (int i = 0; i < B2_J; ++i) bv[i] = beta[blk_j<EPS, B2_J>(tid, i)];
     b2_ab_column<LP>(tb, bf, c, cw, tid, bv, smem);
 }
 
@@ -210,7 +165,7 @@ __global__ __launch_bounds__(B2G<LP>::THREADS, 4) void blk2_az(BlkTables tb, Amp
         const int t = tb.col_t[q];
         const int g0 = tb.gptr[t], ng = tb.gptr[t + 1] - g0;
         for (int m2 = 0; m2 < 2; ++m2) {
-            const int tl = b2_opaque(tid);
+            const int tl = opaque(tid);
             // rows of class m2: U[k1] = sum over k = k1 mod P of G[k] conj(w_N2^(m2 k));
             // at most two slots (k1, k1 + P) share a row, and two float additions
             // onto a zero commute, so the atomic sum is deterministic.  The thread's
@@ -223,7 +178,7 @@ __global__ __launch_bounds__(B2G<LP>::THREADS, 4) void blk2_az(BlkTables tb, Amp
                 kp[e] = tb.gk[g0 + g];
                 vp[e] = gcw[g0 + g];
             }
-            b2_clear<LP>(smem, tl);
+            blk_clear<B2G<LP>::THREADS, B2G<LP>::IMG>(smem, tl);
             __syncthreads();
             auto row = [&](int k, cx<float> v) {
                 if (m2) {
@@ -246,13 +201,13 @@ __global__ __launch_bounds__(B2G<LP>::THREADS, 4) void blk2_az(BlkTables tb, Amp
             b2_pos_load<LP>(tb, t, m2, tl, pv);
 #pragma unroll
             for (int i = 0; i < B2_J; ++i)  // (the other class's entries read the zero trash slot)
-                u[i] += dr[b2_pos(pv, i)];
+                u[i] += dr[blk_pos(pv, i)];
             __syncthreads();
         }
     }
     // ---- sections of the column block (sparc.py:972, :429-432, :485-487), one
     // at a time: s = beta + tau u, x = s / tau, beta = exp(x - max) / sum, MAP =
-    // first index of max s.  A wavefront owns whole sections (b2_j).
+    // first index of max s.  A wavefront owns whole sections (blk_j).
     const int lane = tid & 63, wv = tid >> 6;
     constexpr int eps = EPS, spw = 2048 / (64 * EPS);
     const int nsec = tb.Mc / tb.M;
@@ -282,16 +237,16 @@ __global__ __launch_bounds__(B2G<LP>::THREADS, 4) void blk2_az(BlkTables tb, Amp
                 arg = lane * eps + e;
             }
         }
-        xm = b2_wave_max(xm);
-        const float gm = b2_wave_max(sm);
-        arg = b2_wave_min(sm == gm ? arg : 0x7fffffff);
+        xm = wave_max(xm);
+        const float gm = wave_max(sm);
+        arg = wave_min(sm == gm ? arg : 0x7fffffff);
         float dn = 0.f;
 #pragma unroll
         for (int e = 0; e < eps; ++e) {
             x[e] = __builtin_amdgcn_exp2f(x[e] - xm);
             dn += x[e];
         }
-        dn = b2_wave_sum(dn);
+        dn = wave_sum(dn);
         const float idn = 1.0f / dn;
         const int truth = bf.true_idx ? bf.true_idx[(size_t)cw * tb.L + l0 + ls] : -1;
         float ss = 0.f, se = 0.f;
@@ -304,8 +259,8 @@ __global__ __launch_bounds__(B2G<LP>::THREADS, 4) void blk2_az(BlkTables tb, Amp
             ss += b * b;
             se += dl * dl;
         }
-        ss = b2_wave_sum(ss);
-        se = b2_wave_sum(se);
+        ss = wave_sum(ss);
+        se = wave_sum(se);
         if (lane == 0) {
             const size_t o = (size_t)cw * tb.L + l0 + ls;
             bf.sec_sumsq[o] = (double)ss;
@@ -324,12 +279,9 @@ __global__ __launch_bounds__(B2G<LP>::THREADS, 4) void blk2_az(BlkTables tb, Amp
 
 template <int LP, int EPS>
 static int blk2_set_attrs(size_t lds) {
-    static size_t done = 0;
-    if (done >= lds) return SG_OK;
-    SG_HIP(hipFuncSetAttribute((const void *)blk2_ab<LP, EPS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SG_HIP(hipFuncSetAttribute((const void *)blk2_az<LP, EPS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    done = lds;
-    return SG_OK;
+    static size_t done_ab = 0, done_az = 0;
+    SG_TRY(set_max_lds((const void *)blk2_ab<LP, EPS>, lds, &done_ab));
+    return set_max_lds((const void *)blk2_az<LP, EPS>, lds, &done_az);
 }
 
 // section size M = 64 EPS, 64 <= M <= 2048

@@ -34,27 +34,6 @@
 namespace sg {
 namespace {
 
-__device__ __forceinline__ double cw_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double cw_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double cblock_sum(double v, double *red) {
-    v = cw_sum(v);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < nw; ++w) t += red[w];
-    return t;
-}
-
 // ------------------------------------------------------------------ pass A
 // INV = false: input beta of the transform's column block scattered by order1;
 // INV = true: input z / phi of its row block scattered by order0.
@@ -203,7 +182,7 @@ __device__ __forceinline__ void map_update(int K, const cxd *__restrict__ c, cxd
 }
 // the section's first maximum over the wavefront; entry e lives on lane e & 63
 __device__ __forceinline__ void map_finish(int K, const MapBest &b, int *idx, int *sym) {
-    const double g = cw_max(b.v);
+    const double g = wave_max(b.v);
     int cand = (b.flat != 0x7fffffff && b.v == g) ? b.flat : 0x7fffffff;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
@@ -249,7 +228,7 @@ __global__ __launch_bounds__(256) void camp_eta(CampTables tb, CampBufs bf) {
         m = fmax(m, psk_shift(K, cs, x));
         map_update(K, cs, s, e, mb);
     }
-    m = cw_max(m);
+    m = wave_max(m);
     int midx, msym;
     map_finish(K, mb, &midx, &msym);
     double den = 0.0;
@@ -260,7 +239,7 @@ __global__ __launch_bounds__(256) void camp_eta(CampTables tb, CampBufs bf) {
         beta[e] = top;
         den += dn;
     }
-    den = cw_sum(den);
+    den = wave_sum(den);
     const int truth = bf.true_idx ? bf.true_idx[(size_t)cw * tb.L + l] : -1;
     cxd tv{1.0, 0.0};
     if (K > 1 && bf.true_sym && truth >= 0) tv = cs[bf.true_sym[(size_t)cw * tb.L + l]];
@@ -273,8 +252,8 @@ __global__ __launch_bounds__(256) void camp_eta(CampTables tb, CampBufs bf) {
         const double dx = b.x - (e == truth ? tv.x : 0.0), dy = b.y - (e == truth ? tv.y : 0.0);
         se += dx * dx + dy * dy;
     }
-    ss = cw_sum(ss);
-    se = cw_sum(se);
+    ss = wave_sum(ss);
+    se = wave_sum(se);
     if (lane == 0) {
         const size_t o = (size_t)cw * tb.L + l;
         bf.sec_sumsq[o] = ss;
@@ -349,7 +328,7 @@ __global__ __launch_bounds__(1024) void camp_control(CampTables tb, CampBufs bf,
             for (int r = 0; r < Lr; ++r) {
                 double acc = 0.0;
                 for (int i = r * tb.Mr + tid; i < (r + 1) * tb.Mr; i += blockDim.x) acc += z[i].x * z[i].x + z[i].y * z[i].y;
-                acc = cblock_sum(acc, red);
+                acc = block_sum(acc, red);
                 if (tid == 0) phi[r] = acc / (double)tb.Mr;
             }
         }
@@ -374,8 +353,8 @@ __global__ __launch_bounds__(1024) void camp_control(CampTables tb, CampBufs bf,
             a += bf.sec_sumsq[(size_t)cw * tb.L + l];
             e += bf.sec_err[(size_t)cw * tb.L + l];
         }
-        a = cblock_sum(a, red);
-        e = cblock_sum(e, red);
+        a = block_sum(a, red);
+        e = block_sum(e, red);
         if (tid == 0) {
             psi[c] = 1.0 - a / denom;
             nmse[(size_t)(t + 1) * Lc + c] = e / denom;
@@ -426,7 +405,7 @@ __global__ __launch_bounds__(256) void psk_mmse_kernel(const cxd *__restrict__ x
     const cxd *xs = x + (size_t)l * M;
     double m = -INFINITY;
     for (int e = lane; e < M; e += 64) m = fmax(m, psk_shift(K, cs, xs[e]));
-    m = cw_max(m);
+    m = wave_max(m);
     double den = 0.0;
     for (int e = lane; e < M; e += 64) {
         cxd top;
@@ -435,7 +414,7 @@ __global__ __launch_bounds__(256) void psk_mmse_kernel(const cxd *__restrict__ x
         out[(size_t)l * M + e] = top;
         den += dn;
     }
-    den = cw_sum(den);
+    den = wave_sum(den);
     for (int e = lane; e < M; e += 64) {
         cxd &o = out[(size_t)l * M + e];
         o = cxd{o.x / den, o.y / den};

@@ -28,24 +28,6 @@
 namespace sg {
 namespace {
 
-// hides the thread index from loop-invariant code motion, so the FFT's LDS
-// addresses are recomputed per class instead of held across the class loop
-__device__ __forceinline__ int cw_opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-__device__ __forceinline__ double cw_block_sum(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < CW_THREADS / 64; ++w) t += red[w];
-    return t;
-}
-
 constexpr int CW_LOG2P = 13, CW_P = 1 << CW_LOG2P, CW_EPT = CW_P / CW_THREADS;
 constexpr int CW_SN = 9;   // class entries per thread (host: largest class <= CW_SN * 1024)
 constexpr int CW_CO = 8;   // output rows per thread (host: n <= CW_CO * 1024)
@@ -66,14 +48,6 @@ __device__ __forceinline__ cx<float> cw_w(const CwTables &tb, uint32_t j) {
 constexpr int cw_nstages() { return 4; }
 constexpr int cw_radix(int st) { return st == 0 ? 16 : 8; }
 constexpr int cw_log2ns(int st) { return st == 0 ? 0 : 4 + 3 * (st - 1); }
-
-// lanes 32..63 of a <-> lanes 0..31 of b (v_permlane32_swap, no LDS)
-__device__ __forceinline__ void cw_swap32(cx<float> &a, cx<float> &b) {
-    const auto rx = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.x), __float_as_uint(b.x), false, false);
-    const auto ry = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.y), __float_as_uint(b.y), false, false);
-    a = {__uint_as_float(rx[0]), __uint_as_float(ry[0])};
-    b = {__uint_as_float(rx[1]), __uint_as_float(ry[1])};
-}
 
 // First Stockham stage at radix 16 (Ns = 1, no twiddles) with 8 values per
 // thread: butterfly j = 32 w + (l & 31) of wavefront w is shared by lanes l
@@ -98,7 +72,7 @@ __device__ __forceinline__ void cw_stage0_r16(cx<float> *d, int tid, uint32_t ms
         v[jj] = {__uint_as_float(__float_as_uint(v[jj].x) & mx), __uint_as_float(__float_as_uint(v[jj].y) & my)};
     }
 #pragma unroll
-    for (int jj = 0; jj < 4; ++jj) cw_swap32(v[jj], v[jj + 4]);  // lane half H: x[J], x[8 + J], J = jj + 4 H
+    for (int jj = 0; jj < 4; ++jj) swap32(v[jj], v[jj + 4]);  // lane half H: x[J], x[8 + J], J = jj + 4 H
     {
         constexpr float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, r2 = 0.70710678118654752440f;
         const cx<float> w16[4] = {{1.f, 0.f}, {c1, INV ? s1 : -s1}, {r2, INV ? r2 : -r2}, {s1, INV ? c1 : -c1}};
@@ -111,7 +85,7 @@ __device__ __forceinline__ void cw_stage0_r16(cx<float> *d, int tid, uint32_t ms
         }
     }
 #pragma unroll
-    for (int jj = 0; jj < 4; ++jj) cw_swap32(v[jj], v[jj + 4]);  // lane half p: y_p[0..7]
+    for (int jj = 0; jj < 4; ++jj) swap32(v[jj], v[jj + 4]);  // lane half p: y_p[0..7]
     dft8<float, INV>(v);                                         // v[q] = X_j[2 q + H]
     __syncthreads();
 #pragma unroll
@@ -255,7 +229,7 @@ __global__ __launch_bounds__(CW_THREADS) void cw_iter(CwTables tb, RegBufs<float
         };
         if constexpr (early) gather_stats();
         for (int m2 = 0; m2 < tb.Q; ++m2) {
-            const int tl = cw_opaque(tid);
+            const int tl = opaque(tid);
             if (m2 == 2) CW_TP(8);
             if constexpr (!early) gather_stats();  // (after the previous class's closing barrier)
             if (m2 == 2) CW_TP(9);
@@ -269,7 +243,7 @@ __global__ __launch_bounds__(CW_THREADS) void cw_iter(CwTables tb, RegBufs<float
             cw_fft_from<false, 0>(d, tl, cmk);
             if (m2 == 2) CW_TP(11);
             if (m2 + 1 < tb.Q) {  // the next class in flight under the accumulation
-                const int tn = cw_opaque(tl);
+                const int tn = opaque(tl);
                 q0 = tb.cls_ptr[m2 + 1];
                 q1 = tb.cls_ptr[m2 + 2];
 #pragma unroll
@@ -367,7 +341,7 @@ __global__ __launch_bounds__(CW_THREADS) void cw_iter(CwTables tb, RegBufs<float
     }
     double phi;
     if (sum_z) {
-        phi = cw_block_sum(acc, red) / (double)tb.n;  // sparc.py:949-955
+        phi = block_sum<CW_THREADS / 64>(acc, red) / (double)tb.n;  // sparc.py:949-955
     } else {
         __syncthreads();
         phi = pr.awgn_var + g;
@@ -450,7 +424,7 @@ __global__ __launch_bounds__(CW_THREADS) void cw_iter(CwTables tb, RegBufs<float
         }
     }
     for (int m2 = 0; m2 < tb.Q; ++m2) {
-        const int tl = cw_opaque(tid);
+        const int tl = opaque(tid);
         if (m2 == 2) CW_TP(16);
         // the rows' image values (the same every class; reloaded, not held across the loop)
         const uint32_t rmk = tb.cmask[tb.Q * CW_THREADS + tl];
@@ -587,8 +561,8 @@ __global__ __launch_bounds__(CW_THREADS) void cw_iter(CwTables tb, RegBufs<float
             }
         }
     }
-    a = cw_block_sum(a, red);
-    er = cw_block_sum(er, red);
+    a = block_sum<CW_THREADS / 64>(a, red);
+    er = block_sum<CW_THREADS / 64>(er, red);
     if (tid == 0) {
         double *nmse = sc.nmse + (size_t)cw * pr.t_max;
         const double denom = (double)tb.L;

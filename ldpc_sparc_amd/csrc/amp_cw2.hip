@@ -70,11 +70,6 @@ constexpr int C2_RC = 4;
 constexpr double C2_LOG2E = 1.4426950408889634074;
 __device__ __forceinline__ float c2_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-__device__ __forceinline__ int c2_opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
 // w_N2^j = exp(-2 pi i j / N2) from the hardware sine / cosine (revolutions;
 // (j mod N2) / N2 is exact in f32 for N2 <= 2^19)
 __device__ __forceinline__ cx<float> c2_w(const Cw2Tables &tb, uint32_t j) {
@@ -178,14 +173,6 @@ __device__ __forceinline__ void c2_dft16(c2f *a) {
     }
 }
 
-// lanes 32..63 of a <-> lanes 0..31 of b (v_permlane32_swap, no LDS)
-__device__ __forceinline__ void c2_swap32(c2f &a, c2f &b) {
-    const auto rx = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.x), __float_as_uint(b.x), false, false);
-    const auto ry = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.y), __float_as_uint(b.y), false, false);
-    a = c2f{__uint_as_float(rx[0]), __uint_as_float(ry[0])};
-    b = c2f{__uint_as_float(rx[1]), __uint_as_float(ry[1])};
-}
-
 // First Stockham stage at radix 32 (Ns = 1, no twiddles), 16 values per
 // thread: butterfly j = 32 w + (l & 31) of wavefront w is shared by lanes l
 // and l ^ 32, lane half H holding inputs m = 16 H + jj (x[j + 256 m]).  Two
@@ -213,7 +200,7 @@ __device__ __forceinline__ void c2_stage0_r32(int tid, uint32_t msk) {
                     __uint_as_float(__float_as_uint(v[jj].y) & (uint32_t)my)};
     }
 #pragma unroll
-    for (int jj = 0; jj < 8; ++jj) c2_swap32(v[jj], v[jj + 8]);  // lane half H: x[J], x[16 + J], J = jj + 8 H
+    for (int jj = 0; jj < 8; ++jj) swap32(v[jj], v[jj + 8]);  // lane half H: x[J], x[16 + J], J = jj + 8 H
     {
         // w32^J = cos(2 pi J / 32) -+ i sin(2 pi J / 32) for J = jj + 8 H (forward -, inverse +);
         // w32^(jj + 8) = -i w32^jj
@@ -233,7 +220,7 @@ __device__ __forceinline__ void c2_stage0_r32(int tid, uint32_t msk) {
         }
     }
 #pragma unroll
-    for (int jj = 0; jj < 8; ++jj) c2_swap32(v[jj], v[jj + 8]);  // lane half p: sub-sequence p, J = 0..15
+    for (int jj = 0; jj < 8; ++jj) swap32(v[jj], v[jj + 8]);  // lane half p: sub-sequence p, J = 0..15
     c2_dft16<INV>(v);                                            // v[q] = X_j[2 q + H]
     __syncthreads();
     c2lds *dst = c2_at(33 * j + H);  // c2pos(32 j + 2 q + H) = 33 j + 2 q + H
@@ -289,8 +276,8 @@ __device__ __forceinline__ void c2_stage_r16(int tid) {
 template <bool INV>
 __device__ __forceinline__ void c2_fft(int tid, uint32_t msk) {
     c2_stage0_r32<INV>(tid, msk);
-    c2_stage_r16<INV, 5>(c2_opaque(tid));
-    c2_stage_r16<INV, 9>(c2_opaque(tid));
+    c2_stage_r16<INV, 5>(opaque(tid));
+    c2_stage_r16<INV, 9>(opaque(tid));
 }
 
 }  // namespace
@@ -332,34 +319,7 @@ __device__ __forceinline__ const int *c2_stage_cp(unsigned char *smem, const Cw2
 static_assert(C2_TW1 * 8 == C2_IMG_BYTES + 2 * 1024 * 4 + 16, "twiddle table after the trash slot");
 static_assert(CW2_TRASH == (C2_IMG_BYTES + 2 * 1024 * 4) / 4, "trash slot after the staged statistics");
 
-// Raw buffer resources: loads and stores address by a per-lane byte offset
-// plus a scalar one (no 64-bit address arithmetic on the vector ALUs), and
-// the hardware range check (offset >= bytes) returns 0 for loads and drops
-// stores -- the class slices' ragged ends need no clamps or branches.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t c2_rsrc(const void *p, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, bytes > 0 ? bytes : 0, 0x00020000);
-}
-__device__ __forceinline__ float c2_ldf(__amdgpu_buffer_rsrc_t r, int vo, int so) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0));
-}
-__device__ __forceinline__ uint32_t c2_ldu(__amdgpu_buffer_rsrc_t r, int vo, int so) {
-    return __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0);
-}
-// workgroup-uniform values (class bounds) in scalar registers: a buffer
-// resource built from them stays scalar (no waterfall loop)
-__device__ __forceinline__ int c2_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-// a thread's OT slot words of a thread-major [512][OTP] table, 16 bytes per load
-template <int OT>
-__device__ __forceinline__ void c2_ld_slots(__amdgpu_buffer_rsrc_t r, int tl, uint32_t *out) {
-    constexpr int OTP = cw2_otp(OT);
-#pragma unroll
-    for (int q = 0; q < OTP / 4; ++q) {
-        const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, 4 * OTP * tl, 16 * q, 0);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (4 * q + c < OT) out[4 * q + c] = v[c];
-    }
-}
+// (the class slices go through raw buffer resources, device_util.hpp: their ragged ends need no clamps)
 constexpr int C2_SN = C2_NC * C2_SC;  // class entries per thread
 
 
@@ -389,9 +349,9 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
     // a = 0, unused); the owned indices a and the rows' LDS byte addresses (host table rab) reloaded per
     // class from L1 (held across the transform they spill), in two rounds
     constexpr int OTP = cw2_otp(OT);
-    const __amdgpu_buffer_rsrc_t rk = c2_rsrc(tb.kat, 4 * OTP * C2_T);  // thread-major: OTP / 4 loads of 16 B
+    const __amdgpu_buffer_rsrc_t rk = buf_rsrc(tb.kat, 4 * OTP * C2_T);  // thread-major: OTP / 4 loads of 16 B
     auto acc_tables = [&](int tl, uint32_t *ka) {
-        c2_ld_slots<OT>(rk, tl, ka);
+        ld_slots<OT>(rk, tl, ka);
     };
     auto accumulate = [&](int m, const uint32_t *ka) {
 #pragma unroll
@@ -414,9 +374,9 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
     constexpr bool PL = OT <= 12;
     uint32_t kapf[PL ? OT : 1];
     for (int m2 = h * Qh; m2 < (h + 1) * Qh; ++m2) {
-        const int tl = c2_opaque(tid);
+        const int tl = opaque(tid);
         C2_TPC(0);
-        const int q0 = c2_uni(cpl[m2]), q1 = c2_uni(cpl[m2 + 1]);
+        const int q0 = uni(cpl[m2]), q1 = uni(cpl[m2 + 1]);
         // (at more than 12 outputs per thread the slice is requested after the accumulation: in flight
         // during it, it spills)
         if (!PL && m2 > h * Qh) {
@@ -429,12 +389,12 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
         uint32_t e[C2_SN];
         {  // every load of the class slice in one round trip; past the class's end s reads 0 and the
            // padded table points at the trash slot (sparc.py:429-432 below writes there harmlessly)
-            const __amdgpu_buffer_rsrc_t rs0 = c2_rsrc(s + q0, 4 * (q1 - q0));
-            const __amdgpu_buffer_rsrc_t re = c2_rsrc(tb.cls2 + (size_t)m2 * CW2_SLICE, 4 * CW2_SLICE);
+            const __amdgpu_buffer_rsrc_t rs0 = buf_rsrc(s + q0, 4 * (q1 - q0));
+            const __amdgpu_buffer_rsrc_t re = buf_rsrc(tb.cls2 + (size_t)m2 * CW2_SLICE, 4 * CW2_SLICE);
 #pragma unroll
             for (int i = 0; i < C2_SN; ++i) {
-                v[i] = c2_ldf(rs0, 4 * tl + 4 * i * C2_T, 0);
-                e[i] = c2_ldu(re, 4 * tl, 4 * i * C2_T);
+                v[i] = buf_ldf(rs0, 4 * tl + 4 * i * C2_T, 0);
+                e[i] = buf_ldu(re, 4 * tl, 4 * i * C2_T);
             }
         }
         // (requested before the scatter's stores: a later load would wait for them, vmcnt is in order)
@@ -444,7 +404,7 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
             __syncthreads();  // the image is read before the scatter overwrites it
         }
         C2_TPC(8);
-        const __amdgpu_buffer_rsrc_t rs = c2_rsrc(s + q0, 4 * (q1 - q0));
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(s + q0, 4 * (q1 - q0));
 #pragma unroll
         for (int c = 0; c < C2_NC; ++c) {  // beta = eta(s), sparc.py:429-432, scattered into the image and
                                            // stored over s for cw2_az (its beta_prev; past the end: dropped)
@@ -465,11 +425,11 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
         c2_fft<false>(tl, cmk);
         C2_SETPRIO(C2_PRIO_REST);
         C2_TPC(6);
-        if constexpr (PL) acc_tables(c2_opaque(tid), kapf);  // class-invariant: in flight across the loop edge
+        if constexpr (PL) acc_tables(opaque(tid), kapf);  // class-invariant: in flight across the loop edge
     }
     {
         uint32_t ka[OT];
-        acc_tables(c2_opaque(tid), ka);
+        acc_tables(opaque(tid), ka);
         accumulate((h + 1) * Qh - 1, ka);
     }
     C2_TP(11);
@@ -484,6 +444,8 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
 }
 
 // ---------------------------------------------------------------------------- control
+// (the wave count is read after the barriers here; block_sum of device_util.hpp reads it before them, which
+// compiles the control kernels differently, so this engine keeps its own form)
 __device__ __forceinline__ double c2_block_sum(double v, double *red) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -495,7 +457,7 @@ __device__ __forceinline__ double c2_block_sum(double v, double *red) {
     return t;
 }
 
-// two sums at once (one pair of barriers), each in c2_block_sum's order
+// two sums at once (one pair of barriers), each in c2_block_sum's order (as block_sum, device_util.hpp)
 __device__ __forceinline__ void c2_block_sum2(double &a, double &b, double *red) {
     for (int o = 32; o > 0; o >>= 1) {
         a += __shfl_xor(a, o, 64);
@@ -658,13 +620,13 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
     __syncthreads();  // the staged statistics
     C2_TP(42);
     for (int m2 = h * Qh; m2 < (h + 1) * Qh; ++m2) {
-        const int tl = c2_opaque(tid);
+        const int tl = opaque(tid);
         C2_TPC(32);
         const uint32_t rmk = tb.cmask[tb.Q * C2_T + tl];
         // the class slice (entries' image positions, beta_prev), requested before the transform and
         // consumed after it, so its HBM latency hides behind the transform
-        const int q0 = c2_uni(cpl[m2]), q1 = c2_uni(cpl[m2 + 1]);
-        const __amdgpu_buffer_rsrc_t rs = c2_rsrc(s + q0, 4 * (q1 - q0));  // past the class's end: reads 0,
+        const int q0 = uni(cpl[m2]), q1 = uni(cpl[m2 + 1]);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(s + q0, 4 * (q1 - q0));  // past the class's end: reads 0,
                                                                            // stores dropped
         // (at more than 12 outputs per thread the slice stays out of flight during the rows and the
         // transform: it would spill)
@@ -674,14 +636,14 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
         auto load_slice = [&]() {  // the entries' positions and beta_prev
             // the entries' image positions two per word (clsp: entries i and i + 9 of the thread), half the
             // table loads and bytes of the full words (the sections are not needed here)
-            const __amdgpu_buffer_rsrc_t re = c2_rsrc(tb.clsp + (size_t)m2 * (CW2_SLICE / 2), 2 * CW2_SLICE);
+            const __amdgpu_buffer_rsrc_t re = buf_rsrc(tb.clsp + (size_t)m2 * (CW2_SLICE / 2), 2 * CW2_SLICE);
 #pragma unroll
             for (int i = 0; i < C2_SN / 2; ++i) {
-                const uint32_t w = c2_ldu(re, 4 * tl, 4 * i * C2_T);
+                const uint32_t w = buf_ldu(re, 4 * tl, 4 * i * C2_T);
                 e[i] = w;  // (packed: entries i and i + 9, unpacked at the gather -- 9 VGPRs across the transform)
             }
 #pragma unroll
-            for (int i = 0; i < C2_SN; ++i) v[i] = c2_ldf(rs, 4 * tl + 4 * i * C2_T, 0);  // (t = 0: unused)
+            for (int i = 0; i < C2_SN; ++i) v[i] = buf_ldf(rs, 4 * tl + 4 * i * C2_T, 0);  // (t = 0: unused)
         };
         {  // rows r and P - r of each owned pair: sum of al v conj(W) / be v W over its outputs
             // (v = z / phi).  Polar form (build_cw2): al conj(W) = |al| (cos x, sin x) and be W = |be| (sin x,
@@ -691,14 +653,14 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
             // sums) and writes both rows (invalid slots: zero scale).  (Slot words and v reloaded per class from
             // L1 / L2: held across the transform, or loaded one class ahead, they spill.)
             constexpr int CH = VZH ? OT : (OT + 1) / 2;  // slots per load round (one round up to 12 per thread)
-            const __amdgpu_buffer_rsrc_t rv2 = c2_rsrc(vz, 8 * OTP * C2_T),  // (the slot-major rounds')
-                                         rk = c2_rsrc(VZH ? tb.kat : tb.ka, 4 * OTP * C2_T);
+            const __amdgpu_buffer_rsrc_t rv2 = buf_rsrc(vz, 8 * OTP * C2_T),  // (the slot-major rounds')
+                                         rk = buf_rsrc(VZH ? tb.kat : tb.ka, 4 * OTP * C2_T);
             uint32_t kall[VZH ? OT : 1];
             c2f vall[VZH ? OT : 1];
             if constexpr (VZH) {  // one load round, 16-byte loads (thread-major): slot words, z / phi (4 B per
                                   // slot) and the plan's (|al|, |be|)
-                c2_ld_slots<OT>(rk, tl, kall);
-                const __amdgpu_buffer_rsrc_t rv = c2_rsrc(vz, 4 * OTP * C2_T), rg = c2_rsrc(tb.gmt, 8 * OTP * C2_T);
+                ld_slots<OT>(rk, tl, kall);
+                const __amdgpu_buffer_rsrc_t rv = buf_rsrc(vz, 4 * OTP * C2_T), rg = buf_rsrc(tb.gmt, 8 * OTP * C2_T);
                 float v1[OTP];
 #pragma unroll
                 for (int q = 0; q < OTP / 4; ++q) {
@@ -728,7 +690,7 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
                         ka[i] = kall[j];
                         vv[i] = vall[j];
                     } else {  // (two load rounds: slot-major, each load a contiguous run of the wavefront)
-                        ka[i] = c2_ldu(rk, 4 * tl, 4 * j * C2_T);
+                        ka[i] = buf_ldu(rk, 4 * tl, 4 * j * C2_T);
                         const auto w = __builtin_amdgcn_raw_buffer_load_b64(rv2, 8 * tl, 8 * j * C2_T, 0);
                         vv[i] = c2f{__uint_as_float(w[0]), __uint_as_float(w[1])};
                     }
@@ -769,7 +731,7 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
         int sa[2], sb[2];  // the sections' segments of the class (in flight during the transform; sections
                            // past Lb read 0 as their end: empty)
         {
-            const __amdgpu_buffer_rsrc_t rg = c2_rsrc(tb.seg + (size_t)m2 * (Lb + 1), 2 * (Lb + 1));
+            const __amdgpu_buffer_rsrc_t rg = buf_rsrc(tb.seg + (size_t)m2 * (Lb + 1), 2 * (Lb + 1));
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const int sec = tl + k * C2_T;

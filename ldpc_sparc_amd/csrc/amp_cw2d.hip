@@ -52,7 +52,6 @@ constexpr int D_P = 8192;
 constexpr int D_SC = 9, D_NC = 2, D_SN = D_SC * D_NC;  // 18 class entries per thread (CW2_SLICE / 512)
 static_assert(D_SN * D_T == CW2_SLICE, "class slices of 18 entries per thread");
 
-typedef double d2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) d2 d2lds;
 typedef __attribute__((address_space(3))) double dlds;
 // complex element pos of the LDS (16 bytes each); the kernels have no static LDS
@@ -70,11 +69,6 @@ constexpr int D_TW1 = D_TRASH + 1;          // [15][32] w_512^(r k) of the first
 constexpr int D_CP_BYTES = 16 * (D_TW1 + 15 * 32);
 constexpr int D_LDS_BYTES = D_CP_BYTES + 4 * 72;  // + the class pointers (Q + 1 <= 72)
 static_assert(D_LDS_BYTES <= 160 * 1024, "LDS budget");
-
-__device__ __forceinline__ int d_opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
 
 __device__ __forceinline__ d2 dmul(d2 a, d2 w) {
     return d2{__builtin_fma(a.x, w.x, -(a.y * w.y)), __builtin_fma(a.x, w.y, a.y * w.x)};
@@ -137,20 +131,6 @@ __device__ __forceinline__ void d_dft16(d2 *a) {
     }
 }
 
-// lanes 32..63 of a <-> lanes 0..31 of b, every dword of the two doubles (v_permlane32_swap)
-__device__ __forceinline__ void d_swap32(d2 &a, d2 &b) {
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    u4 ua = __builtin_bit_cast(u4, a), ub = __builtin_bit_cast(u4, b);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const auto r = __builtin_amdgcn_permlane32_swap(ua[c], ub[c], false, false);
-        ua[c] = r[0];
-        ub[c] = r[1];
-    }
-    a = __builtin_bit_cast(d2, ua);
-    b = __builtin_bit_cast(d2, ub);
-}
-
 // First Stockham stage at radix 32, the read pattern of amp_cw2.hip c2_stage0_r32 (its masks, host
 // table cmask, say which image values this transform wrote; the stale ones read as zero)
 template <bool INV>
@@ -173,7 +153,7 @@ __device__ __forceinline__ void d_stage0_r32(int tid, uint32_t msk) {
         v[jj] = __builtin_bit_cast(d2, u);
     }
 #pragma unroll
-    for (int jj = 0; jj < 8; ++jj) d_swap32(v[jj], v[jj + 8]);  // lane half H: x[J], x[16 + J], J = jj + 8 H
+    for (int jj = 0; jj < 8; ++jj) swap32(v[jj], v[jj + 8]);  // lane half H: x[J], x[16 + J], J = jj + 8 H
     {
         constexpr double co[8] = {1.0, 0.98078528040323044913, 0.92387953251128675613, 0.83146961230254523708,
                                   0.70710678118654752440, 0.55557023301960222474, 0.38268343236508977173,
@@ -191,7 +171,7 @@ __device__ __forceinline__ void d_stage0_r32(int tid, uint32_t msk) {
         }
     }
 #pragma unroll
-    for (int jj = 0; jj < 8; ++jj) d_swap32(v[jj], v[jj + 8]);  // lane half p: sub-sequence p
+    for (int jj = 0; jj < 8; ++jj) swap32(v[jj], v[jj + 8]);  // lane half p: sub-sequence p
     d_dft16<INV>(v);                                             // v[q] = X_j[2 q + H]
     __syncthreads();
     d2lds *dst = d_at(33 * j + H);  // c2pos(32 j + 2 q + H) = 33 j + 2 q + H
@@ -245,12 +225,12 @@ __device__ __forceinline__ void d_fft(int tid, uint32_t msk, const double *twp) 
     const d2 *tp = reinterpret_cast<const d2 *>(twp);
     d2 w1 = tp[tid], w4 = tp[4 * tid];
     d_stage0_r32<INV>(tid, msk);
-    d_stage_r16<INV, 5>(d_opaque(tid), w1, w4);
+    d_stage_r16<INV, 5>(opaque(tid), w1, w4);
     if (INV) {
         w1 = dconj(w1);
         w4 = dconj(w4);
     }
-    d_stage_r16<INV, 9>(d_opaque(tid), w1, w4);
+    d_stage_r16<INV, 9>(opaque(tid), w1, w4);
 }
 
 // the first radix-16 stage's table w_512^(r k) = w_8192^(16 (r k mod 512)), r = 1..15, k < 32
@@ -268,35 +248,6 @@ __device__ __forceinline__ const int *d_stage_cp(unsigned char *smem, const Cw2d
     int *cp = reinterpret_cast<int *>(smem + D_CP_BYTES);
     for (int i = tid; i <= tb.Q; i += D_T) cp[i] = tb.cls_ptr[i];
     return cp;
-}
-
-// raw buffer resources (amp_cw2.hip c2_rsrc): out-of-range loads read 0, stores are dropped
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t d_rsrc(const void *p, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, bytes > 0 ? bytes : 0, 0x00020000);
-}
-__device__ __forceinline__ double d_ldd(__amdgpu_buffer_rsrc_t r, int vo, int so) {
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0));
-}
-__device__ __forceinline__ d2 d_ld2(__amdgpu_buffer_rsrc_t r, int vo, int so) {
-    return __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, 0));
-}
-__device__ __forceinline__ void d_std(__amdgpu_buffer_rsrc_t r, double v, int vo, int so) {
-    typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), r, vo, so, 0);
-}
-__device__ __forceinline__ int d_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// a thread's OT slot words of a thread-major [512][OTP] table, 16 bytes per load
-template <int OT>
-__device__ __forceinline__ void d_ld_slots(__amdgpu_buffer_rsrc_t r, int tl, uint32_t *out) {
-    constexpr int OTP = cw2_otp(OT);
-#pragma unroll
-    for (int q = 0; q < OTP / 4; ++q) {
-        const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, 4 * OTP * tl, 16 * q, 0);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (4 * q + c < OT) out[4 * q + c] = v[c];
-    }
 }
 
 // x when i < n, else the double whose high word is fill (low word 0), by bit masks: written as a compare
@@ -345,7 +296,7 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_ab(Cw2dTables tb, RegBufs<double>
     d_tw1_init<false>(tid, tb.twp);
     const int *cpl = d_stage_cp(smem, tb, tid);
     __syncthreads();
-    const __amdgpu_buffer_rsrc_t rk = d_rsrc(tb.ka, 4 * OT * D_T), rS = d_rsrc(tb.sa, 16 * OT * D_T);
+    const __amdgpu_buffer_rsrc_t rk = buf_rsrc(tb.ka, 4 * OT * D_T), rS = buf_rsrc(tb.sa, 16 * OT * D_T);
     // the thread's slot words and S = w_N2^a, slot-major: every load a contiguous run of the wavefront's
     // lanes (thread-major rows of 12 complex doubles put each lane on its own cache lines:
     // profiles/r05_f64_ablation.txt); class-invariant, so requested after each transform and in flight
@@ -356,7 +307,7 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_ab(Cw2dTables tb, RegBufs<double>
 #pragma unroll
         for (int j = 0; j < OT; ++j) {
             ka[j] = __builtin_amdgcn_raw_buffer_load_b32(rk, 4 * tl, 4 * j * D_T, 0);
-            S[j] = d_ld2(rS, 16 * tl, 16 * j * D_T);
+            S[j] = buf_ld2(rS, 16 * tl, 16 * j * D_T);
         }
     };
     // Horner step of class m's transform (still in the image) for every owned output
@@ -376,17 +327,17 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_ab(Cw2dTables tb, RegBufs<double>
         }
     };
     for (int m2 = mhi - 1; m2 >= mlo; --m2) {
-        const int tl = d_opaque(tid);
-        const int q0 = d_uni(cpl[m2]), q1 = d_uni(cpl[m2 + 1]);
+        const int tl = opaque(tid);
+        const int q0 = uni(cpl[m2]), q1 = uni(cpl[m2 + 1]);
         const bool prev = m2 < mhi - 1;
         double v[D_SN];
         uint32_t e[D_SN];
         {
-            const __amdgpu_buffer_rsrc_t rb = d_rsrc(beta + q0, 8 * (q1 - q0));  // past the class's end: 0
-            const __amdgpu_buffer_rsrc_t re = d_rsrc(tb.cls2 + (size_t)m2 * CW2_SLICE, 4 * CW2_SLICE);
+            const __amdgpu_buffer_rsrc_t rb = buf_rsrc(beta + q0, 8 * (q1 - q0));  // past the class's end: 0
+            const __amdgpu_buffer_rsrc_t re = buf_rsrc(tb.cls2 + (size_t)m2 * CW2_SLICE, 4 * CW2_SLICE);
 #pragma unroll
             for (int i = 0; i < D_SN; ++i) {
-                v[i] = d_ldd(rb, 8 * tl + 8 * i * D_T, 0);
+                v[i] = buf_ldd(rb, 8 * tl + 8 * i * D_T, 0);
                 e[i] = __builtin_amdgcn_raw_buffer_load_b32(re, 4 * tl, 4 * i * D_T, 0);
             }
         }
@@ -400,11 +351,11 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_ab(Cw2dTables tb, RegBufs<double>
             *d_re(e[i] & 0xffffu) = v[i];
         __syncthreads();
         d_fft<false>(tl, cmk, tb.twp);
-        acc_tables(d_opaque(tid));
+        acc_tables(opaque(tid));
     }
     accumulate();
     // this half's part of the forward output Re(c1 H[a] + c2 conj H[b]), H = S^mlo (Horner sums)
-    const __amdgpu_buffer_rsrc_t rc = d_rsrc(tb.cf, 32 * OT * D_T);
+    const __amdgpu_buffer_rsrc_t rc = buf_rsrc(tb.cf, 32 * OT * D_T);
     double *xr = tb.xr + ((size_t)cw * 2 + h) * OT * D_T;
 #pragma unroll
     for (int j = 0; j < OT; ++j) {
@@ -414,12 +365,14 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_ab(Cw2dTables tb, RegBufs<double>
             ha = dmul(ha, w0);
             hb = dmul(hb, w0);
         }
-        const d2 c1 = d_ld2(rc, 32 * tid, 32 * j * D_T), c2 = d_ld2(rc, 32 * tid, 32 * j * D_T + 16);
+        const d2 c1 = buf_ld2(rc, 32 * tid, 32 * j * D_T), c2 = buf_ld2(rc, 32 * tid, 32 * j * D_T + 16);
         xr[j * D_T + tid] = (c1.x * ha.x - c1.y * ha.y) + (c2.x * hb.x - c2.y * hb.y);
     }
 }
 
 // ---------------------------------------------------------------------------- control
+// (the wave count is read after the barriers here; block_sum of device_util.hpp reads it before them, which
+// compiles the control kernels differently, so this engine keeps its own form)
 __device__ __forceinline__ double d_block_sum(double v, double *red) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -532,15 +485,15 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_az(Cw2dTables tb, RegBufs<double>
     const double *beta = tb.beta + (size_t)cw * tb.LM;
     const double *vz = tb.vz + (size_t)cw * OT * D_T;
     const int Qh = tb.Q >> 1, mlo = h * Qh, mhi = mlo + Qh;
-    const __amdgpu_buffer_rsrc_t rS = d_rsrc(tb.sa, 16 * OT * D_T);
+    const __amdgpu_buffer_rsrc_t rS = buf_rsrc(tb.sa, 16 * OT * D_T);
     d2 W[OT];  // w_N2^(m a) of the class, rotated by S = w_N2^a per class
 #pragma unroll
-    for (int j = 0; j < OT; ++j) W[j] = d_pow(d_ld2(rS, 16 * tid, 16 * j * D_T), mlo);
+    for (int j = 0; j < OT; ++j) W[j] = d_pow(buf_ld2(rS, 16 * tid, 16 * j * D_T), mlo);
     d_tw1_init<true>(tid, tb.twp);
     const int *cpl = d_stage_cp(smem, tb, tid);
     __syncthreads();
-    const __amdgpu_buffer_rsrc_t rv = d_rsrc(vz, 8 * OT * D_T), rk = d_rsrc(tb.ka, 4 * OT * D_T),
-                                 rg = d_rsrc(tb.gf, 32 * OT * D_T);
+    const __amdgpu_buffer_rsrc_t rv = buf_rsrc(vz, 8 * OT * D_T), rk = buf_rsrc(tb.ka, 4 * OT * D_T),
+                                 rg = buf_rsrc(tb.gf, 32 * OT * D_T);
     // the rows' slot words, z / phi and S are class-invariant, but requested at the rows of every class: held
     // across the loop they are 84 loop-carried VGPRs, 68 spilled (Az 1.05 -> 1.93 ms per launch)
     uint32_t kall[OT];
@@ -550,14 +503,14 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_az(Cw2dTables tb, RegBufs<double>
 #pragma unroll
         for (int j = 0; j < OT; ++j) {
             kall[j] = __builtin_amdgcn_raw_buffer_load_b32(rk, 4 * tl, 4 * j * D_T, 0);
-            vall[j] = d_ldd(rv, 8 * tl, 8 * j * D_T);
-            S[j] = d_ld2(rS, 16 * tl, 16 * j * D_T);
+            vall[j] = buf_ldd(rv, 8 * tl, 8 * j * D_T);
+            S[j] = buf_ld2(rS, 16 * tl, 16 * j * D_T);
         }
     };
     for (int m2 = mlo; m2 < mhi; ++m2) {
-        const int tl = d_opaque(tid);
+        const int tl = opaque(tid);
         const uint32_t rmk = tb.cmask[tb.Q * D_T + tl];
-        const int q0 = d_uni(cpl[m2]), q1 = d_uni(cpl[m2 + 1]);
+        const int q0 = uni(cpl[m2]), q1 = uni(cpl[m2 + 1]);
         {
             rows_tables(tl);
             // rows r and P - r of each owned pair: sums of al v conj(W) / be v W over its outputs (v = z / phi),
@@ -571,8 +524,8 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_az(Cw2dTables tb, RegBufs<double>
 #pragma unroll
                 for (int i = 0; i < CH; ++i) {
                     if (j0 + i >= OT) break;
-                    al[i] = d_ld2(rg, 32 * tl, 32 * (j0 + i) * D_T);
-                    be[i] = d_ld2(rg, 32 * tl, 32 * (j0 + i) * D_T + 16);
+                    al[i] = buf_ld2(rg, 32 * tl, 32 * (j0 + i) * D_T);
+                    be[i] = buf_ld2(rg, 32 * tl, 32 * (j0 + i) * D_T + 16);
                 }
 #pragma unroll
                 for (int i = 0; i < CH; ++i) {
@@ -596,22 +549,22 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_az(Cw2dTables tb, RegBufs<double>
         double v[D_SN];
         uint32_t e[D_SN];
         {
-            const __amdgpu_buffer_rsrc_t rb = d_rsrc(beta + q0, 8 * (q1 - q0));
-            const __amdgpu_buffer_rsrc_t re = d_rsrc(tb.cls2 + (size_t)m2 * CW2_SLICE, 4 * CW2_SLICE);
+            const __amdgpu_buffer_rsrc_t rb = buf_rsrc(beta + q0, 8 * (q1 - q0));
+            const __amdgpu_buffer_rsrc_t re = buf_rsrc(tb.cls2 + (size_t)m2 * CW2_SLICE, 4 * CW2_SLICE);
 #pragma unroll
             for (int i = 0; i < D_SN; ++i) {
                 e[i] = __builtin_amdgcn_raw_buffer_load_b32(re, 4 * tl, 4 * i * D_T, 0);
-                v[i] = have_beta ? d_ldd(rb, 8 * tl + 8 * i * D_T, 0) : 0.0;
+                v[i] = have_beta ? buf_ldd(rb, 8 * tl + 8 * i * D_T, 0) : 0.0;
             }
         }
         __syncthreads();
         d_fft<true>(tl, rmk, tb.twp);
         {
-            const __amdgpu_buffer_rsrc_t rs = d_rsrc(s + q0, 8 * (q1 - q0));  // past the class's end: dropped
+            const __amdgpu_buffer_rsrc_t rs = buf_rsrc(s + q0, 8 * (q1 - q0));  // past the class's end: dropped
 #pragma unroll
             for (int i = 0; i < D_SN; ++i) {  // s = beta_prev + tau u (sparc.py:972), class order
                 const double sv = v[i] + tau * *d_re(e[i] & 0xffffu);
-                d_std(rs, sv, 8 * tl + 8 * i * D_T, 0);
+                buf_std(rs, sv, 8 * tl + 8 * i * D_T, 0);
             }
         }
         __syncthreads();  // the next class overwrites the image
@@ -634,16 +587,6 @@ __global__ __launch_bounds__(D_T, 1) void cw2d_az(Cw2dTables tb, RegBufs<double>
 constexpr int D_ST_MAXW = 16;
 constexpr int ST_WAVES_MIN = 4;
 constexpr int ST_K = 8;      // entries per lane: sections of M <= 512 entries
-__device__ __forceinline__ double d_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double d_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 template <int ST_WAVES>
 __global__ __launch_bounds__(64 * ST_WAVES) void cw2d_stats(Cw2dTables tb, RegBufs<double> bf) {
     // per wavefront: exclusive prefix of the segment lengths over the classes, and each segment's base
@@ -691,7 +634,7 @@ __global__ __launch_bounds__(64 * ST_WAVES) void cw2d_stats(Cw2dTables tb, RegBu
     double m = x[0];
 #pragma unroll
     for (int j = 1; j < ST_K; ++j) m = fmax(m, x[j]);
-    const double M = d_wave_max(m);
+    const double M = wave_max(m);
     const double ms = M / tau;  // (amp_fused.hip sm_stage)
     double S1 = 0.0, S2 = 0.0;
 #pragma unroll
@@ -700,8 +643,8 @@ __global__ __launch_bounds__(64 * ST_WAVES) void cw2d_stats(Cw2dTables tb, RegBu
         S1 += x[j];
         S2 = __builtin_fma(x[j], x[j], S2);
     }
-    S1 = d_wave_sum(S1);
-    S2 = d_wave_sum(S2);
+    S1 = wave_sum(S1);
+    S2 = wave_sum(S2);
     const double inv = 1.0 / S1;
 #pragma unroll
     for (int j = 0; j < ST_K; ++j)

@@ -161,19 +161,6 @@ __global__ __launch_bounds__(256) void az_passB(AmpTables<T> tb, AmpBufs<T> bf, 
 // ------------------------------------------------------------------ eta
 // One wavefront per section; EPL = ceil(M/64) elements per lane.
 template <typename T>
-__device__ __forceinline__ T wave_max(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-template <typename T>
 __device__ __forceinline__ T gather_u(const AmpTables<T> &tb, const AmpBufs<T> &bf, int cw, int c, int jl) {
     T u = T(0);
     for (int q = tb.col_ptr[c]; q < tb.col_ptr[c + 1]; ++q) {
@@ -253,17 +240,6 @@ __global__ __launch_bounds__(256) void eta_kernel(AmpTables<T> tb, AmpBufs<T> bf
 // phase 0 (before Az, iteration t): Onsager residual and phi/tau
 // (sparc.py:932-969); phase 1 (after eta): psi, NMSE, stopping
 // (sparc.py:976-988); phase 2: initialisation.
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < nw; ++w) t += red[w];
-    return t;
-}
-
 template <typename T>
 __global__ __launch_bounds__(1024) void control_kernel(AmpTables<T> tb, AmpBufs<T> bf, AmpScalars sc, AmpParams pr,
                                                        int phase, int t) {

@@ -90,17 +90,6 @@ __device__ __forceinline__ cx<T> reg_tw2(const RegTables<T> &tb, int m2, int k1)
     return cmul(tb.twa[m2 * 64 + (k1 & 63)], tb.twb[m2 * tb.nB + (k1 >> 6)]);
 }
 
-__device__ __forceinline__ double reg_block_sum(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < nw; ++w) t += red[w];
-    return t;
-}
-
 // diagnostics: wave 0 of a workgroup stamps the shader clock at phase k
 // (and, at the first and last phase, the device-wide 100 MHz realtime clock)
 #define SG_TP(buf, k)                                                                                           \
@@ -649,7 +638,7 @@ __global__ __launch_bounds__(1024) void reg_ctrl0(RegTables<T> tb, RegBufs<T> bf
     }
     double phi;
     if (sum_z) {
-        phi = reg_block_sum(acc, red) / (double)tb.n;
+        phi = block_sum(acc, red) / (double)tb.n;
     } else {
         __syncthreads();
         phi = pr.awgn_var + sh_g;
@@ -767,8 +756,8 @@ __global__ __launch_bounds__(1024) void reg_merge(RegTables<T> tb, RegBufs<T> bf
                 e += err;
             }
         }
-        a = reg_block_sum(a, red);
-        e = reg_block_sum(e, red);
+        a = block_sum(a, red);
+        e = block_sum(e, red);
         if (tid == 0) {
             const double denom = (Lc == 1) ? (double)tb.L : (double)Lb;
             // f32 accumulates 1 - sum beta^2 per section; f64 the reference's sum beta^2

@@ -23,7 +23,7 @@ int build_block(sg_amp_plan *p, const uint32_t *order0, const uint32_t *order1, 
             const long long sl = slot_of_pos(o1[j], N);
             const uint32_t lds = (uint32_t)(2 * ppos((int)(sl >> 1)) + (int)(sl & 1));
             SG_CHECK_ARG(lds < 65536u, "internal: padded LDS index beyond 16 bits");
-            // owner (thread, entry) of column entry j: amp_block.hip bk_j
+            // owner (thread, entry) of column entry j: amp_block_common.hpp blk_j at 16 entries per thread
             const int M = p->M, eps = M / 64, spw = 1024 / M;
             const int l = j / M, rr = j % M;
             const int tid = (l / spw) * 64 + rr / eps, i = (l % spw) * eps + rr % eps;
@@ -67,7 +67,7 @@ int build_block(sg_amp_plan *p, const uint32_t *order0, const uint32_t *order1, 
 // Tables of the two-class block engine (amp_block2.hip): N2 = 2 P with P = 2^14
 // (w = 2^16) or 2^13 (w = 2^15).  Column entry j sits at packed slot
 // m = 2 m1 + m2 of its transform: class m2, real LDS index 2 ppos(m1) +
-// component in the class image; owned by (thread, entry) as b2_j.  Output
+// component in the class image; owned by (thread, entry) as blk_j at 32 entries per thread.  Output
 // coefficients per class fold the class factor w_N2^(m2 k) and the last
 // radix-RF stage (RF = P / 4096): al = c1 w_N2^((m2 + 2 r) a).
 int build_block2(sg_amp_plan *p, const uint32_t *order0, const uint32_t *order1, const std::vector<double> &t_scale,

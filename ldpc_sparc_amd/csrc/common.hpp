@@ -60,3 +60,17 @@ struct HipError {
         if (r_ != SG_OK)                                                                    \
             return r_;                                                                      \
     } while (0)
+
+namespace sg {
+
+// Raises kernel fn's dynamic-LDS limit to lds bytes.  *done is the caller's
+// record of the limit already set for fn (a static of the launcher, one per
+// kernel instance; grow-only); null: set it on every call.
+static inline int set_max_lds(const void *fn, size_t lds, size_t *done) {
+    if (done && *done >= lds) return SG_OK;
+    SG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (done) *done = lds;
+    return SG_OK;
+}
+
+}  // namespace sg

@@ -19,23 +19,13 @@
 #include <algorithm>
 
 #include "dense.hpp"
+#include "device_util.hpp"
 
 namespace sg {
 
 namespace {
 
 constexpr int IB = 256;  // block size of the section kernels
-
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < IB / 64; ++w) t += red[w];
-    return t;
-}
 
 __device__ __forceinline__ int log2i(int M) {
     int k = 0;
@@ -110,7 +100,7 @@ __global__ __launch_bounds__(IB) void update_post_kernel(const T *gamma, const T
     const size_t o = ((size_t)b * L + l) * M;
     double bot = 0.0;
     for (int i = threadIdx.x; i < M; i += IB) bot += (double)((alpha_w[o + i] / (T)ascale) * gamma[o + i]);
-    const T bt = (T)block_sum(bot, red);
+    const T bt = (T)block_sum<IB / 64>(bot, red);
     for (int i = threadIdx.x; i < M; i += IB) {
         const T top = (alpha_w[o + i] / (T)ascale) * gamma[o + i];
         beta[o + i] = (T)snp * (top / bt);
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(IB) void deta_kernel(int post, const T *beta, const
         double a = 0.0;
         for (int i = threadIdx.x; i < M; i += IB)
             if (((i >> (logM - 1 - k)) & 1) == 0) a += (double)(alpha_w[o + i] / (T)ascale);
-        a = block_sum(a, red);
+        a = block_sum<IB / 64>(a, red);
         if (threadIdx.x == 0) {
             const double v = fmin(fmax((double)vk0[((size_t)b * L + l) * logM + k], 1e-10), 1.0 - 1e-10);
             sA[k] = a;
@@ -159,8 +149,8 @@ __global__ __launch_bounds__(IB) void deta_kernel(int post, const T *beta, const
             bot += al * g;
             botd += ad * g + al * (g * mt);
         }
-        bot = block_sum(bot, red);
-        botd = block_sum(botd, red);
+        bot = block_sum<IB / 64>(bot, red);
+        botd = block_sum<IB / 64>(botd, red);
     }
     double sum = 0.0;
     for (int i = threadIdx.x; i < M; i += IB) {
@@ -183,7 +173,7 @@ __global__ __launch_bounds__(IB) void deta_kernel(int post, const T *beta, const
         if (out) out[o + i] = (T)de;
         sum += de;
     }
-    sum = block_sum(sum, red);
+    sum = block_sum<IB / 64>(sum, red);
     if (threadIdx.x == 0) part[(size_t)b * L + l] = sum;
 }
 
@@ -193,7 +183,7 @@ __global__ void deta_finish_kernel(const double *part, int L, double *ons) {
     const int b = blockIdx.x;
     double v = 0.0;
     for (int l = threadIdx.x; l < L; l += IB) v += part[(size_t)b * L + l];
-    v = block_sum(v, red);
+    v = block_sum<IB / 64>(v, red);
     if (threadIdx.x == 0) ons[b] = v;
 }
 

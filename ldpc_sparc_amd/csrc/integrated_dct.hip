@@ -11,23 +11,13 @@
 //                          one pass for the dense loop's dense_launch_eta, glue_launch_llr, integ_launch_llr
 // Fixed-order reductions, no atomics: the same bits on every run.
 #include "dense.hpp"
+#include "device_util.hpp"
 
 namespace sg {
 
 namespace {
 
 constexpr int RB = 256;  // block size of the residual kernel
-
-__device__ __forceinline__ double rblock_sum(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < RB / 64; ++w) t += red[w];
-    return t;
-}
 
 template <typename T>
 __device__ __forceinline__ T sexp(T x);
@@ -56,7 +46,7 @@ __global__ __launch_bounds__(RB) void idct_residual_kernel(const T *y, const T *
     if (t > 0 && ons_mode == 0) {
         double v = 0.0;
         for (int l = tid; l < L; l += RB) v += sec_bsq[(size_t)b * L + l];
-        bsq = rblock_sum(v, red);
+        bsq = block_sum<RB / 64>(v, red);
     }
     double zz = 0.0;
     for (int i = tid; i < n; i += RB) {
@@ -72,7 +62,7 @@ __global__ __launch_bounds__(RB) void idct_residual_kernel(const T *y, const T *
         z[o + i] = zn;
         zz += (double)zn * (double)zn;
     }
-    zz = rblock_sum(zz, red);  // (its barriers: every thread has read tau[b] before thread 0 writes it)
+    zz = block_sum<RB / 64>(zz, red);  // (its barriers: every thread has read tau[b] before thread 0 writes it)
     if (tid == 0) {
         const double t2 = zz / n;
         tau[b] = t2;
