@@ -199,6 +199,35 @@ int sg_ldpc_decode(sg_graph *g, int dectype, int precision, const double *ch, in
  * infinity or a value that overflows float to the table kernel instead. */
 int sg_ldpc_decode_device(sg_graph *g, int dectype, int precision, const void *d_ch, int B,
                           int max_it, double corr, void *d_app, int32_t *d_it, void *stream);
+/* Layered (row-serial) schedule (DESIGN.md "Layered schedule"): layer l is the
+ * checks [l*layer, (l+1)*layer); an iteration takes the layers in ascending
+ * order, each check computing Q_k = app[v_k] - R[c,k], the new check messages
+ * R'[c,.] from Q (minsum: Lxfb without correction, times `corr`; sumprod2:
+ * Lxfb with Lxor's correction) and app[v_k] = Q_k + R'[c,k] at once.  After the
+ * last layer the syndrome of the hard decisions app < 0 stops the codeword:
+ * it[b] is the 0-based index of that iteration, else max_it; app is as the last
+ * executed layer left it.  For a quasi-cyclic code layer = z.
+ *
+ * sg_ldpc_layer_check (host only, no device): SG_OK when `layer` divides nc and
+ * no variable occurs twice within a layer, else SG_ERR_INVALID with the first
+ * offending layer and variable in sg_last_error(). */
+int sg_ldpc_layer_check(const int64_t *vdeg, const int64_t *cdeg, const int64_t *intrlv, int nv, int nc,
+                        int nmsg, int layer);
+/* As sg_ldpc_decode / sg_ldpc_decode_device on the layered schedule.  The layer
+ * size is validated as by sg_ldpc_layer_check at first use of a (graph, layer)
+ * pair and its tables are kept on the graph handle.  SG_ERR_INVALID: max_it < 1,
+ * a layer size that fails the check.  SG_ERR_UNSUPPORTED, before anything is
+ * launched: SG_SUMPROD (the tanh form), a check degree above 32, more than
+ * 65536 variables, a graph whose app, messages and tables exceed one
+ * workgroup's 160 KB of LDS at this precision. */
+int sg_ldpc_decode_layered(sg_graph *g, int dectype, int precision, int layer, const double *ch, int B,
+                           int max_it, double corr, double *app, int32_t *it);
+int sg_ldpc_decode_layered_device(sg_graph *g, int dectype, int precision, int layer, const void *d_ch, int B,
+                                  int max_it, double corr, void *d_app, int32_t *d_it, void *stream);
+/* Name of the kernel the layered entry points launch (e.g.
+ * "bp_layered_kernel<float, 2, 8, 128>"), as sg_ldpc_decode_kernel. */
+int sg_ldpc_decode_layered_kernel(const sg_graph *g, int dectype, int precision, int layer, char *name,
+                                  size_t len);
 /* Device-side error counting against known codewords (ldpc_awgn.py:97-104):
  * d_x[B][nv] uint8 transmitted bits, app from sg_ldpc_decode_device.  Adds to
  * d_counts[4] = {bit errors over nv, frame errors, bit errors over the first

@@ -65,6 +65,12 @@ SIGNATURES = [
     ("sg_ldpc_decode", ct.c_int, [vp, ct.c_int, ct.c_int, vp, ct.c_int, ct.c_int, ct.c_double, vp, vp]),
     ("sg_ldpc_decode_device", ct.c_int,
      [vp, ct.c_int, ct.c_int, vp, ct.c_int, ct.c_int, ct.c_double, vp, vp, vp]),
+    ("sg_ldpc_layer_check", ct.c_int, [vp, vp, vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int]),
+    ("sg_ldpc_decode_layered", ct.c_int,
+     [vp, ct.c_int, ct.c_int, ct.c_int, vp, ct.c_int, ct.c_int, ct.c_double, vp, vp]),
+    ("sg_ldpc_decode_layered_device", ct.c_int,
+     [vp, ct.c_int, ct.c_int, ct.c_int, vp, ct.c_int, ct.c_int, ct.c_double, vp, vp, vp]),
+    ("sg_ldpc_decode_layered_kernel", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, ct.c_char_p, ct.c_size_t]),
     ("sg_ldpc_codeword_errors_device", ct.c_int, [vp, ct.c_int, vp, vp, ct.c_int, vp, vp]),
     ("sg_ldpc_count_errors_device", ct.c_int,
      [vp, ct.c_int, vp, vp, vp, ct.c_int, ct.c_int, vp, vp]),

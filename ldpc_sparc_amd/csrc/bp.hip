@@ -47,31 +47,6 @@ constexpr int BP_PS_PAD = 2;
 // kernel's scheme; three workgroups share a CU): 1.456 -> 1.392 ms per launch on the C3 code (table kernel
 // forced), bit-identical.  Double-precision sumprod2 measured 1 % slower with it, so the other kinds stay
 // flat (profiles/r05_prio_ab.txt).
-template <typename T>
-__device__ __forceinline__ T dev_log(T x);
-template <>
-__device__ __forceinline__ double dev_log<double>(double x) { return log(x); }
-template <>
-__device__ __forceinline__ float dev_log<float>(float x) { return __logf(x); }
-template <typename T>
-__device__ __forceinline__ T dev_exp(T x);
-template <>
-__device__ __forceinline__ double dev_exp<double>(double x) { return exp(x); }
-template <>
-__device__ __forceinline__ float dev_exp<float>(float x) { return __expf(x); }
-
-// Pairwise XOR-LLR (reference Lxor, c_ldpc.c:234-251).
-template <typename T, bool CORR>
-__device__ __forceinline__ T lxor(T a, T b) {
-    const bool same = (signbit(a) != 0) == (signbit(b) != 0);
-    T out = (same ? T(1) : T(-1)) * fmin(fabs(a), fabs(b));
-    if (CORR) {
-        out += dev_log<T>(T(1) + dev_exp<T>(-fabs(a + b)));
-        out -= dev_log<T>(T(1) + dev_exp<T>(-fabs(a - b)));
-    }
-    return out;
-}
-
 template <typename T, int MAXDC>
 __device__ __forceinline__ void check_load(const T *__restrict__ msg, int c, int nc, int d, T *L) {
 #pragma unroll

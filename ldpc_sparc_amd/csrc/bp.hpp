@@ -59,9 +59,63 @@ int bp_grouped_launch(const BpGrpArgs &a, hipStream_t s);
 // per wave (the host lays meta / vmap out with these strides)
 inline int grp_kvj(int vj, int cj) { return (vj <= 4 && cj <= 2) ? 4 : 8; }
 inline int grp_kcj(int vj, int cj) { return (vj <= 4 && cj <= 2) ? 2 : 4; }
+// Layered (row-serial) schedule (bp_layered.hip).  Layer l is the checks [l S, (l + 1) S); no variable occurs
+// twice within a layer (capi_ldpc.cpp layer_validate), so a layer's checks run one per lane with no ordering
+// among them.  Message slot of check c = l S + i, port k: loff[l] + k S + i (a layer's ports side by side,
+// padded to the layer's largest degree); evar[slot] is the variable on that port.
+constexpr int LAY_MAXDC = 32;  // check degrees accepted, as bp.hip dispatch_dc
+constexpr int LAY_STATIC_LDS = 256;  // the kernel's static LDS (the stop vote), beside the dynamic image
+template <typename T>
+struct BpLayArgs {
+    const uint16_t *evar;  // [slots] variable of each message slot (pad slots: 0, never read)
+    const uint8_t *cdeg;   // [nc]
+    const int32_t *loff;   // [nlayers] first slot of each layer
+    int nv, nc, S, nlayers, slots, max_cdeg;
+    const T *ch;           // [B][nv]
+    T *app;                // [B][nv]
+    int32_t *it;           // [B]
+    int B, max_it;
+    T factor;
+};
+// LDS bytes of one codeword's workgroup: app and R, then the tables
+template <typename T>
+inline size_t bp_layered_lds_bytes(int nv, int nc, int slots, int nlayers) {
+    size_t b = sizeof(T) * ((size_t)nv + slots) + sizeof(int32_t) * (size_t)nlayers + sizeof(uint16_t) * (size_t)slots + nc;
+    return (b + 15) / 16 * 16;
+}
+inline int bp_layered_threads(int S) { return S <= 64 ? 64 : 128; }
+template <typename T>
+int bp_layered_launch(const BpLayArgs<T> &a, int dectype, hipStream_t s);
+
 template <typename T>
 int bp_count_launch(const T *app, const uint8_t *x, const int32_t *its, int B, int nv, int k,
                     int64_t *counts, hipStream_t s, int32_t *per_cw = nullptr);
 int lxfb_launch(double *dL, int dc, int corr, double *dagg, hipStream_t s);
+
+// Device arithmetic shared by the flooding (bp.hip) and the layered (bp_layered.hip) kernels
+template <typename T>
+__device__ __forceinline__ T dev_log(T x);
+template <>
+__device__ __forceinline__ double dev_log<double>(double x) { return log(x); }
+template <>
+__device__ __forceinline__ float dev_log<float>(float x) { return __logf(x); }
+template <typename T>
+__device__ __forceinline__ T dev_exp(T x);
+template <>
+__device__ __forceinline__ double dev_exp<double>(double x) { return exp(x); }
+template <>
+__device__ __forceinline__ float dev_exp<float>(float x) { return __expf(x); }
+
+// Pairwise XOR-LLR (reference Lxor, c_ldpc.c:234-251).
+template <typename T, bool CORR>
+__device__ __forceinline__ T lxor(T a, T b) {
+    const bool same = (signbit(a) != 0) == (signbit(b) != 0);
+    T out = (same ? T(1) : T(-1)) * fmin(fabs(a), fabs(b));
+    if (CORR) {
+        out += dev_log<T>(T(1) + dev_exp<T>(-fabs(a + b)));
+        out -= dev_log<T>(T(1) + dev_exp<T>(-fabs(a - b)));
+    }
+    return out;
+}
 
 }  // namespace sg

@@ -11,6 +11,13 @@
 
 #include "bp.hpp"
 
+// What the layered schedule needs for one layer size of a graph (bp.hpp BpLayArgs)
+struct sg_layer_plan {
+    int layer = 0, nlayers = 0, slots = 0;
+    uint16_t *d_evar = nullptr;
+    int32_t *d_loff = nullptr;
+};
+
 struct sg_graph {
     int device = 0;
     int nv = 0, nc = 0, nmsg = 0, max_cdeg = 0, max_vdeg = 0, slots = 0;
@@ -28,6 +35,7 @@ struct sg_graph {
     int grp_ntab = 0, grp_msg_bytes = 0, grp_vj = 0, grp_cj = 0;
     int32_t *d_grp_meta = nullptr, *d_grp_vmap = nullptr;
     uint16_t *d_grp_vtab = nullptr;
+    std::vector<sg_layer_plan> layers;  // layered schedule: one plan per layer size used so far
 };
 
 namespace sg {
@@ -290,6 +298,133 @@ static int build_graph(const int64_t *vdeg, const int64_t *cdeg, const int64_t *
     return SG_OK;
 }
 
+// Variable of every check-ordered message and the checks' message offsets, with graph creation's validation
+// (degree ranges and sums, intrlv a permutation).  Host only.
+static int msg_variables(const int64_t *vdeg, const int64_t *cdeg, const int64_t *intrlv, int nv, int nc, int nmsg,
+                         std::vector<int32_t> &coff, std::vector<int32_t> &mvar) {
+    SG_CHECK_ARG(vdeg && cdeg && intrlv, "null graph array");
+    SG_CHECK_ARG(nv > 0 && nc > 0 && nmsg > 0, "empty graph (Nv=%d Nc=%d Nmsg=%d)", nv, nc, nmsg);
+    coff.assign(nc + 1, 0);
+    for (int c = 0; c < nc; ++c) {
+        SG_CHECK_ARG(cdeg[c] >= 2 && cdeg[c] < 256, "check degree %lld out of range (need 2..255)", (long long)cdeg[c]);
+        SG_CHECK_ARG(coff[c] + cdeg[c] <= nmsg, "check degrees sum past Nmsg=%d", nmsg);
+        coff[c + 1] = coff[c] + (int32_t)cdeg[c];
+    }
+    mvar.assign(nmsg, -1);
+    long p = 0;
+    for (int v = 0; v < nv; ++v) {
+        SG_CHECK_ARG(vdeg[v] >= 0 && vdeg[v] < 256, "variable degree %lld out of range", (long long)vdeg[v]);
+        SG_CHECK_ARG(p + vdeg[v] <= nmsg, "variable degrees sum past Nmsg=%d", nmsg);
+        for (int k = 0; k < (int)vdeg[v]; ++k, ++p) {
+            const int64_t m = intrlv[p];
+            SG_CHECK_ARG(m >= 0 && m < nmsg && mvar[m] < 0, "intrlv is not a permutation of [0, Nmsg)");
+            mvar[m] = v;
+        }
+    }
+    SG_CHECK_ARG(p == nmsg && coff[nc] == nmsg, "degree sums (%ld, %d) do not match Nmsg=%d", p, coff[nc], nmsg);
+    return SG_OK;
+}
+
+// Layers of `layer` consecutive checks for the layered schedule: layer divides nc and no variable occurs twice
+// within a layer (its checks then update disjoint posteriors and run side by side)
+static int layer_validate(const std::vector<int32_t> &coff, const std::vector<int32_t> &mvar, int nv, int nc,
+                          int layer) {
+    SG_CHECK_ARG(layer > 0 && layer <= nc && nc % layer == 0, "layer size %d does not divide Nc=%d", layer, nc);
+    std::vector<int32_t> seen(nv, -1);
+    for (int c = 0; c < nc; ++c)
+        for (int m = coff[c]; m < coff[c + 1]; ++m) {
+            const int v = mvar[m], l = c / layer;
+            SG_CHECK_ARG(seen[v] != l, "variable %d occurs twice in layer %d (checks %d..%d) at layer size %d: "
+                         "its checks are not independent", v, l, l * layer, (l + 1) * layer - 1, layer);
+            seen[v] = l;
+        }
+    return SG_OK;
+}
+
+// The plan of a (graph, layer size) pair: validated and uploaded at first use, kept on the graph handle
+static int layer_plan(sg_graph *g, int layer, const sg_layer_plan **out) {
+    for (const sg_layer_plan &p : g->layers)
+        if (p.layer == layer) {
+            *out = &p;
+            return SG_OK;
+        }
+    std::vector<int32_t> coff, mvar;
+    SG_TRY(msg_variables(g->h_vdeg.data(), g->h_cdeg.data(), g->h_intrlv.data(), g->nv, g->nc, g->nmsg, coff, mvar));
+    SG_TRY(layer_validate(coff, mvar, g->nv, g->nc, layer));
+    if (g->max_cdeg > LAY_MAXDC)
+        return fail(SG_ERR_UNSUPPORTED, "check degree %d exceeds the supported maximum of %d", g->max_cdeg, LAY_MAXDC);
+    if (g->nv > 65536)
+        return fail(SG_ERR_UNSUPPORTED, "graph with %d variables exceeds the layered decoder's 16-bit LDS table", g->nv);
+    sg_layer_plan p;
+    p.layer = layer;
+    p.nlayers = g->nc / layer;
+    std::vector<int32_t> loff(p.nlayers);
+    long slots = 0;
+    for (int l = 0; l < p.nlayers; ++l) {
+        int dmax = 0;
+        for (int i = 0; i < layer; ++i) dmax = std::max(dmax, (int)g->h_cdeg[l * layer + i]);
+        loff[l] = (int32_t)slots;
+        slots += (long)dmax * layer;
+    }
+    p.slots = (int)slots;
+    std::vector<uint16_t> evar(slots, 0);
+    for (int c = 0; c < g->nc; ++c)
+        for (int k = 0; k < coff[c + 1] - coff[c]; ++k)
+            evar[loff[c / layer] + (long)k * layer + c % layer] = (uint16_t)mvar[coff[c] + k];
+    hipStream_t s = lib_stream();
+    SG_HIP(hipSetDevice(g->device));
+    bool ok = hipMalloc(&p.d_evar, sizeof(uint16_t) * evar.size()) == hipSuccess &&
+              hipMalloc(&p.d_loff, sizeof(int32_t) * loff.size()) == hipSuccess;
+    ok = ok && hipMemcpyAsync(p.d_evar, evar.data(), sizeof(uint16_t) * evar.size(), hipMemcpyHostToDevice, s) == hipSuccess &&
+         hipMemcpyAsync(p.d_loff, loff.data(), sizeof(int32_t) * loff.size(), hipMemcpyHostToDevice, s) == hipSuccess &&
+         hipStreamSynchronize(s) == hipSuccess;
+    if (!ok) {
+        if (p.d_evar) hipFree(p.d_evar);
+        if (p.d_loff) hipFree(p.d_loff);
+        return fail(SG_ERR_NOMEM, "device allocation/upload of the layer tables failed");
+    }
+    g->layers.push_back(p);
+    *out = &g->layers.back();
+    return SG_OK;
+}
+
+template <typename T>
+static int layered_launch(sg_graph *g, const sg_layer_plan &p, int dectype, const void *d_ch, int B, int max_it,
+                          double corr, void *d_app, int32_t *d_it, hipStream_t s) {
+    BpLayArgs<T> a;
+    a.evar = p.d_evar; a.cdeg = g->d_cdeg; a.loff = p.d_loff;
+    a.nv = g->nv; a.nc = g->nc; a.S = p.layer; a.nlayers = p.nlayers; a.slots = p.slots; a.max_cdeg = g->max_cdeg;
+    a.ch = (const T *)d_ch; a.app = (T *)d_app; a.it = d_it;
+    a.B = B; a.max_it = max_it; a.factor = (T)corr;
+    return bp_layered_launch<T>(a, dectype, s);
+}
+
+// Argument checks of the layered entry points that need no device
+static int layered_check_args(const sg_graph *g, int dectype, int precision, int layer, int B, int max_it) {
+    SG_CHECK_ARG(g, "graph is NULL");
+    SG_CHECK_ARG(B >= 0, "negative batch");
+    SG_CHECK_ARG(dectype == SG_SUMPROD || dectype == SG_SUMPROD2 || dectype == SG_MINSUM,
+                 "Decoder type unknonwn (dectype=%d)", dectype);
+    if (dectype == SG_SUMPROD)
+        return fail(SG_ERR_UNSUPPORTED, "the layered schedule decodes minsum and sumprod2 only: sumprod (the tanh "
+                    "form) runs on the flooding schedule");
+    SG_CHECK_ARG(precision == SG_F64 || precision == SG_F32, "precision must be SG_F64 or SG_F32");
+    SG_CHECK_ARG(max_it >= 1, "the layered schedule needs max_it >= 1 (got %d)", max_it);
+    SG_CHECK_ARG(layer > 0 && g->nc % layer == 0, "layer size %d does not divide Nc=%d", layer, g->nc);
+    return SG_OK;
+}
+
+static int decode_layered_device(sg_graph *g, int dectype, int precision, int layer, const void *d_ch, int B,
+                                 int max_it, double corr, void *d_app, int32_t *d_it, hipStream_t s) {
+    SG_TRY(layered_check_args(g, dectype, precision, layer, B, max_it));
+    const sg_layer_plan *p = nullptr;
+    SG_TRY(layer_plan(g, layer, &p));
+    if (B == 0) return SG_OK;
+    SG_CHECK_ARG(d_ch && d_app && d_it, "null device buffer");
+    if (precision == SG_F64) return layered_launch<double>(g, *p, dectype, d_ch, B, max_it, corr, d_app, d_it, s);
+    return layered_launch<float>(g, *p, dectype, d_ch, B, max_it, corr, d_app, d_it, s);
+}
+
 template <typename T>
 static BpArgs<T> make_args(sg_graph *g, const void *ch, int B, int max_it, double corr, void *app, int32_t *it) {
     BpArgs<T> a;
@@ -359,8 +494,9 @@ static int ensure_staging(sg_graph *g, int B) {
     return SG_OK;
 }
 
+// layer > 0: the layered schedule at that layer size, else flooding
 static int decode_host(sg_graph *g, int dectype, int precision, const double *ch, int B, int max_it, double corr,
-                       double *app, int32_t *it) {
+                       double *app, int32_t *it, int layer = 0) {
     SG_CHECK_ARG(g, "graph is NULL");
     SG_CHECK_ARG(B >= 0, "negative batch");
     if (B == 0) return SG_OK;
@@ -391,7 +527,10 @@ static int decode_host(sg_graph *g, int dectype, int precision, const double *ch
         SG_HIP(hipMemcpyAsync(g->d_ch, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice, s));
         SG_HIP(hipStreamSynchronize(s));
     }
-    SG_TRY(decode_device(g, dectype, precision, g->d_ch, B, max_it, corr, g->d_app, g->d_it, s, ch_has_nan));
+    if (layer > 0)
+        SG_TRY(decode_layered_device(g, dectype, precision, layer, g->d_ch, B, max_it, corr, g->d_app, g->d_it, s));
+    else
+        SG_TRY(decode_device(g, dectype, precision, g->d_ch, B, max_it, corr, g->d_app, g->d_it, s, ch_has_nan));
     SG_HIP(hipMemcpyAsync(it, g->d_it, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
     if (precision == SG_F64) {
         SG_HIP(hipMemcpyAsync(app, g->d_app, n * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -467,6 +606,10 @@ int sg_ldpc_graph_destroy(sg_graph *g) {
     if (g->d_ch) hipFree(g->d_ch);
     if (g->d_app) hipFree(g->d_app);
     if (g->d_it) hipFree(g->d_it);
+    for (sg_layer_plan &p : g->layers) {
+        hipFree(p.d_evar);
+        hipFree(p.d_loff);
+    }
     delete g;
     return SG_OK;
 }
@@ -548,6 +691,34 @@ int sg_ldpc_decode_kernel(const sg_graph *g, int dectype, int precision, char *n
                  dectype, dc, vj);
     }
     snprintf(name, len, "%s", buf);
+    return SG_OK;
+}
+
+int sg_ldpc_layer_check(const int64_t *vdeg, const int64_t *cdeg, const int64_t *intrlv, int nv, int nc, int nmsg,
+                        int layer) {
+    std::vector<int32_t> coff, mvar;
+    SG_TRY(msg_variables(vdeg, cdeg, intrlv, nv, nc, nmsg, coff, mvar));
+    return layer_validate(coff, mvar, nv, nc, layer);
+}
+
+int sg_ldpc_decode_layered(sg_graph *g, int dectype, int precision, int layer, const double *ch, int B, int max_it,
+                           double corr, double *app, int32_t *it) {
+    SG_TRY(layered_check_args(g, dectype, precision, layer, B, max_it));
+    return decode_host(g, dectype, precision, ch, B, max_it, corr, app, it, layer);
+}
+
+int sg_ldpc_decode_layered_device(sg_graph *g, int dectype, int precision, int layer, const void *d_ch, int B,
+                                  int max_it, double corr, void *d_app, int32_t *d_it, void *stream) {
+    SG_TRY(layered_check_args(g, dectype, precision, layer, B, max_it));
+    SG_TRY(ensure_device());
+    return decode_layered_device(g, dectype, precision, layer, d_ch, B, max_it, corr, d_app, d_it, pick_stream(stream));
+}
+
+int sg_ldpc_decode_layered_kernel(const sg_graph *g, int dectype, int precision, int layer, char *name, size_t len) {
+    SG_CHECK_ARG(name && len > 0, "null name buffer");
+    SG_TRY(layered_check_args(g, dectype, precision, layer, 0, 1));
+    snprintf(name, len, "bp_layered_kernel<%s, %d, %d, %d>", precision == SG_F64 ? "double" : "float", dectype,
+             g->max_cdeg <= 8 ? 8 : 0, bp_layered_threads(layer));
     return SG_OK;
 }
 

@@ -34,6 +34,15 @@ def _shift(blocks, s):
     return np.roll(blocks, -int(s), axis=-1)
 
 
+SCHEDULES = ('flooding', 'layered')
+
+
+def _check_schedule(schedule):
+    if schedule not in SCHEDULES:
+        raise NameError('Schedule unknown')
+    return schedule
+
+
 class code:
     def __init__(self, standard='802.11n', rate='1/2', z=27, ptype='A'):
         self.standard = standard
@@ -178,13 +187,19 @@ class code:
             self._graph = g
         return self._graph
 
-    def decode_kernel(self, dectype="minsum", precision=None):
+    def decode_kernel(self, dectype="minsum", precision=None, schedule='flooding'):
         """Name of the GPU kernel decode_batch launches for this code (as
         rocprofv3 lists it): the degree-grouped min-sum kernel for
-        single-precision min-sum on graphs it takes, else the table kernel."""
+        single-precision min-sum on graphs it takes, else the table kernel;
+        the layered kernel for schedule='layered'."""
         prec = _native.SG_F32 if precision is None else precision
         buf = ct.create_string_buffer(128)
-        _native.check(_native.lib().sg_ldpc_decode_kernel(self._device_graph(), _native.DECTYPES[dectype], prec, buf, 128))
+        if _check_schedule(schedule) == 'layered':
+            _native.check(_native.lib().sg_ldpc_decode_layered_kernel(
+                self._device_graph(), _native.DECTYPES[dectype], prec, int(self.z), buf, 128))
+        else:
+            _native.check(_native.lib().sg_ldpc_decode_kernel(self._device_graph(), _native.DECTYPES[dectype], prec,
+                                                              buf, 128))
         return buf.value.decode()
 
     def __del__(self):
@@ -223,34 +238,46 @@ class code:
         codewords (uint8 [B, N]) -- the throughput-mode encoder."""
         _native.check(_native.lib().sg_ldpc_encode_device(self._device_encoder(), d_info, int(B), d_cw, stream))
 
-    def decode(self, ch, max_itcount=200, dectype='sumprod2', corr_factor=0.7):
+    def decode(self, ch, max_itcount=200, dectype='sumprod2', corr_factor=0.7, schedule='flooding'):
         """Decode one codeword of channel LLRs (ldpc.py:463-490) on the GPU in
-        double precision.  Returns (app float64[N], iterations)."""
+        double precision.  Returns (app float64[N], iterations).
+        schedule='layered': the row-serial schedule, one block row (z checks)
+        at a time (decode_batch)."""
         ch = np.asarray(ch, dtype=np.float64)
         if len(ch) != len(self.vdeg):
             raise NameError('Channel inputs not consistent with variable degrees')
         if dectype not in _native.DECTYPES:
             raise NameError('Decoder type unknonwn')
-        app, it = self.decode_batch(ch[None, :], max_itcount, dectype, corr_factor)
+        _check_schedule(schedule)
+        app, it = self.decode_batch(ch[None, :], max_itcount, dectype, corr_factor, schedule=schedule)
         return app[0], int(it[0])
 
     def decode_batch(self, ch, max_itcount=200, dectype='sumprod2', corr_factor=0.7,
-                     precision='f64'):
+                     precision='f64', schedule='flooding'):
         """Decode a [B, N] batch of LLR vectors in one GPU launch.
-        Returns (app float64[B, N], it int32[B])."""
+        Returns (app float64[B, N], it int32[B]).  schedule='flooding' is the
+        reference's schedule; 'layered' takes the block rows of the
+        protograph (layers of z checks) one after the other and updates the
+        posteriors at once (minsum and sumprod2; max_itcount >= 1)."""
         ch = np.ascontiguousarray(ch, dtype=np.float64)
         if ch.ndim != 2 or ch.shape[1] != self.Nv:
             raise NameError('Channel inputs not consistent with variable degrees')
         if dectype not in _native.DECTYPES:
             raise NameError('Decoder type unknonwn')
+        layered = _check_schedule(schedule) == 'layered'
         prec = {'f64': _native.SG_F64, 'f32': _native.SG_F32}[precision]
         g = self._device_graph()
         B = ch.shape[0]
         app = np.zeros_like(ch)
         it = np.zeros(B, dtype=np.int32)
-        _native.check(_native.lib().sg_ldpc_decode(
-            g, _native.DECTYPES[dectype], prec, _native.ptr(ch), B, int(max_itcount),
-            float(corr_factor), _native.ptr(app), _native.ptr(it)))
+        if layered:
+            _native.check(_native.lib().sg_ldpc_decode_layered(
+                g, _native.DECTYPES[dectype], prec, int(self.z), _native.ptr(ch), B, int(max_itcount),
+                float(corr_factor), _native.ptr(app), _native.ptr(it)))
+        else:
+            _native.check(_native.lib().sg_ldpc_decode(
+                g, _native.DECTYPES[dectype], prec, _native.ptr(ch), B, int(max_itcount),
+                float(corr_factor), _native.ptr(app), _native.ptr(it)))
         return app, it
 
     def Lxor(self, L1, L2, corrflag=1):

@@ -175,8 +175,10 @@ class LdpcTrial:
     does (ldpc_awgn.py:97-104).  aux0 = sum of decode iteration counts."""
 
     def __init__(self, c, snrs, dectype="sumprod2", max_it=200, corr=0.7, precision="f32", seed=0, rng="host",
-                 per_unit=False):
+                 per_unit=False, schedule="flooding"):
+        from .ldpc import _check_schedule
         self.c, self.snrs, self.dectype = c, list(snrs), dectype
+        self.schedule = _check_schedule(schedule)  # 'layered': layers of c.z checks (ldpc.code.decode_batch)
         self.per_unit = bool(per_unit)  # per-codeword counter rows (exact stopping rule, run_point)
         self.max_it, self.corr, self.seed = int(max_it), float(corr), int(seed)
         self.prec = {"f64": _native.SG_F64, "f32": _native.SG_F32}[precision]
@@ -230,8 +232,13 @@ class LdpcTrial:
         g = c._device_graph()
         d_app = _native.DeviceBuffer(B * c.N * np.dtype(dt).itemsize)
         d_it = _native.DeviceBuffer(B * 4)
-        _native.check(lib.sg_ldpc_decode_device(g, _native.DECTYPES[self.dectype], self.prec, d_ch.ptr, B,
-                                                self.max_it, self.corr, d_app.ptr, d_it.ptr, None))
+        if self.schedule == "layered":
+            _native.check(lib.sg_ldpc_decode_layered_device(g, _native.DECTYPES[self.dectype], self.prec, int(c.z),
+                                                            d_ch.ptr, B, self.max_it, self.corr, d_app.ptr, d_it.ptr,
+                                                            None))
+        else:
+            _native.check(lib.sg_ldpc_decode_device(g, _native.DECTYPES[self.dectype], self.prec, d_ch.ptr, B,
+                                                    self.max_it, self.corr, d_app.ptr, d_it.ptr, None))
         if self.per_unit:  # one row per codeword: [1, bit errors, frame error, iterations, 0]
             d_be = _native.DeviceBuffer(B * 4)
             _native.check(lib.sg_ldpc_codeword_errors_device(g, self.prec, d_app.ptr, d_x.ptr, B, d_be.ptr, None))
@@ -557,7 +564,7 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
 def ldpc_awgn_campaign(standard, rate, z, ptype="A", *, rank=0, world=1, agg=None, N_MEASUREMENTS=24,
                        C_AWGN_OFFSET=1.0, P_STEP=100.0, MIN_ERRORS=100, MAX_BLOCKS=400000, block=256,
                        blocks_per_round=16, dectype="sumprod2", max_it=200, precision="f32", seed=0,
-                       results_file=None, checkpoint_dir=None, trial=None):
+                       results_file=None, checkpoint_dir=None, trial=None, schedule="flooding"):
     """The BER/FER campaign of ldpc_awgn.sim (ldpc_awgn.py:60-114) on the GPU(s):
     same starting SNR, stopping rule (each point ends at the codeword whose
     frame error is the MIN_ERRORS-th, or at MAX_BLOCKS codewords, counted in
@@ -565,7 +572,9 @@ def ldpc_awgn_campaign(standard, rate, z, ptype="A", *, rank=0, world=1, agg=Non
     (rank 0) appends the result tuples (standard, rate, z, ptype, SNR, nblocks,
     nblockerrors, nblocks*K, nbiterrors, nit_total) -- the 11-field form that
     results2csv.c parses (results2csv.c:47-48).  `trial` replaces the GPU
-    trial (tests)."""
+    trial (tests).  schedule='layered' decodes on the layered schedule and
+    keeps its checkpoints under a tag and parameters of their own, so a
+    flooding checkpoint is never resumed as layered or the reverse."""
     from .ldpc import code
     Rv = {"1/2": .5, "2/3": 0.6667, "3/4": 0.75, "5/6": 0.83333}
     if rate not in Rv:
@@ -574,14 +583,19 @@ def ldpc_awgn_campaign(standard, rate, z, ptype="A", *, rank=0, world=1, agg=Non
     c = code(standard, rate, z, ptype)
     snr = 10.0 * np.log10(np.power(2, Rv[rate]) - 1.0) + C_AWGN_OFFSET
     res = []
-    trial = trial or LdpcTrial(c, [], dectype, max_it, 0.7, precision, seed, per_unit=True)
+    from .ldpc import _check_schedule
+    layered = _check_schedule(schedule) == "layered"
+    trial = trial or LdpcTrial(c, [], dectype, max_it, 0.7, precision, seed, per_unit=True, schedule=schedule)
     for point in range(N_MEASUREMENTS):
         trial.snrs.append(snr)
         params = {"seed": seed, "dectype": dectype, "max_it": max_it, "precision": precision, "snr": float(snr),
                   "min_errors": MIN_ERRORS, "max_blocks": MAX_BLOCKS}
+        if layered:  # (flooding checkpoints keep the tag and parameters they have always had)
+            params["schedule"] = schedule
         tot = run_point(trial, point, block=block, blocks_per_round=blocks_per_round, rank=rank, world=world,
                         agg=agg, min_errors=MIN_ERRORS, max_units=MAX_BLOCKS, checkpoint_dir=checkpoint_dir,
-                        tag=f"ldpc_{standard}_{rate.replace('/', '')}_{z}_{ptype}", params=params)
+                        tag=f"ldpc_{standard}_{rate.replace('/', '')}_{z}_{ptype}" + ("_layered" if layered else ""),
+                        params=params)
         nblocks = int(tot[0])
         out = (standard, rate, z, ptype, snr, nblocks, int(tot[2]), nblocks * c.K, int(tot[1]), int(tot[3]))
         res.append(out)
