@@ -540,6 +540,56 @@ int sg_section_mmse_psk(const double *x, int L, int M, int K, const double *cons
 int sg_section_map_psk(const double *s, int L, int M, int K, const double *constel,
                        int s_is_complex, int32_t *idx, int32_t *sym);
 
+/* Soft output of the complex engine (camp_llr.hip).  A section carries
+ * log2 M MSB-first location bits, then log2 K Gray-coded K-PSK bits
+ * (msg_vector_2_bin_arr, sparc.py:366-400).  For K >= 2 the decoder's final
+ * beta is a conditional mean, not a posterior, so P(bit = 0) is a marginal of
+ * the joint posterior p(j, k) ~ exp(Re(x_j conj c_k)), x = s / (tau / 2), of
+ * the last effective observation s = beta + tau u and its tau.
+ * sg_camp_soft_output(p, 1) makes the following decodes keep that s: 16 L M
+ * bytes per codeword, allocated with the batch workspace on the next decode;
+ * off (the default) nothing is allocated and the decoder stores what it always
+ * did.  Switching clears the state below. */
+int sg_camp_soft_output(sg_camp_plan *p, int on);
+/* For sections [l0, l0 + nl) of each of the B codewords of the last decode
+ * through this plan: P(bit = 0) of the log2 M + log2 K section bits, clipped
+ * to [1e-15, 1 - 1e-15] and written as log p - log(1 - p) (ldpc_bp,
+ * sparc_new.py:1167-1169) to d_llr[b * llr_ld + (l - l0) * (log2 M + log2 K) + i];
+ * probs_only: the unclipped probabilities.  A codeword that stopped early
+ * gives the s and the tau of its last executed iteration.  K and constel as
+ * the decode's.  Enqueued on the stream; allocates nothing.  SG_ERR_BAD_ARG:
+ * soft output off; no decode yet, or its state cleared (every decode call
+ * resets it, a failed or B = 0 one leaves it cleared; sg_camp_apply and
+ * sg_camp_encode_device clear it); B or K different from the decode's; a
+ * section range outside [0, L]; llr_ld < nl (log2 M + log2 K); M < 2.
+ * SG_ERR_UNSUPPORTED: M > 2048. */
+int sg_camp_llr_device(sg_camp_plan *p, int B, int K, const double *constel, int l0, int nl, int llr_ld,
+                       int probs_only, double *d_llr, void *stream);
+/* Host variant: out [B][nl * (log2 M + log2 K)], blocking.  A decode enqueued
+ * on a caller's stream must have completed. */
+int sg_camp_llr(sg_camp_plan *p, int B, int K, const double *constel, int l0, int nl, int probs_only,
+                double *out);
+/* The same function of a caller's vector, the twin of sg_section_mmse_psk:
+ * x = s / tau with tau already halved, [L*M] interleaved complex if
+ * x_is_complex else real (K <= 2: the exponents are +-x); out
+ * [L][log2 M + log2 K].  M a power of two in [2, 2048] (larger:
+ * SG_ERR_UNSUPPORTED). */
+int sg_section_llr_psk(const double *x, int L, int M, int K, const double *constel, int x_is_complex,
+                       int probs_only, double *out);
+/* sg_bits_to_psk_sections_device with row strides, as
+ * sg_bits_to_sections_strided_device: codeword b's L (logM + logK) bits at
+ * d_bits + b * bit_stride, its L locations and constellation indices at
+ * d_idx / d_sym + b * idx_stride. */
+int sg_bits_to_psk_sections_strided_device(const uint8_t *d_bits, size_t bit_stride, int B, int L, int logM,
+                                           int logK, int32_t *d_idx, int32_t *d_sym, size_t idx_stride,
+                                           void *stream);
+/* d_word [B][L] = d_idx << logK | bin2gray(d_sym): the log2 M + log2 K message
+ * bits of every section as one integer (logK = 0: d_sym may be NULL), so that
+ * sg_concat_count_errors_device counts a K-PSK codeword's unprotected bits
+ * with logM + logK in the place of logM. */
+int sg_psk_pack_sections_device(const int32_t *d_idx, const int32_t *d_sym, int B, int L, int logK,
+                                int32_t *d_word, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

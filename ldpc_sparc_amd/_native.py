@@ -111,6 +111,14 @@ SIGNATURES = [
                                                vp]),
     ("sg_section_mmse_psk", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, vp, ct.c_int, vp]),
     ("sg_section_map_psk", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, vp, ct.c_int, vp, vp]),
+    # soft output of the complex engine
+    ("sg_camp_soft_output", ct.c_int, [vp, ct.c_int]),
+    ("sg_camp_llr_device", ct.c_int, [vp, ct.c_int, ct.c_int, vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp, vp]),
+    ("sg_camp_llr", ct.c_int, [vp, ct.c_int, ct.c_int, vp, ct.c_int, ct.c_int, ct.c_int, vp]),
+    ("sg_section_llr_psk", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, vp, ct.c_int, ct.c_int, vp]),
+    ("sg_bits_to_psk_sections_strided_device", ct.c_int,
+     [vp, ct.c_size_t, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp, vp, ct.c_size_t, vp]),
+    ("sg_psk_pack_sections_device", ct.c_int, [vp, vp, ct.c_int, ct.c_int, ct.c_int, vp, vp]),
     ("Lxfb", ct.c_double, [dp, ct.c_long, ct.c_int]),
     ("sg_device_synchronize", ct.c_int, []),
     ("sg_profile_enable", ct.c_int, [ct.c_int]),

@@ -23,7 +23,8 @@
 // w-entry host table (16 MB at 2^20); nothing uses device sincos.
 // The needed outputs are single bins, read where they are used (the residual
 // of the control kernel, the s update of eta) from X at (k mod P) Q + k / P.
-//   eta     (one wavefront per section): s = beta + tau u, the K-PSK MMSE
+//   eta     (one wavefront per section): s = beta + tau u (also stored in
+//           CampBufs::s_keep when soft output is on), the K-PSK MMSE
 //           denoiser (max-shifted per section: the same function as the
 //           reference's global-max float128 form), the MAP decision of s and
 //           the section statistics
@@ -217,6 +218,7 @@ __global__ __launch_bounds__(256) void camp_eta(CampTables tb, CampBufs bf) {
     const cxd *cs = bf.constel;
     cxd *beta = bf.beta + (size_t)cw * tb.LM + (size_t)l * tb.M;
     const int jl0 = l * tb.M - c * tb.Mc;
+    cxd *keep = bf.s_keep ? bf.s_keep + (size_t)cw * tb.LM + (size_t)l * tb.M : nullptr;  // soft output: the last s
     double m = -INFINITY;
     MapBest mb = map_init();
     for (int e = lane; e < tb.M; e += 64) {
@@ -224,6 +226,7 @@ __global__ __launch_bounds__(256) void camp_eta(CampTables tb, CampBufs bf) {
         const cxd b = beta[e];
         const cxd s{b.x + tau * u.x, b.y + tau * u.y};  // sparc.py:972
         const cxd x{s.x / th, s.y / th};
+        if (keep) keep[e] = s;
         beta[e] = x;
         m = fmax(m, psk_shift(K, cs, x));
         map_update(K, cs, s, e, mb);

@@ -58,6 +58,7 @@ struct CampBufs {
     int32_t *sec_idx;    // [B][L] MAP location of s per section
     int32_t *sec_sym;    // [B][L] MAP constellation index of s per section
     const int32_t *true_idx, *true_sym;  // [B][L] or null
+    cxd *s_keep;         // [B][LM] natural order: eta also stores s = beta + tau u here (soft output), or null
 };
 
 int camp_prepare_fft(const CampTables &tb);  // once per plan: geometry check, LDS limit of the long-row pass B
@@ -79,5 +80,13 @@ int camp_launch_scatter(const CampTables &tb, const CampBufs &bf, const int32_t 
 int camp_launch_count(const int32_t *map_idx, const int32_t *map_sym, const int32_t *true_idx, const int32_t *true_sym,
                       const int32_t *t_final, int B, int L, int logM, int logK, int64_t *counts, int32_t *rows,
                       hipStream_t s);
+// soft output (camp_llr.hip): bit probabilities / LLRs [B][llr_ld] of sections [l0, l0 + nl) from s [B][L M] and
+// tau [B][Lc] (null: s is x = s / tau already); M > 2048 is SG_ERR_UNSUPPORTED
+int camp_launch_llr(const cxd *s, const double *tau, int B, int L, int Lc, int M, int K, const cxd *constel, int l0,
+                    int nl, int llr_ld, int probs_only, double *llr, hipStream_t st);
+// camp_launch_bits_to_psk with row strides; word = idx << logK | bin2gray(sym) over [B][L] (sym may be null)
+int camp_launch_bits_to_psk_strided(const uint8_t *bits, size_t bit_stride, int B, int L, int logM, int logK,
+                                    int32_t *idx, int32_t *sym, size_t idx_stride, hipStream_t s);
+int camp_launch_pack(const int32_t *idx, const int32_t *sym, int B, int L, int logK, int32_t *word, hipStream_t s);
 
 }  // namespace sg

@@ -1,0 +1,167 @@
+// Soft output of the complex AMP engine (DESIGN.md "Soft output of the complex
+// engine") and the two small kernels a concatenated K-PSK SPARC + LDPC
+// campaign needs around it, double precision.
+//
+// For K >= 2 the engine's final beta is the conditional mean sum_k p(j,k) c_k,
+// not a posterior, so the bit marginals come from the joint posterior over
+// (location j, symbol k) of the last effective observation s (kept by camp_eta
+// in CampBufs::s_keep) and its tau:
+//   p(j,k) ~ exp(Re(x_j conj c_k)),  x = s / (tau / 2)   (sparc.py:402-465)
+// A section carries log2 M MSB-first location bits, then log2 K Gray-coded
+// symbol bits (msg_vector_2_bin_arr, sparc.py:366-400); P(bit = 0) is the sum
+// of p over the (j, k) whose bit is clear.  The clip and the log are ldpc_bp's
+// (sparc_new.py:1167-1169).
+#include <algorithm>
+
+#include "amp_cfft.hpp"
+
+namespace sg {
+namespace {
+
+constexpr int LLR_HI = 5;   // location bits above the six lane bits (M <= 2048)
+constexpr int LLR_SYM = 6;  // symbol bits (K <= 64)
+
+__device__ __forceinline__ int bin_to_gray(int b) { return b ^ (b >> 1); }  // sparc.py:206-211
+
+// exponent argument of (entry x, symbol k): Re x for K = 1, else Re(x conj c_k).  The host's constellation is
+// exact for K = 2 and K = 4, so this one form equals the specialised ones of psk_terms (amp_cfft.hip).
+__device__ __forceinline__ double llr_arg(int K, const cxd *__restrict__ c, cxd x, int k) {
+    return K == 1 ? x.x : x.x * c[k].x + x.y * c[k].y;
+}
+
+// One wavefront per section, lane owns entries e = lane, lane + 64, ...: two
+// passes over the section (the maximum, then the accumulation) with no
+// per-entry register arrays, so every M up to 2048 runs in the same few
+// registers.  Per lane, in double: the total, the partial sums of the location
+// bits 6 and up (over the e whose bit of e >> 6 is clear) and of the symbol
+// bits (over the k whose Gray code has the bit clear).  The six low location
+// bits are lane-masked wave sums of the lanes' totals.  Fixed xor-butterfly
+// reductions, no atomics: the output is the same bits on every run.
+// s [B][LM] natural order; tau [B][Lc] (x = s / (tau / 2)) or null (x = s).
+__global__ __launch_bounds__(256) void camp_llr_kernel(const cxd *__restrict__ sbuf, const double *__restrict__ taubuf,
+                                                       int L, int Lc, int M, int K, const cxd *__restrict__ cs, int l0,
+                                                       int nl, int logM, int logK, int llr_ld, int probs_only,
+                                                       double *__restrict__ llr) {
+    const int lane = threadIdx.x & 63;
+    const int li = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int cw = blockIdx.y;
+    if (li >= nl) return;
+    const int l = l0 + li;
+    const double th = taubuf ? taubuf[(size_t)cw * Lc + l / (L / Lc)] / 2 : 1.0;  // s is complex: sparc.py:417-418
+    const cxd *s = sbuf + ((size_t)cw * L + l) * M;
+    double m = -INFINITY;
+    for (int e = lane; e < M; e += 64) {
+        const cxd x{s[e].x / th, s[e].y / th};
+        for (int k = 0; k < K; ++k) m = fmax(m, llr_arg(K, cs, x, k));
+    }
+    m = wave_max(m);
+    double tot = 0.0, hp[LLR_HI] = {0.0, 0.0, 0.0, 0.0, 0.0}, sp[LLR_SYM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int e = lane; e < M; e += 64) {
+        const cxd x{s[e].x / th, s[e].y / th};
+        double we = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double w = exp(llr_arg(K, cs, x, k) - m);
+            const int g = bin_to_gray(k);
+            we += w;
+#pragma unroll
+            for (int i = 0; i < LLR_SYM; ++i)
+                if (i < logK && ((g >> (logK - 1 - i)) & 1) == 0) sp[i] += w;  // MSB first
+        }
+        tot += we;
+#pragma unroll
+        for (int h = 0; h < LLR_HI; ++h)
+            if ((((e >> 6) >> h) & 1) == 0) hp[h] += we;
+    }
+    const double total = wave_sum(tot);
+    double out = 0.0;
+    for (int pos = 0; pos < logM; ++pos) {
+        const int bit = logM - 1 - pos;  // MSB first
+        double p = ((lane >> bit) & 1) == 0 ? tot : 0.0;
+#pragma unroll
+        for (int h = 0; h < LLR_HI; ++h)
+            if (bit == 6 + h) p = hp[h];
+        p = wave_sum(p);
+        if (lane == pos) out = p;
+    }
+#pragma unroll
+    for (int i = 0; i < LLR_SYM; ++i) {
+        if (i < logK) {
+            const double p = wave_sum(sp[i]);
+            if (lane == logM + i) out = p;
+        }
+    }
+    if (lane < logM + logK) {
+        const double p = out / total;
+        const double eps = 1e-15;
+        const double pc = fmin(fmax(p, eps), 1.0 - eps);  // ldpc_bp's clip (sparc_new.py:1167)
+        llr[(size_t)cw * llr_ld + (size_t)li * (logM + logK) + lane] = probs_only ? p : log(pc) - log(1.0 - pc);
+    }
+}
+
+// bits_to_psk_sections_kernel (camp_campaign.hip) with row strides: codeword b's bits at bits + b * bit_stride,
+// its L locations / constellation indices at idx / sym + b * idx_stride
+__device__ __forceinline__ int gray_to_bin(int g) {  // sparc.py:214-223
+    for (int m = g >> 1; m; m >>= 1) g ^= m;
+    return g;
+}
+__global__ __launch_bounds__(256) void bits_to_psk_strided_kernel(const uint8_t *__restrict__ bits, size_t bit_stride,
+                                                                  int L, int logM, int logK, int32_t *__restrict__ idx,
+                                                                  int32_t *__restrict__ sym, size_t idx_stride) {
+    const int b = blockIdx.y, per = logM + logK;
+    for (int l = blockIdx.x * blockDim.x + threadIdx.x; l < L; l += gridDim.x * blockDim.x) {
+        const uint8_t *x = bits + (size_t)b * bit_stride + (size_t)l * per;
+        int v = 0, g = 0;
+        for (int j = 0; j < logM; ++j) v = (v << 1) | (x[j] & 1);
+        for (int j = 0; j < logK; ++j) g = (g << 1) | (x[logM + j] & 1);
+        idx[(size_t)b * idx_stride + l] = v;
+        if (sym) sym[(size_t)b * idx_stride + l] = gray_to_bin(g);
+    }
+}
+
+// word = idx << logK | bin2gray(sym): the section's message bits as one integer
+__global__ __launch_bounds__(256) void psk_pack_kernel(const int32_t *__restrict__ idx, const int32_t *__restrict__ sym,
+                                                       size_t total, int logK, int32_t *__restrict__ word) {
+    const unsigned mK = (1u << logK) - 1u;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const unsigned g = sym ? (unsigned)bin_to_gray(sym[i]) & mK : 0u;
+        word[i] = (int32_t)(((unsigned)idx[i] << logK) | g);
+    }
+}
+
+unsigned grid_of(size_t items) { return (unsigned)std::max<size_t>(1, std::min<size_t>(1024, (items + 255) / 256)); }
+
+}  // namespace
+
+// s [B][L*M] natural order and tau [B][Lc] (or null: s is already x) on the device; the caller has checked the
+// section range, llr_ld >= nl (log2 M + log2 K), K a power of two <= CAMP_MAX_K and M a power of two >= 2
+int camp_launch_llr(const cxd *s, const double *tau, int B, int L, int Lc, int M, int K, const cxd *constel, int l0,
+                    int nl, int llr_ld, int probs_only, double *llr, hipStream_t st) {
+    if (M > 2048) return fail(SG_ERR_UNSUPPORTED, "bit LLRs of sections of M = %d > 2048 entries", M);
+    if (B <= 0 || nl <= 0) return SG_OK;
+    int logM = 0, logK = 0;
+    while ((1 << logM) < M) ++logM;
+    while ((1 << logK) < K) ++logK;
+    hipLaunchKernelGGL(camp_llr_kernel, dim3((nl + 3) / 4, B), dim3(256), 0, st, s, tau, L, Lc, M, K, constel, l0, nl,
+                       logM, logK, llr_ld, probs_only, llr);
+    SG_HIP(hipGetLastError());
+    return SG_OK;
+}
+
+int camp_launch_bits_to_psk_strided(const uint8_t *bits, size_t bit_stride, int B, int L, int logM, int logK,
+                                    int32_t *idx, int32_t *sym, size_t idx_stride, hipStream_t s) {
+    if (B <= 0 || L <= 0) return SG_OK;
+    hipLaunchKernelGGL(bits_to_psk_strided_kernel, dim3(grid_of((size_t)L), B), dim3(256), 0, s, bits, bit_stride, L,
+                       logM, logK, idx, sym, idx_stride);
+    SG_HIP(hipGetLastError());
+    return SG_OK;
+}
+
+int camp_launch_pack(const int32_t *idx, const int32_t *sym, int B, int L, int logK, int32_t *word, hipStream_t s) {
+    const size_t total = (size_t)B * L;
+    if (total == 0) return SG_OK;
+    hipLaunchKernelGGL(psk_pack_kernel, dim3(grid_of(total)), dim3(256), 0, s, idx, sym, total, logK, word);
+    SG_HIP(hipGetLastError());
+    return SG_OK;
+}
+
+}  // namespace sg

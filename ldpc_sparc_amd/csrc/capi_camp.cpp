@@ -28,6 +28,11 @@ struct sg_camp_plan {
     int32_t *active = nullptr, *sec_idx = nullptr, *sec_sym = nullptr, *true_idx = nullptr, *true_sym = nullptr,
             *t_final = nullptr;
     std::vector<cxd> h_constel;  // what `constel` holds (set_constel)
+    // soft output (sg_camp_soft_output): s_keep is carved from ws by the next ensure_ws; last_B / last_K of the
+    // last decode that filled it, 0 before any and after whatever overwrites or may move the workspace
+    bool soft = false;
+    cxd *s_keep = nullptr;
+    int last_B = 0, last_K = 0;
 };
 
 namespace {
@@ -61,11 +66,12 @@ std::vector<cxd> twiddles(int len) {  // exp(-2 pi i e / len)
 }
 
 int ensure_ws(sg_camp_plan *p, int B, int t_max) {
-    if (p->ws && B <= p->ws_B && t_max <= p->ws_tmax) return SG_OK;
+    if (p->ws && B <= p->ws_B && t_max <= p->ws_tmax && (!p->soft || p->s_keep)) return SG_OK;
     B = std::max(B, p->ws_B);
     t_max = std::max(t_max, p->ws_tmax);
     if (p->ws) hipFree(p->ws);
     p->ws = nullptr;
+    p->s_keep = nullptr;
     p->ws_B = p->ws_tmax = 0;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -83,6 +89,7 @@ int ensure_ws(sg_camp_plan *p, int B, int t_max) {
                  o_nm = take(sB * t_max * p->Lc * 8), o_act = take(sB * 4), o_si = take(sB * p->L * 4),
                  o_sy = take(sB * p->L * 4), o_ti = take(sB * p->L * 4), o_ts = take(sB * p->L * 4),
                  o_tf = take(sB * 4);
+    const size_t o_keep = p->soft ? take(sB * p->LM * sizeof(cxd)) : 0;  // 16 LM bytes per codeword, only when on
     SG_HIP(hipMalloc(&p->ws, off));
     char *b = (char *)p->ws;
     p->beta = (cxd *)(b + o_beta); p->y = (cxd *)(b + o_y); p->z = (cxd *)(b + o_z);
@@ -93,6 +100,7 @@ int ensure_ws(sg_camp_plan *p, int B, int t_max) {
     p->gamma = (double *)(b + o_gam); p->bco = (double *)(b + o_bco); p->nmse = (double *)(b + o_nm);
     p->active = (int32_t *)(b + o_act); p->sec_idx = (int32_t *)(b + o_si); p->sec_sym = (int32_t *)(b + o_sy);
     p->true_idx = (int32_t *)(b + o_ti); p->true_sym = (int32_t *)(b + o_ts); p->t_final = (int32_t *)(b + o_tf);
+    if (p->soft) p->s_keep = (cxd *)(b + o_keep);
     p->ws_B = B;
     p->ws_tmax = t_max;
     return SG_OK;
@@ -118,6 +126,7 @@ CampBufs bufs(const sg_camp_plan *p, int B, int K) {
     bf.phi = p->phi; bf.tau = p->tau; bf.active = p->active;
     bf.sec_sumsq = p->sec_sumsq; bf.sec_err = p->sec_err; bf.sec_idx = p->sec_idx; bf.sec_sym = p->sec_sym;
     bf.true_idx = nullptr; bf.true_sym = nullptr;
+    bf.s_keep = nullptr;  // only a decode with soft output on sets it
     return bf;
 }
 
@@ -256,6 +265,7 @@ int sg_camp_apply(sg_camp_plan *p, int transpose, const double *in, int B, doubl
     SG_CHECK_ARG(p && in && out, "null argument");
     SG_CHECK_ARG(B >= 0, "negative batch");
     if (B == 0) return SG_OK;
+    p->last_B = p->last_K = 0;  // works in the decode's buffers
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = lib_stream();
     SG_TRY(ensure_ws(p, B, 2));
@@ -281,6 +291,7 @@ int sg_camp_decode_device(sg_camp_plan *p, const void *d_y, int B, int K, const 
                           double *d_psi, void *stream) {
     SG_TRY(ensure_device());
     SG_CHECK_ARG(p, "plan is NULL");
+    p->last_B = p->last_K = 0;  // every decode call resets the soft-output state; a completed one sets it below
     SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B, "batch must be in [0, 65535]");
     if (B == 0) return SG_OK;
     SG_CHECK_ARG(d_y, "null received words");
@@ -304,6 +315,7 @@ int sg_camp_decode_device(sg_camp_plan *p, const void *d_y, int B, int K, const 
     bf.sec_sym = d_map_sym ? d_map_sym : p->sec_sym;
     bf.true_idx = d_true_idx;
     bf.true_sym = (K > 1 && d_true_idx) ? d_true_sym : nullptr;
+    bf.s_keep = p->soft ? p->s_keep : nullptr;
     AmpScalars sc;
     sc.psi = d_psi ? d_psi : p->psi; sc.psi_prev = p->psi_prev; sc.phi_prev = p->phi_prev; sc.gamma = p->gamma;
     sc.bcoef = p->bco;
@@ -331,6 +343,7 @@ int sg_camp_decode_device(sg_camp_plan *p, const void *d_y, int B, int K, const 
             if (na == 0) break;
         }
     }
+    if (p->soft) { p->last_B = B; p->last_K = K; }
     return SG_OK;
 }
 
@@ -340,6 +353,7 @@ int sg_camp_decode(sg_camp_plan *p, const double *y, int B, int K, const double 
                    int32_t *map_sym, int32_t *t_final, double *nmse, double *psi) {
     SG_TRY(ensure_device());
     SG_CHECK_ARG(p, "plan is NULL");
+    p->last_B = p->last_K = 0;
     SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B, "batch must be in [0, 65535]");
     if (B == 0) return SG_OK;
     SG_CHECK_ARG(y && map_idx && t_final && nmse && psi, "null host buffer");
@@ -396,6 +410,7 @@ int sg_camp_encode_device(sg_camp_plan *p, int K, const double *constel, const i
     SG_CHECK_ARG(psk_order_ok(K), "K must be 1 or a power of two");
     if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
     SG_CHECK_ARG(K == 1 || (constel && d_sym), "K > 1 needs the constellation and d_sym");
+    p->last_B = p->last_K = 0;  // overwrites beta
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = pick_stream(stream);
     SG_TRY(ensure_ws(p, B, 2));
@@ -479,6 +494,135 @@ int sg_section_map_psk(const double *sv, int L, int M, int K, const double *cons
     hipFree(d);
     if (rc == SG_OK && sym) std::memcpy(sym, hsym.data(), (size_t)L * sizeof(int32_t));
     return rc;
+}
+
+// ------------------------------------------------------------------ soft output
+int sg_camp_soft_output(sg_camp_plan *p, int on) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    p->soft = on != 0;
+    p->last_B = p->last_K = 0;  // s_keep is filled by the next decode
+    return SG_OK;
+}
+
+}  // extern "C"
+
+// Every refusal of sg_camp_llr*: the state the last decode left must be the one asked for.
+static int camp_llr_checks(sg_camp_plan *p, int B, int K, const double *constel, int l0, int nl, long long llr_ld,
+                           int *per_out) {
+    SG_CHECK_ARG(p->soft, "soft output is off: sg_camp_soft_output(plan, 1) before the decode");
+    SG_CHECK_ARG(p->last_B > 0 && p->s_keep, "no decode through this plan yet (or its state was overwritten)");
+    SG_CHECK_ARG(B == p->last_B, "B = %d, but the last decode held %d codewords", B, p->last_B);
+    SG_CHECK_ARG(K == p->last_K, "K = %d, but the last decode ran K = %d", K, p->last_K);
+    SG_CHECK_ARG(K == 1 || constel, "K > 1 needs the constellation");
+    SG_CHECK_ARG(l0 >= 0 && nl >= 0 && l0 <= p->L && nl <= p->L - l0, "sections [%d, %d + %d) outside [0, %d]", l0, l0,
+                 nl, p->L);
+    SG_CHECK_ARG(p->M >= 2, "section size M = %d must be a power of two >= 2", p->M);
+    if (p->M > 2048) return fail(SG_ERR_UNSUPPORTED, "bit LLRs of sections of M = %d > 2048 entries", p->M);
+    int per = 0;
+    while ((1 << per) < p->M) ++per;
+    for (int k = 1; k < K; k <<= 1) ++per;
+    SG_CHECK_ARG(llr_ld >= (long long)nl * per, "llr_ld = %lld < nl (log2 M + log2 K) = %lld", llr_ld,
+                 (long long)nl * per);
+    *per_out = per;
+    return SG_OK;
+}
+
+extern "C" {
+
+int sg_camp_llr_device(sg_camp_plan *p, int B, int K, const double *constel, int l0, int nl, int llr_ld,
+                       int probs_only, double *d_llr, void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p && d_llr, "null argument");
+    int per = 0;
+    SG_TRY(camp_llr_checks(p, B, K, constel, l0, nl, llr_ld, &per));
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = pick_stream(stream);
+    SG_TRY(set_constel(p, K, constel, s));  // the decode's own: nothing moves
+    return camp_launch_llr(p->s_keep, p->tau, B, p->L, p->Lc, p->M, K, p->constel, l0, nl, llr_ld, probs_only, d_llr, s);
+}
+
+int sg_camp_llr(sg_camp_plan *p, int B, int K, const double *constel, int l0, int nl, int probs_only, double *out) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p && out, "null argument");
+    int per = 0;
+    SG_TRY(camp_llr_checks(p, B, K, constel, l0, nl, INT32_MAX, &per));
+    const size_t ld = (size_t)nl * per, nv = (size_t)B * ld;
+    if (nv == 0) return SG_OK;
+    SG_CHECK_ARG(ld <= (size_t)INT32_MAX, "too many bits per codeword");
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = lib_stream();
+    double *d = nullptr;  // staging of its own: the plan's buffers hold the state being read
+    SG_HIP(hipMalloc((void **)&d, nv * sizeof(double)));
+    auto run = [&]() -> int {
+        SG_TRY(set_constel(p, K, constel, s));
+        SG_TRY(camp_launch_llr(p->s_keep, p->tau, B, p->L, p->Lc, p->M, K, p->constel, l0, nl, (int)ld, probs_only, d,
+                               s));
+        SG_HIP(hipMemcpyAsync(out, d, nv * sizeof(double), hipMemcpyDeviceToHost, s));
+        SG_HIP(hipStreamSynchronize(s));
+        return SG_OK;
+    };
+    const int rc = run();
+    hipFree(d);
+    return rc;
+}
+
+// x as sg_section_mmse_psk; out [L][log2 M + log2 K]: P(bit = 0) of the section bits, or their clipped LLRs
+int sg_section_llr_psk(const double *x, int L, int M, int K, const double *constel, int x_is_complex, int probs_only,
+                       double *out) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(x && out && L >= 0, "bad arguments");
+    SG_CHECK_ARG(M >= 2 && (M & (M - 1)) == 0, "section size M = %d must be a power of two >= 2", M);
+    SG_CHECK_ARG(psk_order_ok(K) && (K == 1 || constel), "K must be 1 or a power of two with its constellation");
+    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    if (M > 2048) return fail(SG_ERR_UNSUPPORTED, "bit LLRs of sections of M = %d > 2048 entries", M);
+    if (L == 0) return SG_OK;
+    hipStream_t s = lib_stream();
+    int per = 0;
+    while ((1 << per) < M) ++per;
+    for (int k = 1; k < K; k <<= 1) ++per;
+    const size_t N = (size_t)L * M, nout = (size_t)L * per;
+    std::vector<cxd> hx(N);
+    for (size_t i = 0; i < N; ++i) hx[i] = x_is_complex ? cxd{x[2 * i], x[2 * i + 1]} : cxd{x[i], 0.0};
+    cxd *d = nullptr;
+    SG_HIP(hipMalloc((void **)&d, (N + CAMP_MAX_K) * sizeof(cxd) + nout * sizeof(double)));
+    cxd *dc = d + N;
+    double *dout = (double *)(dc + CAMP_MAX_K);
+    auto run = [&]() -> int {
+        SG_HIP(hipMemcpyAsync(d, hx.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
+        if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
+        // one "codeword" of L sections, x given: no tau
+        SG_TRY(camp_launch_llr(d, nullptr, 1, L, 1, M, K, dc, 0, L, (int)nout, probs_only, dout, s));
+        SG_HIP(hipMemcpyAsync(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost, s));
+        SG_HIP(hipStreamSynchronize(s));
+        return SG_OK;
+    };
+    const int rc = run();
+    hipFree(d);
+    return rc;
+}
+
+int sg_bits_to_psk_sections_strided_device(const uint8_t *d_bits, size_t bit_stride, int B, int L, int logM, int logK,
+                                           int32_t *d_idx, int32_t *d_sym, size_t idx_stride, void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(d_bits && d_idx, "null device buffer");
+    SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B && L >= 0, "bad (B, L)");
+    SG_CHECK_ARG(logM >= 0 && logM <= 30 && logK >= 0 && logK <= 30 && logM + logK >= 1, "bad (logM, logK)");
+    SG_CHECK_ARG(logK == 0 || d_sym, "logK > 0 needs d_sym");
+    SG_CHECK_ARG(bit_stride >= (size_t)L * (logM + logK) && idx_stride >= (size_t)L, "strides shorter than a row");
+    if (!B || !L) return SG_OK;
+    return camp_launch_bits_to_psk_strided(d_bits, bit_stride, B, L, logM, logK, d_idx, d_sym, idx_stride,
+                                           pick_stream(stream));
+}
+
+int sg_psk_pack_sections_device(const int32_t *d_idx, const int32_t *d_sym, int B, int L, int logK, int32_t *d_word,
+                                void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(d_idx && d_word, "null device buffer");
+    SG_CHECK_ARG(B >= 0 && L >= 0, "bad (B, L)");
+    SG_CHECK_ARG(logK >= 0 && logK <= 30, "bad logK");
+    SG_CHECK_ARG(logK == 0 || d_sym, "logK > 0 needs d_sym");
+    return camp_launch_pack(d_idx, logK ? d_sym : nullptr, B, L, logK, d_word, pick_stream(stream));
 }
 
 }  // extern "C"

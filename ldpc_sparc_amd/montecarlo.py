@@ -456,11 +456,16 @@ class ConcatTrial:
     default_rng([seed, p, b]) on the host (rng "host"), so results do not
     depend on the rank count.  Counters [codewords, user-bit errors, codeword errors,
     unprotected-bit errors, protected-bit errors]; per-block BERs of this
-    rank are kept in block_ber[point]."""
+    rank are kept in block_ber[point].  With `granule` (a divisor of the
+    block) a block is drawn and decoded as block / granule batches of that
+    many codewords, batch g of the point keyed like block g above: the
+    counters then do not depend on the block size either."""
 
-    def __init__(self, pipe, awgn_vars, seed=0, rng="device"):
+    def __init__(self, pipe, awgn_vars, seed=0, rng="device", granule=None):
         self.pipe, self.vars, self.seed = pipe, list(awgn_vars), int(seed)
-        self.user_bits = pipe.L_unp * pipe.logM + pipe.mults * pipe.c.K
+        self.granule = None if granule is None else int(granule)
+        # bits of a section: log2 M, plus log2 K on a K-PSK pipeline (pipeline.CsparcConcatPipeline)
+        self.user_bits = pipe.L_unp * getattr(pipe, "bits_per_section", pipe.logM) + pipe.mults * pipe.c.K
         self.block_ber = {}
         if rng not in ("host", "device"):
             raise ValueError("rng must be 'host' (numpy default_rng([seed, point, block])) or 'device' (Philox)")
@@ -468,28 +473,37 @@ class ConcatTrial:
 
     def __call__(self, point, first_block, n_blocks, block):
         tot = np.zeros(NC, dtype=np.int64)
+        size = self.granule or block
+        if size <= 0 or block % size:
+            raise ValueError(f"granule {size} must divide the block of {block} codewords")
+        per = block // size
         for b in range(first_block, first_block + n_blocks):
-            if self.rng == "device":  # throughput mode: no host encode or host RNG in the loop
-                self.pipe.make_batch_device(block, self.vars[point], self.seed, (int(point) << 32) | int(b))
-            else:
-                self.pipe.make_batch(block, self.vars[point], np.random.default_rng([self.seed, int(point), int(b)]))
-            self.pipe.reset_counts()
-            self.pipe.decode()
-            c = self.pipe.counts()
+            c = np.zeros(NC, dtype=np.int64)
+            for g in range(b * per, (b + 1) * per):  # (no granule: the block itself, g = b)
+                if self.rng == "device":  # throughput mode: no host encode or host RNG in the loop
+                    self.pipe.make_batch_device(size, self.vars[point], self.seed, (int(point) << 32) | int(g))
+                else:
+                    self.pipe.make_batch(size, self.vars[point], np.random.default_rng([self.seed, int(point), int(g)]))
+                self.pipe.reset_counts()
+                self.pipe.decode()
+                c += self.pipe.counts()
             tot += c
             self.block_ber.setdefault(point, []).append(float(c[1]) / (c[0] * self.user_bits))
         return tot
 
 
-def concat_checkpoint_tag(L, M, n, design="dense"):
-    """Checkpoint tag of a concat_ber_sweep: concat_L.. (dense), concat_dct_L.. (DCT design)."""
+def concat_checkpoint_tag(L, M, n, design="dense", K=1):
+    """Checkpoint tag of a concat_ber_sweep: concat_L.. (dense), concat_dct_L.. (DCT design),
+    concat_fft_L.._M.._K.. (complex FFT design with K-PSK; K = 1 unmodulated)."""
+    if design == "fft":
+        return f"concat_fft_L{L}_M{M}_K{K}_n{n}"
     return f"concat_L{L}_M{M}_n{n}" if design == "dense" else f"concat_{design}_L{L}_M{M}_n{n}"
 
 
 def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, block=256, blocks_per_round=None,
                      rank=0, world=1, agg=None, design_seed=0, seed=0, t_max=25, bp_its=200, precision="f32",
                      ldpc=("802.11n", "1/2", 81), min_errors=None, checkpoint_dir=None, npz_file=None, rng="device",
-                     trial=None, max_rounds=None, on_point=None, design="dense"):
+                     trial=None, max_rounds=None, on_point=None, design="dense", K=1, granule=None):
     """BER / FER of concatenated SPARC + LDPC against Eb/N0 (the experiment of
     ldpc_sparc/performance_plots_general.py:100-138 for the plain concatenated
     decoder), `codewords` per point sharded over the ranks.  Eb/N0 to noise as
@@ -507,22 +521,44 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
     the sub-sampled DCT design drawn from `design_seed`, decoded by the public
     AMP with early stopping (pipeline.DctConcatPipeline).  A DCT sweep keeps
     its checkpoints under its own tag and parameters, so neither kind resumes
-    the other."""
+    the other.  "fft" is the complex sub-sampled FFT design with K-PSK
+    modulated sections (`K` = 1: unmodulated; pipeline.CsparcConcatPipeline,
+    double precision only: precision="f32" raises NotImplementedError): a
+    section carries log2 M + log2 K bits, and the n channel uses are complex.
+    For complex noise of variance awgn_var per sample N0 = awgn_var, so there
+    Eb/N0 = P / (R_overall awgn_var), awgn_var = P / (R_overall 10^(Eb/N0 / 10))
+    with R_overall = user bits / n; the real sweeps keep their factor 2
+    (N0 = 2 awgn_var).  Its checkpoints carry the design name and K in tag and
+    parameters, so a resumed real or dense sweep never reads them.  `granule`
+    (ConcatTrial) fixes the size of the batches a block is drawn in, which
+    makes the counters independent of `block`; it then is part of the
+    checkpointed parameters."""
     from .ldpc import code
-    if design not in ("dense", "dct"):
-        raise ValueError(f"design must be 'dense' or 'dct', not {design!r}")
+    if design not in ("dense", "dct", "fft"):
+        raise ValueError(f"design must be 'dense', 'dct' or 'fft', not {design!r}")
+    K = int(K)
+    if design != "fft" and K != 1:
+        raise ValueError("K-PSK modulation needs the complex design: design='fft'")
     agg = agg or Aggregator()
     logM = int(np.log2(M))
-    user_bits = L_unprotected * logM + mults * code(*ldpc).K
+    per = logM + (int(round(np.log2(K))) if design == "fft" else 0)
+    user_bits = L_unprotected * per + mults * code(*ldpc).K
     r_overall = user_bits / n
-    vars_ = [P / (2 * r_overall * 10 ** (e / 10)) for e in ebn0_db]
+    if design == "fft":  # complex samples: N0 = awgn_var
+        vars_ = [P / (r_overall * 10 ** (e / 10)) for e in ebn0_db]
+    else:
+        vars_ = [P / (2 * r_overall * 10 ** (e / 10)) for e in ebn0_db]
     if trial is None:
-        from .pipeline import ConcatPipeline, DctConcatPipeline
-        make = DctConcatPipeline if design == "dct" else ConcatPipeline
-        pipe = make(L, M, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed, precision=precision,
-                    t_max=t_max, bp_its=bp_its)
-        assert pipe.L_unp * pipe.logM + pipe.mults * pipe.c.K == user_bits
-        trial = ConcatTrial(pipe, vars_, seed, rng)
+        from .pipeline import ConcatPipeline, CsparcConcatPipeline, DctConcatPipeline
+        if design == "fft":
+            pipe = CsparcConcatPipeline(L, M, K, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed,
+                                        precision=precision, t_max=t_max, bp_its=bp_its)
+        else:
+            make = DctConcatPipeline if design == "dct" else ConcatPipeline
+            pipe = make(L, M, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed, precision=precision,
+                        t_max=t_max, bp_its=bp_its)
+        trial = ConcatTrial(pipe, vars_, seed, rng, granule)
+        assert trial.user_bits == user_bits
     bpr = blocks_per_round or max(1, world)
     out = []
     for point, e in enumerate(ebn0_db):
@@ -537,9 +573,13 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
             params["blocks_per_round"] = bpr
         if design != "dense":  # (dense sweeps keep the parameters their checkpoints were written with)
             params["design"] = design
+        if design == "fft":
+            params["K"] = K
+        if granule is not None:
+            params["granule"] = int(granule)
         tot = run_point(trial, point, block=block, blocks_per_round=bpr, rank=rank, world=world, agg=agg,
                         min_errors=min_errors, max_units=codewords, checkpoint_dir=checkpoint_dir,
-                        tag=concat_checkpoint_tag(L, M, n, design), params=params, max_rounds=max_rounds)
+                        tag=concat_checkpoint_tag(L, M, n, design, K), params=params, max_rounds=max_rounds)
         out.append({"ebn0_db": float(e), "awgn_var": vars_[point], "codewords": int(tot[0]),
                     "ber": float(tot[1]) / (tot[0] * user_bits) if tot[0] else None,
                     "fer": float(tot[2]) / tot[0] if tot[0] else None,

@@ -234,3 +234,158 @@ class DctIntegratedPipeline(DctConcatPipeline):
         _native.check(lib.sg_concat_count_errors_device(self.prec, self.d_true.ptr, self.d_true.ptr, B, self.L, 0,
                                                         self.logM, self.d_app.ptr, self.d_info.ptr, self.mults, c.N,
                                                         c.K, self.d_cnt.ptr, None))
+
+
+class CsparcConcatPipeline(ConcatPipeline):
+    """The concatenated scheme on a complex SPARC with the sub-sampled FFT
+    design (sparc.py:593-646), unmodulated (K = 1) or K-PSK modulated (K up to
+    64): a section carries log2 M location bits and log2 K Gray-coded symbol
+    bits, and the last L - L_unprotected sections hold `mults` LDPC blocks.
+    Double precision only, like the rest of the complex surface.  Same
+    methods and counter layout as ConcatPipeline, so montecarlo.ConcatTrial
+    takes it unchanged; `bits_per_section` = log2 M + log2 K stands where the
+    real pipelines have logM.
+
+    `op` is a sparc.ComplexDesignOperator over (L, M, n); by default the flat
+    design W = P with the orders generate_ordering(..., csparc=True) draws
+    from `design_seed`.
+
+    decode() per batch, nothing returning to the host but the five counters:
+    sg_camp_decode_device with soft output on (MAP location and symbol of every
+    section) -> sg_psk_pack_sections_device (the section's bits as one word) ->
+    sg_camp_llr_device over the protected sections (bit LLRs from the joint
+    posterior over (location, symbol) of the decoder's last s and tau) ->
+    sg_ldpc_decode_device -> sg_concat_count_errors_device on the words."""
+
+    def __init__(self, L, M, K, n, P, L_unprotected, mults, ldpc=("802.11n", "1/2", 81), design_seed=0,
+                 precision="f64", t_max=25, rtol=1e-6, phi_method=1, bp_dectype="sumprod2", bp_its=200, op=None):
+        from . import sparc
+        if precision != "f64":
+            raise NotImplementedError("complex SPARCs run in double precision only (precision='f64')")
+        self.L, self.M, self.K, self.n, self.P = int(L), int(M), int(K), int(n), float(P)
+        sparc._check_psk(self.K)
+        self.logM = int(round(np.log2(self.M)))
+        self.logK = int(round(np.log2(self.K)))
+        self.bits_per_section = self.logM + self.logK
+        self.L_unp, self.mults = int(L_unprotected), int(mults)
+        self.c = code(*ldpc)
+        assert (self.L - self.L_unp) * self.bits_per_section == self.mults * self.c.N, \
+            "protected sections must hold the blocks"
+        self.prec, self.dt = _native.SG_F64, np.float64
+        self.t_max, self.bp_dectype, self.bp_its = int(t_max), bp_dectype, int(bp_its)
+        self.rtol, self.phi_method = float(rtol), int(phi_method)
+        if op is None:
+            W = np.array(float(P))
+            o0, o1 = sparc.generate_ordering(W, self.n, self.L * self.M, design_seed, csparc=True)
+            op = sparc.ComplexDesignOperator(W, self.L, self.M, self.n, o0, o1)
+        if not op.csparc or (op.L, op.M, op.n) != (self.L, self.M, self.n):
+            raise ValueError(f"op must be a ComplexDesignOperator with L = {self.L}, M = {self.M}, n = {self.n}")
+        self.op = op
+        self.constel = sparc._interleaved(sparc.psk_constel(self.K)) if self.K != 1 else None
+        self.plan = op.plan()
+        op.soft_output(True)
+        self.graph = self.c._device_graph()
+        self._cap = 0
+
+    def _ensure(self, B):
+        if B <= self._cap:
+            return
+        c, per = self.c, self.bits_per_section
+        self.d_y = _native.DeviceBuffer(B * self.n * 16)
+        self.d_x = _native.DeviceBuffer(B * self.n * 16)
+        self.d_idx = _native.DeviceBuffer(B * self.L * 4)    # decoded section words
+        self.d_true = _native.DeviceBuffer(B * self.L * 4)   # transmitted section words
+        self.d_tidx = _native.DeviceBuffer(B * self.L * 4)   # transmitted location / constellation index
+        self.d_tsym = _native.DeviceBuffer(B * self.L * 4)
+        self.d_midx = _native.DeviceBuffer(B * self.L * 4)   # MAP location / constellation index
+        self.d_msym = _native.DeviceBuffer(B * self.L * 4)
+        self.d_llr = _native.DeviceBuffer(B * self.mults * c.N * 8)
+        self.d_app = _native.DeviceBuffer(B * self.mults * c.N * 8)
+        self.d_it = _native.DeviceBuffer(B * self.mults * 4)
+        self.d_info = _native.DeviceBuffer(B * self.mults * c.K)
+        self.d_unp = _native.DeviceBuffer(max(1, B * self.L_unp * per))
+        self.d_cw = _native.DeviceBuffer(B * self.mults * c.N)
+        self.d_cnt = _native.DeviceBuffer(5 * 8)
+        self.d_tsym.zero()
+        self._cap = B
+
+    def _encode(self, B):
+        """d_true (words) and x = A beta0 [B, n] from the (location, symbol) pairs in d_tidx / d_tsym."""
+        lib = _native.lib()
+        _native.check(lib.sg_psk_pack_sections_device(self.d_tidx.ptr, self.d_tsym.ptr, B, self.L, self.logK,
+                                                      self.d_true.ptr, None))
+        _native.check(lib.sg_camp_encode_device(self.plan, self.K, _native.ptr(self.constel), self.d_tidx.ptr,
+                                                self.d_tsym.ptr, B, self.d_x.ptr, None))
+
+    def make_batch(self, B, awgn_var, rng):
+        """Random user bits -> LDPC blocks -> (location, symbol) per section
+        (bin_arr_2_msg_vector, sparc.py:330-364); x = A beta0 on the GPU;
+        y = x + CN(0, awgn_var) from the host RNG (real parts, then imaginary
+        parts).  Leaves y, the true section words and the information bits on
+        the device; returns (idx [B, L], sym [B, L], info [B * mults, K])."""
+        from . import sparc
+        self._ensure(B)
+        c, logM, per = self.c, self.logM, self.bits_per_section
+        unp = rng.integers(0, 2, (B, self.L_unp * per))
+        info = rng.integers(0, 2, (B * self.mults, c.K))
+        cw = c.encode_batch(info).reshape(B, self.mults * c.N)
+        bits = np.concatenate([unp, cw], axis=1).reshape(B, self.L, per).astype(np.int64)
+        idx = (bits[:, :, :logM] @ (1 << np.arange(logM)[::-1])).astype(np.int32)
+        sym = np.zeros((B, self.L), dtype=np.int32)
+        if self.logK:
+            sym = sparc.gray2bin(bits[:, :, logM:] @ (1 << np.arange(self.logK)[::-1])).astype(np.int32)
+        self.d_tidx.upload(idx)
+        self.d_tsym.upload(sym)
+        self.d_info.upload(info.reshape(B, -1).astype(np.uint8))
+        self._encode(B)
+        x = self.d_x.download(np.empty((B, self.n), np.complex128))
+        sd = np.sqrt(awgn_var / 2)
+        y = x + sd * rng.standard_normal(x.shape) + 1j * (sd * rng.standard_normal(x.shape))
+        self.d_y.upload(y)
+        self.B, self.awgn_var = B, float(awgn_var)
+        return idx, sym, info
+
+    def make_batch_device(self, B, awgn_var, seed, stream_id):
+        """The same batch generated on the GPU: Philox user bits of the
+        unprotected sections and of the LDPC information words, the device
+        LDPC encoder, the strided PSK bit mapper, x = A beta0, complex AWGN of
+        variance awgn_var (sqrt(awgn_var / 2) per real dimension).  The draw of
+        codeword b depends only on (seed, stream_id, b)."""
+        self._ensure(B)
+        c, lib, per = self.c, _native.lib(), self.bits_per_section
+        off = _native.offset
+        nu = self.L_unp * per
+        if nu:
+            _native.check(lib.sg_rng_bits_device(seed, stream_id, B, nu, self.d_unp.ptr, None))
+            _native.check(lib.sg_bits_to_psk_sections_strided_device(
+                self.d_unp.ptr, nu, B, self.L_unp, self.logM, self.logK, self.d_tidx.ptr, self.d_tsym.ptr, self.L,
+                None))
+        _native.check(lib.sg_rng_bits_device(seed ^ self._SEED_INFO, stream_id, B * self.mults, c.K, self.d_info.ptr,
+                                             None))
+        c.encode_device(self.d_info.ptr, B * self.mults, self.d_cw.ptr)
+        _native.check(lib.sg_bits_to_psk_sections_strided_device(
+            self.d_cw.ptr, self.mults * c.N, B, self.L - self.L_unp, self.logM, self.logK,
+            off(self.d_tidx.ptr, 4 * self.L_unp), off(self.d_tsym.ptr, 4 * self.L_unp), self.L, None))
+        self._encode(B)
+        _native.check(lib.sg_awgn_device(_native.SG_F64, seed, stream_id, self.d_x.ptr, B, 2 * self.n,
+                                         float(np.sqrt(awgn_var / 2)), self.d_y.ptr, None))
+        self.B, self.awgn_var = B, float(awgn_var)
+
+    def decode(self):
+        """One batch: returns nothing; counters accumulate in d_cnt."""
+        lib, c, B = _native.lib(), self.c, self.B
+        cs = _native.ptr(self.constel)
+        _native.check(lib.sg_camp_decode_device(self.plan, self.d_y.ptr, B, self.K, cs, None, None, self.awgn_var,
+                                                self.t_max, self.rtol, self.phi_method, self.d_midx.ptr,
+                                                self.d_msym.ptr, None, None, None, None))
+        _native.check(lib.sg_psk_pack_sections_device(self.d_midx.ptr, self.d_msym.ptr, B, self.L, self.logK,
+                                                      self.d_idx.ptr, None))
+        ld = self.mults * c.N
+        _native.check(lib.sg_camp_llr_device(self.plan, B, self.K, cs, self.L_unp, self.L - self.L_unp, ld, 0,
+                                             self.d_llr.ptr, None))
+        _native.check(lib.sg_ldpc_decode_device(self.graph, _native.DECTYPES[self.bp_dectype], self.prec,
+                                                self.d_llr.ptr, B * self.mults, self.bp_its, 0.7, self.d_app.ptr,
+                                                self.d_it.ptr, None))
+        _native.check(lib.sg_concat_count_errors_device(self.prec, self.d_idx.ptr, self.d_true.ptr, B, self.L,
+                                                        self.L_unp, self.bits_per_section, self.d_app.ptr,
+                                                        self.d_info.ptr, self.mults, c.N, c.K, self.d_cnt.ptr, None))

@@ -17,7 +17,9 @@ K-PSK modulated complex SPARCs (K up to 64) run on the complex engine
 (csrc/amp_cfft.hip) in double precision only: 'precision': 'f32' with a
 complex design raises NotImplementedError.  Also out of scope, raising
 NotImplementedError: real K=2 modulated SPARCs on the DCT engines, and K > 64.
-Monte-Carlo campaigns of complex SPARCs that stay on the GPU are
+Soft output of the complex engine: ComplexDesignOperator.soft_output() then
+camp_llr (bit LLRs of location and K-PSK symbol bits); section_llr_psk is the
+stand-alone function.  Monte-Carlo campaigns of complex SPARCs that stay on the GPU are
 montecarlo.CSparcTrial / csparc_ser_sweep; state evolution, K-PSK included, is
 sparc_se.py.
 """
@@ -383,6 +385,40 @@ def msg_vector_mmse_estimator(s, tau, M, K=1):
     return out
 
 
+def _section_bit_count(M, K):
+    return int(round(np.log2(M))) + (int(round(np.log2(K))) if K != 1 else 0)
+
+
+def section_llr_psk(s, tau, M, K=1, probs_only=False):
+    """Soft bits of the message vector behind s = beta + sqrt(tau) noise: per
+    section the log2 M MSB-first location bits, then the log2 K Gray-coded
+    K-PSK bits (the bit order of msg_vector_2_bin_arr), as the marginals of
+    the joint posterior over (location, symbol) that msg_vector_mmse_estimator
+    averages.  Returns float64 [L * (log2 M + log2 K)]: the LLRs
+    log p - log(1 - p) of p = P(bit = 0) clipped to [1e-15, 1 - 1e-15]
+    (ldpc_bp, sparc_new.py:1167-1169), or with probs_only the unclipped p.
+    s and tau as msg_vector_mmse_estimator (the caller's tau is left
+    unchanged); M a power of two in [2, 2048].  Evaluated on the GPU."""
+    assert type(s) == np.ndarray
+    assert s.size % M == 0
+    _check_psk(K)
+    _native.require_gpu()
+    cplx = np.iscomplexobj(s)
+    t = np.asarray(tau, dtype=np.float64) / 2 if cplx else np.asarray(tau, dtype=np.float64)
+    if K <= 2 or not cplx:
+        x = np.ascontiguousarray(s.real / t, dtype=np.float64)
+        xc = 0
+    else:
+        x = _interleaved(s.real / t + 1j * (s.imag / t))
+        xc = 1
+    L = s.size // M
+    out = np.empty(L * _section_bit_count(M, K))
+    c = _interleaved(psk_constel(K)) if K != 1 else None
+    _native.check(_native.lib().sg_section_llr_psk(_native.ptr(x), L, M, K, _native.ptr(c), xc,
+                                                   int(bool(probs_only)), _native.ptr(out)))
+    return out
+
+
 def msg_vector_map_estimator(s, M, K=1):
     """MAP estimate per section (sparc.py:467-512) on the GPU: the location
     (and for K>1 the K-PSK symbol) closest to s; first maximum wins."""
@@ -592,6 +628,12 @@ class ComplexDesignOperator(DesignOperator):
             self._plans[precision] = h
         return self._plans[precision]
 
+    def soft_output(self, on=True):
+        """Make the following decodes through this operator keep their last
+        effective observation s for camp_llr (sg_camp_soft_output): 16 L M
+        bytes per codeword of the batch, nothing while off (the default)."""
+        _native.check(_native.lib().sg_camp_soft_output(self.plan(), int(bool(on))))
+
     def __del__(self):
         for h in getattr(self, "_plans", {}).values():
             try:
@@ -714,6 +756,23 @@ def camp_decode_batch(Y, op, awgn_var, t_max, rtol=1e-6, phi_est_method=1, K=1, 
         int(t_max), float(rtol), int(phi_est_method), _native.ptr(map_idx), _native.ptr(map_sym),
         _native.ptr(t_final), _native.ptr(nmse), _native.ptr(psi)))
     return map_idx, map_sym, t_final, nmse, psi
+
+
+def camp_llr(op, B, K, l0, nl, probs_only=False):
+    """Soft output of the last camp_decode_batch of B codewords at PSK order K
+    through the complex operator `op`, decoded after op.soft_output(): for
+    sections [l0, l0 + nl) the bits of section_llr_psk -- log2 M location
+    bits, then log2 K symbol bits -- from each codeword's last effective
+    observation s and its tau (a codeword that stopped early: those of its
+    last iteration).  Returns float64 [B, nl * (log2 M + log2 K)]."""
+    if not op.csparc:
+        raise ValueError("camp_llr needs a ComplexDesignOperator (real designs: amp_llr)")
+    _check_psk(K)
+    out = np.empty((int(B), int(nl) * _section_bit_count(op.M, K)))
+    c = _interleaved(psk_constel(K)) if K != 1 else None
+    _native.check(_native.lib().sg_camp_llr(op.plan(), int(B), int(K), _native.ptr(c), int(l0), int(nl),
+                                            int(bool(probs_only)), _native.ptr(out)))
+    return out
 
 
 def _sparc_amp_complex(y, op, W, L, M, K, decode_params, awgn_var, beta0):
