@@ -16,10 +16,7 @@ template <typename R>
 static int upload_cx_as(sg_amp_plan *p, void **dst, const std::vector<cd> &src) {
     std::vector<R> v(2 * src.size());
     for (size_t i = 0; i < src.size(); ++i) { v[2 * i] = (R)src[i].real(); v[2 * i + 1] = (R)src[i].imag(); }
-    R *d = nullptr;
-    SG_TRY(upload(p, &d, v));
-    *dst = d;
-    return SG_OK;
+    return p->tables.upload((R **)dst, v);
 }
 
 int upload_cx(sg_amp_plan *p, void **dst, const std::vector<cd> &src) {
@@ -104,48 +101,30 @@ int diag_skip() {
 #endif
 }
 
-// ---- workspace: a buffer is allocated into its slot of the plan and the slot recorded, so freeing walks the record
-static int ws_alloc(std::vector<void **> &slots, void **slot, size_t bytes) {
-    SG_HIP(hipMalloc(slot, bytes));
-    slots.push_back(slot);
-    return SG_OK;
-}
-
-static void ws_free(std::vector<void **> &slots) {
-    for (void **x : slots) {
-        hipFree(*x);
-        *x = nullptr;
-    }
-    slots.clear();
-}
-
+// ---- workspace: every buffer is a slot of one of the plan's pools (device_mem.hpp), released together
 int integ_ensure_ws(sg_amp_plan *p, int B, int nbits) {
     if (B <= p->cap_Bi) return SG_OK;
-    ws_free(p->wi_slots);
+    p->wi.release();
     p->cap_Bi = 0;
     const size_t rs = p->precision == SG_F64 ? 8 : 4, Bz = (size_t)B;
-#define SG_ALLOC(ptr, bytes) SG_TRY(ws_alloc(p->wi_slots, (void **)&(ptr), (bytes)))
-    SG_ALLOC(p->wi_alpha, Bz * p->LM * rs);
-    SG_ALLOC(p->wi_gamma, Bz * p->LM * rs);
-    SG_ALLOC(p->wi_x, Bz * p->n * rs);
-    SG_ALLOC(p->wi_vk0, Bz * nbits * rs);
-    SG_ALLOC(p->wi_vk, Bz * nbits * rs);
-    SG_ALLOC(p->wi_llr, Bz * nbits * rs);
-    SG_ALLOC(p->wi_app, Bz * nbits * rs);
-    SG_ALLOC(p->wi_it, Bz * nbits * sizeof(int32_t));
-    SG_ALLOC(p->wi_part, Bz * p->L * sizeof(double));
-    SG_ALLOC(p->wi_ons, Bz * sizeof(double));
-#undef SG_ALLOC
+    SG_TRY(p->wi.alloc(&p->wi_alpha, Bz * p->LM * rs));
+    SG_TRY(p->wi.alloc(&p->wi_gamma, Bz * p->LM * rs));
+    SG_TRY(p->wi.alloc(&p->wi_x, Bz * p->n * rs));
+    SG_TRY(p->wi.alloc(&p->wi_vk0, Bz * nbits * rs));
+    SG_TRY(p->wi.alloc(&p->wi_vk, Bz * nbits * rs));
+    SG_TRY(p->wi.alloc(&p->wi_llr, Bz * nbits * rs));
+    SG_TRY(p->wi.alloc(&p->wi_app, Bz * nbits * rs));
+    SG_TRY(p->wi.alloc(&p->wi_it, Bz * nbits * sizeof(int32_t)));
+    SG_TRY(p->wi.alloc(&p->wi_part, Bz * p->L * sizeof(double)));
+    SG_TRY(p->wi.alloc(&p->wi_ons, Bz * sizeof(double)));
     p->cap_Bi = B;
     return SG_OK;
 }
 
 static void plan_free_ws(sg_amp_plan *p) {
-    ws_free(p->ws_slots);
-    if (p->ws_io) hipFree(p->ws_io);  // (its own grow rule, ensure_io; freed with the workspace)
-    p->ws_io = nullptr;
+    p->ws.release();
+    p->io.reset();  // (its own grow rule, ensure_io; freed with the workspace)
     p->cap_B = p->cap_tmax = 0;
-    p->ws_io_bytes = 0;
 }
 
 int ensure_ws(sg_amp_plan *p, int B, int t_max) {
@@ -153,71 +132,62 @@ int ensure_ws(sg_amp_plan *p, int B, int t_max) {
     plan_free_ws(p);
     const size_t rs = p->precision == SG_F64 ? 8 : 4;
     const size_t Bz = (size_t)B;
-#define SG_ALLOC(ptr, bytes) SG_TRY(ws_alloc(p->ws_slots, (void **)&(ptr), std::max<size_t>(16, (bytes))))
-    SG_ALLOC(p->ws_y, Bz * p->n * rs);
-    SG_ALLOC(p->ws_z, Bz * p->n * rs);
+    auto take = [&](auto *slot, size_t bytes) { return p->ws.alloc(slot, std::max<size_t>(16, bytes)); };
+    SG_TRY(take(&p->ws_y, Bz * p->n * rs));
+    SG_TRY(take(&p->ws_z, Bz * p->n * rs));
     if (p->regular) {
-        SG_ALLOC(p->ws_s, Bz * p->LM * rs);
-        SG_ALLOC(p->ws_tu, Bz * p->nT * p->rQ * p->nRmax * 2 * rs);
-        SG_ALLOC(p->ws_xn, Bz * p->nT * p->nKmax * 2 * rs);
-        SG_ALLOC(p->ws_part, Bz * p->nT * p->rQ * 3 * p->Lblk * rs);
+        SG_TRY(take(&p->ws_s, Bz * p->LM * rs));
+        SG_TRY(take(&p->ws_tu, Bz * p->nT * p->rQ * p->nRmax * 2 * rs));
+        SG_TRY(take(&p->ws_xn, Bz * p->nT * p->nKmax * 2 * rs));
+        SG_TRY(take(&p->ws_part, Bz * p->nT * p->rQ * 3 * p->Lblk * rs));
         if (std::getenv("SG_AMP_TPROF")) {  // diagnostics only (not a workspace slot: it lives until destroy)
-            if (p->tprof) hipFree(p->tprof);
+            p->tprof.reset();
             p->tprof_items = Bz * p->nT * p->rQ;
             // [2 kernels][items][8] shader-clock stamps, then [2 kernels][items][2] realtime start / end
-            SG_HIP(hipMalloc((void **)&p->tprof, std::max<size_t>(16, p->tprof_items * 20 * sizeof(uint64_t))));
-            SG_HIP(hipMemset(p->tprof, 0, p->tprof_items * 20 * sizeof(uint64_t)));
+            SG_TRY(p->tprof.ensure(std::max<size_t>(16, p->tprof_items * 20 * sizeof(uint64_t))));
+            SG_HIP(hipMemset(p->tprof.at(), 0, p->tprof_items * 20 * sizeof(uint64_t)));
         }
         if (p->cw2OT) {  // (reals of the plan's precision; partial statistics: four per section)
-            SG_ALLOC(p->ws_c2xp, Bz * std::max(CW2_NP, 2) * p->cw2OT * CW2_THREADS * rs);
-            SG_ALLOC(p->ws_c2vz, Bz * cw2_otp(p->cw2OT) * CW2_THREADS * 8);  // (f32: two reals per slot)
-            SG_ALLOC(p->ws_c2ys, Bz * p->cw2OT * CW2_THREADS * rs);
-            SG_ALLOC(p->ws_c2zs, Bz * p->cw2OT * CW2_THREADS * rs);
-            SG_ALLOC(p->ws_c2part, Bz * std::max(CW2_NP, 2) * p->Lblk * 4 * rs);
+            SG_TRY(take(&p->ws_c2xp, Bz * std::max(CW2_NP, 2) * p->cw2OT * CW2_THREADS * rs));
+            SG_TRY(take(&p->ws_c2vz, Bz * cw2_otp(p->cw2OT) * CW2_THREADS * 8));  // (f32: two reals per slot)
+            SG_TRY(take(&p->ws_c2ys, Bz * p->cw2OT * CW2_THREADS * rs));
+            SG_TRY(take(&p->ws_c2zs, Bz * p->cw2OT * CW2_THREADS * rs));
+            SG_TRY(take(&p->ws_c2part, Bz * std::max(CW2_NP, 2) * p->Lblk * 4 * rs));
             if (p->precision == SG_F64) {
-                SG_ALLOC(p->ws_c2beta, Bz * p->LM * rs);
-                SG_ALLOC(p->ws_c2sec, Bz * p->L * 2 * rs);
+                SG_TRY(take(&p->ws_c2beta, Bz * p->LM * rs));
+                SG_TRY(take(&p->ws_c2sec, Bz * p->L * 2 * rs));
             }
         }
-        SG_ALLOC(p->ws_stM, Bz * p->L * rs);
-        SG_ALLOC(p->ws_stI, Bz * p->L * rs);
-        SG_ALLOC(p->ws_tau_prev, Bz * p->Lc * 8);
+        SG_TRY(take(&p->ws_stM, Bz * p->L * rs));
+        SG_TRY(take(&p->ws_stI, Bz * p->L * rs));
+        SG_TRY(take(&p->ws_tau_prev, Bz * p->Lc * 8));
     } else {
-        SG_ALLOC(p->ws_beta, Bz * p->LM * rs);
-        SG_ALLOC(p->ws_rbuf, Bz * p->nT * p->Mr * rs);
-        SG_ALLOC(p->ws_buf0, Bz * p->nT * p->N2 * 2 * rs);
-        SG_ALLOC(p->ws_buf1, Bz * p->nT * p->N2 * 2 * rs);
-        SG_ALLOC(p->ws_sumsq, Bz * p->L * 8);
-        SG_ALLOC(p->ws_err, Bz * p->L * 8);
+        SG_TRY(take(&p->ws_beta, Bz * p->LM * rs));
+        SG_TRY(take(&p->ws_rbuf, Bz * p->nT * p->Mr * rs));
+        SG_TRY(take(&p->ws_buf0, Bz * p->nT * p->N2 * 2 * rs));
+        SG_TRY(take(&p->ws_buf1, Bz * p->nT * p->N2 * 2 * rs));
+        SG_TRY(take(&p->ws_sumsq, Bz * p->L * 8));
+        SG_TRY(take(&p->ws_err, Bz * p->L * 8));
     }
-    if (p->block || p->block2) SG_ALLOC(p->ws_gbuf, Bz * (size_t)p->b_ngs * 8);
-    SG_ALLOC(p->ws_phi, Bz * p->Lr * 8);
-    SG_ALLOC(p->ws_tau, Bz * p->Lc * 8);
-    SG_ALLOC(p->ws_psi, Bz * p->Lc * 8);
-    SG_ALLOC(p->ws_psi_prev, Bz * p->Lc * 8);
-    SG_ALLOC(p->ws_phi_prev, Bz * p->Lr * 8);
-    SG_ALLOC(p->ws_gamma, Bz * p->Lr * 8);
-    SG_ALLOC(p->ws_bco, Bz * p->Lr * 8);
-    SG_ALLOC(p->ws_nmse, Bz * std::max(t_max, 2) * p->Lc * 8);
-    SG_ALLOC(p->ws_active, Bz * 4);
-    SG_ALLOC(p->ws_argmax, Bz * p->L * 4);
-    SG_ALLOC(p->ws_true, Bz * p->L * 4);
-    SG_ALLOC(p->ws_tfinal, Bz * 4);
-#undef SG_ALLOC
+    if (p->block || p->block2) SG_TRY(take(&p->ws_gbuf, Bz * (size_t)p->b_ngs * 8));
+    SG_TRY(take(&p->ws_phi, Bz * p->Lr * 8));
+    SG_TRY(take(&p->ws_tau, Bz * p->Lc * 8));
+    SG_TRY(take(&p->ws_psi, Bz * p->Lc * 8));
+    SG_TRY(take(&p->ws_psi_prev, Bz * p->Lc * 8));
+    SG_TRY(take(&p->ws_phi_prev, Bz * p->Lr * 8));
+    SG_TRY(take(&p->ws_gamma, Bz * p->Lr * 8));
+    SG_TRY(take(&p->ws_bco, Bz * p->Lr * 8));
+    SG_TRY(take(&p->ws_nmse, Bz * std::max(t_max, 2) * p->Lc * 8));
+    SG_TRY(take(&p->ws_active, Bz * 4));
+    SG_TRY(take(&p->ws_argmax, Bz * p->L * 4));
+    SG_TRY(take(&p->ws_true, Bz * p->L * 4));
+    SG_TRY(take(&p->ws_tfinal, Bz * 4));
     p->cap_B = B;
     p->cap_tmax = std::max(t_max, 2);
     return SG_OK;
 }
 
-int ensure_io(sg_amp_plan *p, size_t bytes) {
-    if (bytes <= p->ws_io_bytes) return SG_OK;
-    if (p->ws_io) hipFree(p->ws_io);
-    p->ws_io = nullptr;
-    p->ws_io_bytes = 0;
-    SG_HIP(hipMalloc(&p->ws_io, bytes));
-    p->ws_io_bytes = bytes;
-    return SG_OK;
-}
+int ensure_io(sg_amp_plan *p, size_t bytes) { return p->io.ensure(bytes); }
 
 template <typename T>
 AmpTables<T> tables(const sg_amp_plan *p) {
@@ -398,27 +368,27 @@ static int build_plan(int ndim, const double *W, int Lr_in, int Lc_in, int L, in
     std::vector<double> Wd = p->W;
     sg_amp_plan *pp = p.release();
     int rc = [&]() -> int {
-    SG_TRY(upload(pp, &pp->t_row, t_row));
-    SG_TRY(upload(pp, &pp->t_col, t_col));
-    SG_TRY(upload(pp, &pp->col_ptr, col_ptr));
-    SG_TRY(upload(pp, &pp->col_t, col_t));
-    SG_TRY(upload(pp, &pp->row_ptr, row_ptr));
-    SG_TRY(upload(pp, &pp->row_t, row_t));
-    SG_TRY(upload(pp, &pp->inmap, inmap));
-    SG_TRY(upload(pp, &pp->outslot, outslot));
-    SG_TRY(upload(pp, &pp->rp_ptr, rp_ptr));
-    SG_TRY(upload(pp, &pp->rp_i, rp_i));
-    SG_TRY(upload(pp, &pp->rp_ab, rp_ab));
+    SG_TRY(pp->tables.upload(&pp->t_row, t_row));
+    SG_TRY(pp->tables.upload(&pp->t_col, t_col));
+    SG_TRY(pp->tables.upload(&pp->col_ptr, col_ptr));
+    SG_TRY(pp->tables.upload(&pp->col_t, col_t));
+    SG_TRY(pp->tables.upload(&pp->row_ptr, row_ptr));
+    SG_TRY(pp->tables.upload(&pp->row_t, row_t));
+    SG_TRY(pp->tables.upload(&pp->inmap, inmap));
+    SG_TRY(pp->tables.upload(&pp->outslot, outslot));
+    SG_TRY(pp->tables.upload(&pp->rp_ptr, rp_ptr));
+    SG_TRY(pp->tables.upload(&pp->rp_i, rp_i));
+    SG_TRY(pp->tables.upload(&pp->rp_ab, rp_ab));
     SG_TRY(upload_cx(pp, &pp->rp_c, rp_c));
-    SG_TRY(upload(pp, &pp->gs_ptr, gs_ptr));
-    SG_TRY(upload(pp, &pp->gs_loc, gs_loc));
-    SG_TRY(upload(pp, &pp->gs_i, gs_i));
+    SG_TRY(pp->tables.upload(&pp->gs_ptr, gs_ptr));
+    SG_TRY(pp->tables.upload(&pp->gs_loc, gs_loc));
+    SG_TRY(pp->tables.upload(&pp->gs_i, gs_i));
     SG_TRY(upload_cx(pp, &pp->gs_c, gs_c));
     SG_TRY(upload_cx(pp, &pp->twP, twP));
     SG_TRY(upload_cx(pp, &pp->twQ, twQ));
     SG_TRY(upload_cx(pp, &pp->twHi, twHi));
     SG_TRY(upload_cx(pp, &pp->twLo, twLo));
-    SG_TRY(upload(pp, &pp->dW, Wd));
+    SG_TRY(pp->tables.upload(&pp->dW, Wd));
     if (pp->regular) SG_TRY(build_regular(pp, order0, order1, t_scale));
     if (pp->block) SG_TRY(build_block(pp, order0, order1, t_scale, t_row));
     if (pp->block2) SG_TRY(build_block2(pp, order0, order1, t_scale, t_row));
@@ -456,10 +426,6 @@ int sg_amp_plan_create(int ndim, const double *W, int Lr, int Lc, int L, int M, 
 int sg_amp_plan_destroy(sg_amp_plan *p) {
     if (!p) return SG_OK;
     sg_amp_plan_destroy(p->alt);
-    plan_free_ws(p);
-    ws_free(p->wi_slots);
-    for (void *a : p->allocs) hipFree(a);
-    if (p->tprof) hipFree(p->tprof);
     if (p->poll_ev) {
         hipEventSynchronize(p->poll_ev);  // (a copy into h_active may still be in flight)
         hipEventDestroy(p->poll_ev);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "amp.hpp"
+#include "device_mem.hpp"
 
 using cd = std::complex<double>;
 
@@ -27,7 +28,7 @@ struct sg_amp_plan {
     int ndim = 0, L = 0, M = 0, LM = 0, n = 0, Lr = 1, Lc = 1, Mr = 0, Mc = 0, nT = 0;
     int w = 0, N2 = 0, P = 0, Q = 0, log2P = 0, log2Q = 0, npairs = 0;
     std::vector<double> W;
-    std::vector<void *> allocs;  // every device table owned by the plan (upload)
+    sg::DevPool tables;  // every device table of the plan (tables.upload into the members below)
     // general engine (four-step transform per nonzero block of W, amp_dct.hip) and the tables every engine reads
     int32_t *t_row = nullptr, *t_col = nullptr, *col_ptr = nullptr, *col_t = nullptr, *row_ptr = nullptr,
             *row_t = nullptr;
@@ -36,13 +37,12 @@ struct sg_amp_plan {
     int32_t *gs_ptr = nullptr, *gs_loc = nullptr, *gs_i = nullptr;
     void *rp_c = nullptr, *gs_c = nullptr, *twP = nullptr, *twQ = nullptr, *twHi = nullptr, *twLo = nullptr;
     double *dW = nullptr;
-    // batch workspace (grow-only, ensure_ws): every buffer allocated through ws_alloc, which records its slot
-    // here; plan_free_ws frees what is recorded.  ws_io (staging of the host entry points) grows by its own
-    // rule (ensure_io) and is freed with the workspace.
-    std::vector<void **> ws_slots;
+    // batch workspace (grow-only, ensure_ws): every buffer below is a slot of ws, which plan_free_ws releases.
+    // io (staging of the host entry points) grows by its own rule (ensure_io) and is freed with the workspace.
+    sg::DevPool ws;
     int cap_B = 0, cap_tmax = 0;
     void *ws_beta = nullptr, *ws_y = nullptr, *ws_z = nullptr, *ws_rbuf = nullptr, *ws_buf0 = nullptr, *ws_buf1 = nullptr;
-    void *ws_io = nullptr; size_t ws_io_bytes = 0;
+    sg::DevMem io;
     double *ws_phi = nullptr, *ws_tau = nullptr, *ws_sumsq = nullptr, *ws_err = nullptr;
     double *ws_psi = nullptr, *ws_psi_prev = nullptr, *ws_phi_prev = nullptr, *ws_gamma = nullptr, *ws_bco = nullptr;
     double *ws_nmse = nullptr;
@@ -59,7 +59,7 @@ struct sg_amp_plan {
     void *r_oc = nullptr, *r_gc = nullptr, *r_twP = nullptr, *r_twQ = nullptr, *r_stw = nullptr, *r_twa = nullptr,
          *r_twb = nullptr;
     // diagnostics: stage-1 phase timestamps; reallocated by ensure_ws while SG_AMP_TPROF is set, freed at destroy
-    uint64_t *tprof = nullptr; size_t tprof_items = 0;
+    sg::DevMem tprof; size_t tprof_items = 0;
     // active-flag poll (ActivePoll): pinned host copy and its completion event
     int32_t *h_active = nullptr; int h_active_cap = 0;
     hipEvent_t poll_ev = nullptr;
@@ -106,7 +106,7 @@ struct sg_amp_plan {
     // batch workspace's (integ_ensure_ws): u = Az(z) / weighted alpha and gamma [B][LM]; xhat = Ab(beta) [B][n];
     // vk0, vk, LLRs, app [B][L log M]; BP iteration counts; per-section sums (differentiated eta, or beta^2 of
     // the naive decoders) and their per-codeword sum
-    std::vector<void **> wi_slots;
+    sg::DevPool wi;
     int cap_Bi = 0;
     void *wi_alpha = nullptr, *wi_gamma = nullptr, *wi_x = nullptr, *wi_vk0 = nullptr, *wi_vk = nullptr,
          *wi_llr = nullptr, *wi_app = nullptr;
@@ -145,15 +145,6 @@ void inv_contrib(long long q, long long N, long long N2, double sc, F &&add) {
     }
 }
 
-template <typename X>
-int upload(sg_amp_plan *p, X **dst, const std::vector<X> &src) {
-    void *d = nullptr;
-    SG_HIP(hipMalloc(&d, std::max<size_t>(1, src.size() * sizeof(X))));
-    p->allocs.push_back(d);
-    if (!src.empty()) SG_HIP(hipMemcpy(d, src.data(), src.size() * sizeof(X), hipMemcpyHostToDevice));
-    *dst = (X *)d;
-    return SG_OK;
-}
 int upload_cx(sg_amp_plan *p, void **dst, const std::vector<cd> &src);  // as cx<T> of the plan's precision
 
 // Per-stage twiddles of the 2^log2n-point FFT at ept elements per thread, in thread order (fft.hpp fft1_plan,

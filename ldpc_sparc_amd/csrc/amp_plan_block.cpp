@@ -50,14 +50,14 @@ int build_block(sg_amp_plan *p, const uint32_t *order0, const uint32_t *order1, 
     }
     // per-stage twiddles of the N2-point FFT (fft.hpp lds_fft1_ct, EPT 16)
     const std::vector<cd> stw = stage_twiddles(ilog2((int)N2), 16);
-    SG_TRY(upload(p, &p->b_pos2, pos2));
-    SG_TRY(upload(p, &p->b_oab, oab));
+    SG_TRY(p->tables.upload(&p->b_pos2, pos2));
+    SG_TRY(p->tables.upload(&p->b_oab, oab));
     SG_TRY(upload_cx(p, &p->b_oc, oc));
-    SG_TRY(upload(p, &p->b_gptr, gptr));
-    SG_TRY(upload(p, &p->b_grow, grow));
+    SG_TRY(p->tables.upload(&p->b_gptr, gptr));
+    SG_TRY(p->tables.upload(&p->b_grow, grow));
     p->b_ngs = gptr[nT];
-    SG_TRY(upload(p, &p->b_gloc, gloc));
-    SG_TRY(upload(p, &p->b_gi, gi));
+    SG_TRY(p->tables.upload(&p->b_gloc, gloc));
+    SG_TRY(p->tables.upload(&p->b_gi, gi));
     SG_TRY(upload_cx(p, &p->b_gc, gc));
     SG_TRY(upload_cx(p, &p->b_stw, stw));
     SG_CHECK_ARG(blk_lds_bytes(Mc) <= 160 * 1024, "block engine LDS budget");
@@ -124,15 +124,15 @@ int build_block2(sg_amp_plan *p, const uint32_t *order0, const uint32_t *order1,
     // stage twiddles of the P-point FFT (fft.hpp lds_fft1_ct, EPT 16; unused by the sine / cosine stages of
     // amp_block2.hip)
     const std::vector<cd> stw = stage_twiddles(LP, 16);
-    SG_TRY(upload(p, &p->b_pos2, pos2));
-    SG_TRY(upload(p, &p->b_oab, oab));
+    SG_TRY(p->tables.upload(&p->b_pos2, pos2));
+    SG_TRY(p->tables.upload(&p->b_oab, oab));
     SG_TRY(upload_cx(p, &p->b_oc, oc));
-    SG_TRY(upload(p, &p->b_gptr, gptr));
-    SG_TRY(upload(p, &p->b_grow, grow));
+    SG_TRY(p->tables.upload(&p->b_gptr, gptr));
+    SG_TRY(p->tables.upload(&p->b_grow, grow));
     p->b_ngs = gptr[nT];
-    SG_TRY(upload(p, &p->b_gloc, gloc));
-    SG_TRY(upload(p, &p->b_gk, gk));
-    SG_TRY(upload(p, &p->b_gi, gi));
+    SG_TRY(p->tables.upload(&p->b_gloc, gloc));
+    SG_TRY(p->tables.upload(&p->b_gk, gk));
+    SG_TRY(p->tables.upload(&p->b_gi, gi));
     SG_TRY(upload_cx(p, &p->b_gc, gc));
     SG_TRY(upload_cx(p, &p->b_stw, stw));
     SG_CHECK_ARG(blk2_lds_bytes(LP) <= 160 * 1024, "block engine LDS budget");

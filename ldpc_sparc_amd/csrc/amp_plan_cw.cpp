@@ -155,11 +155,11 @@ int build_cw(sg_amp_plan *p, const std::vector<int32_t> &row_k1, const std::vect
         mbit(Q, row_k1[r], 0);
         mbit(Q, row_k1[r], 1);
     }
-    SG_TRY(upload(p, &p->c_cmask, cmask));
-    SG_TRY(upload(p, &p->c_kt, kt));
-    SG_TRY(upload(p, &p->c_oa, c_oa));
-    SG_TRY(upload(p, &p->c_ob, c_ob));
-    SG_TRY(upload(p, &p->c_gi, c_gi));
+    SG_TRY(p->tables.upload(&p->c_cmask, cmask));
+    SG_TRY(p->tables.upload(&p->c_kt, kt));
+    SG_TRY(p->tables.upload(&p->c_oa, c_oa));
+    SG_TRY(p->tables.upload(&p->c_ob, c_ob));
+    SG_TRY(p->tables.upload(&p->c_gi, c_gi));
     SG_TRY(upload_cx(p, &p->c_gc, c_gc));
     SG_TRY(upload_cx(p, &p->c_stw, stw));
     p->cwKT = KT;
@@ -375,7 +375,7 @@ int build_cw2(sg_amp_plan *p, const uint32_t *o0, double sc, const std::vector<i
             const uint32_t pl = 2u * (uint32_t)c2pos(fsw((int)(loc >> 1))) + (loc & 1u);
             cls2[(size_t)m2 * CW2_SLICE + (q - cls_ptr[m2])] = (cls_ls[q] & ~0xffffu) | pl;
         }
-    SG_TRY(upload(p, &p->c2_cls, cls2));
+    SG_TRY(p->tables.upload(&p->c2_cls, cls2));
     {  // image positions alone, two per word (cw2_az's gathers: entries tl + 512 i and tl + 512 (i + 9))
         constexpr int H = CW2_SLICE / 2;
         std::vector<uint32_t> clsp((size_t)Q * H);
@@ -384,29 +384,27 @@ int build_cw2(sg_amp_plan *p, const uint32_t *o0, double sc, const std::vector<i
                 const uint32_t *c = &cls2[(size_t)m2 * CW2_SLICE];
                 clsp[(size_t)m2 * H + q] = (c[q] & 0xffffu) | (c[q + H] << 16);
             }
-        SG_TRY(upload(p, &p->c2_clsp, clsp));
+        SG_TRY(p->tables.upload(&p->c2_clsp, clsp));
     }
-    SG_TRY(upload(p, &p->c2_cmask, cmask));
-    SG_TRY(upload(p, &p->c2_ka, ka));
+    SG_TRY(p->tables.upload(&p->c2_cmask, cmask));
+    SG_TRY(p->tables.upload(&p->c2_ka, ka));
     {  // thread-major copy: thread tid's slots at [tid][OTP] (amp_cw2.hip loads them 16 bytes at a time)
         const int OTP = cw2_otp(OT);
         std::vector<uint32_t> kat((size_t)OTP * T, 0u);
         for (int tid = 0; tid < T; ++tid)
             for (int j = 0; j < OT; ++j) kat[(size_t)tid * OTP + j] = ka[(size_t)j * T + tid];
-        SG_TRY(upload(p, &p->c2_kat, kat));
+        SG_TRY(p->tables.upload(&p->c2_kat, kat));
     }
-    SG_TRY(upload(p, &p->c2_oi, oi));
-    float *dcf = nullptr;
-    SG_TRY(upload(p, &dcf, cf));
-    p->c2_cf = dcf;
-    SG_TRY(upload(p, &p->c2_gm, gm));
+    SG_TRY(p->tables.upload(&p->c2_oi, oi));
+    SG_TRY(p->tables.upload((float **)&p->c2_cf, cf));
+    SG_TRY(p->tables.upload(&p->c2_gm, gm));
     {  // thread-major copy of (|al|, |be|): thread tid's slots at [tid][OTP][2] (16-byte loads of two slots)
         const int OTP = cw2_otp(OT);
         std::vector<float> gmt((size_t)OTP * T * 2, 0.f);
         for (int tid = 0; tid < T; ++tid)
             for (int j = 0; j < OT; ++j)
                 for (int c = 0; c < 2; ++c) gmt[((size_t)tid * OTP + j) * 2 + c] = gm[((size_t)j * T + tid) * 2 + c];
-        SG_TRY(upload(p, &p->c2_gmt, gmt));
+        SG_TRY(p->tables.upload(&p->c2_gmt, gmt));
     }
     p->c2_shoff = pow2 ? ilog2((int)(N / 2)) : 0;
     if (f64) {
@@ -416,10 +414,10 @@ int build_cw2(sg_amp_plan *p, const uint32_t *o0, double sc, const std::vector<i
             twp[2 * k] = w.real();
             twp[2 * k + 1] = w.imag();
         }
-        SG_TRY(upload(p, &p->c2d_cf, cfd));
-        SG_TRY(upload(p, &p->c2d_gf, gfd));
-        SG_TRY(upload(p, &p->c2d_sa, sad));
-        SG_TRY(upload(p, &p->c2d_twp, twp));
+        SG_TRY(p->tables.upload(&p->c2d_cf, cfd));
+        SG_TRY(p->tables.upload(&p->c2d_gf, gfd));
+        SG_TRY(p->tables.upload(&p->c2d_sa, sad));
+        SG_TRY(p->tables.upload(&p->c2d_twp, twp));
     }
     p->cw2OT = OT;
     return SG_OK;
@@ -437,7 +435,7 @@ CwTables ctables(const sg_amp_plan *p, int B) {
     tb.stw = (const cx<float> *)p->c_stw;
     tb.inv_n2 = 1.0f / (float)p->N2;
     // [B][32] stamps (one workgroup per codeword), only when the diagnostics buffer holds them
-    tb.tprof = (p->tprof && p->tprof_items * 20 >= (size_t)32 * B) ? p->tprof : nullptr;
+    tb.tprof = p->tprof_items * 20 >= (size_t)32 * B ? p->tprof.at<uint64_t>() : nullptr;  // (null when empty)
     return tb;
 }
 
@@ -456,7 +454,7 @@ Cw2Tables c2tables(const sg_amp_plan *p, int B) {
     tb.xr = (float *)p->ws_c2xp; tb.vz = (float *)p->ws_c2vz; tb.ys = (float *)p->ws_c2ys; tb.zs = (float *)p->ws_c2zs; tb.part = (float4 *)p->ws_c2part;
     // [np B][64] stamps (workgroup blockIdx.x < np B writes 64 blockIdx.x + k), only when the diagnostics
     // buffer holds them (build_cw2 accepts any even Q, and its B * Q * 20 entries are fewer for small Q)
-    tb.tprof = (p->tprof && p->tprof_items * 20 >= (size_t)64 * tb.np * B) ? p->tprof : nullptr;
+    tb.tprof = p->tprof_items * 20 >= (size_t)64 * tb.np * B ? p->tprof.at<uint64_t>() : nullptr;
     return tb;
 }
 

@@ -171,8 +171,8 @@ int build_regular(sg_amp_plan *p, const uint32_t *order0, const uint32_t *order1
         for (int a = 0; a < 64; ++a) twa[(size_t)m2 * 64 + a] = tw((long long)m2 * a, N2);
         for (int b = 0; b < nB; ++b) twb[(size_t)m2 * nB + b] = tw((long long)m2 * 64 * b, N2);
     }
-    SG_TRY(upload(p, &p->r_nR, nR));
-    SG_TRY(upload(p, &p->r_row_k1, f_rk));
+    SG_TRY(p->tables.upload(&p->r_nR, nR));
+    SG_TRY(p->tables.upload(&p->r_row_k1, f_rk));
     {  // stage-1 order: thread tid holds rows tid + i nthr, i < ept, packed in pairs
         const int ept = p->rept, nthr = P / ept;
         SG_CHECK_ARG(P <= 65536 && ept % 2 == 0, "stage-1 FFT length %d exceeds the 16-bit row index", P);
@@ -186,26 +186,26 @@ int build_regular(sg_amp_plan *p, const uint32_t *order0, const uint32_t *order1
                     pk[(size_t)t * (P / 2) + (size_t)j * nthr + tid] = a | (b << 16);
                 }
         }
-        SG_TRY(upload(p, &p->r_row_k1p, pk));
+        SG_TRY(p->tables.upload(&p->r_row_k1p, pk));
     }
-    SG_TRY(upload(p, &p->r_kptr, f_kp));
-    SG_TRY(upload(p, &p->r_kk2, f_k2));
-    SG_TRY(upload(p, &p->r_krho, f_kr));
-    SG_TRY(upload(p, &p->r_oa, f_oa));
-    SG_TRY(upload(p, &p->r_ob, f_ob));
+    SG_TRY(p->tables.upload(&p->r_kptr, f_kp));
+    SG_TRY(p->tables.upload(&p->r_kk2, f_k2));
+    SG_TRY(p->tables.upload(&p->r_krho, f_kr));
+    SG_TRY(p->tables.upload(&p->r_oa, f_oa));
+    SG_TRY(p->tables.upload(&p->r_ob, f_ob));
     SG_TRY(upload_cx(p, &p->r_oc, f_oc));
-    SG_TRY(upload(p, &p->r_gi, f_gi));
+    SG_TRY(p->tables.upload(&p->r_gi, f_gi));
     SG_TRY(upload_cx(p, &p->r_gc, f_gc));
     for (int t = 0; t < nT; ++t)
         for (int m2 = 0; m2 < Q; ++m2)
             p->rmaxcls = std::max(p->rmaxcls, cls_ptr[(size_t)t * (Q + 1) + m2 + 1] - cls_ptr[(size_t)t * (Q + 1) + m2]);
     p->rimg = (std::max(2 * P, fpad(p->rmaxcls + 16) + 1) + 3) / 4 * 4;
     SG_CHECK_ARG(reg_stage1_lds(p->rimg, P, Lblk, rb) <= 160 * 1024, "a class exceeds the LDS budget");
-    SG_TRY(upload(p, &p->r_cls_ptr, cls_ptr));
-    SG_TRY(upload(p, &p->r_cls_ls, cls_ls));
-    SG_TRY(upload(p, &p->r_cls_j, cls_j));
-    SG_TRY(upload(p, &p->r_qpos, qpos));
-    SG_TRY(upload(p, &p->r_seg, seg));
+    SG_TRY(p->tables.upload(&p->r_cls_ptr, cls_ptr));
+    SG_TRY(p->tables.upload(&p->r_cls_ls, cls_ls));
+    SG_TRY(p->tables.upload(&p->r_cls_j, cls_j));
+    SG_TRY(p->tables.upload(&p->r_qpos, qpos));
+    SG_TRY(p->tables.upload(&p->r_seg, seg));
     SG_TRY(upload_cx(p, &p->r_twP, twP));
     SG_TRY(upload_cx(p, &p->r_twQ, twQ));
     SG_TRY(upload_cx(p, &p->r_stw, stw));
@@ -264,11 +264,11 @@ RegBufs<T> rbufs(const sg_amp_plan *p, int B, const void *y) {
     bf.phi = p->ws_phi; bf.tau = p->ws_tau; bf.tau_prev = p->ws_tau_prev; bf.active = p->ws_active;
     bf.true_idx = nullptr; bf.map = p->ws_argmax; bf.ext_in = nullptr; bf.ext_out = nullptr;
     bf.tprof_ab = bf.tprof_az = bf.trt_ab = bf.trt_az = nullptr;
-    if (p->tprof && (size_t)B * p->nT * p->rQ <= p->tprof_items) {
-        bf.tprof_ab = p->tprof;
-        bf.tprof_az = p->tprof + p->tprof_items * 8;
-        bf.trt_ab = p->tprof + p->tprof_items * 16;
-        bf.trt_az = p->tprof + p->tprof_items * 18;
+    if (uint64_t *tp = p->tprof.at<uint64_t>(); tp && (size_t)B * p->nT * p->rQ <= p->tprof_items) {
+        bf.tprof_ab = tp;
+        bf.tprof_az = tp + p->tprof_items * 8;
+        bf.trt_ab = tp + p->tprof_items * 16;
+        bf.trt_az = tp + p->tprof_items * 18;
     }
     return bf;
 }

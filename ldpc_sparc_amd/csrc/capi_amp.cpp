@@ -451,10 +451,10 @@ int sg_amp_decode(sg_amp_plan *p, const double *y, int B, const int32_t *true_id
     SG_TRY(ensure_ws(p, B, t_max));
     const size_t ny = (size_t)B * p->n;
     SG_TRY(ensure_io(p, ny * sizeof(double)));
-    SG_HIP(hipMemcpyAsync(p->ws_io, y, ny * sizeof(double), hipMemcpyHostToDevice, s));
+    SG_HIP(hipMemcpyAsync(p->io.at(), y, ny * sizeof(double), hipMemcpyHostToDevice, s));
     SG_TRY(by_precision(p->precision, [&](auto t) {
         using T = decltype(t);
-        SG_TRY(amp_launch_cast<T>(p->ws_io, 1, (T *)p->ws_y, ny, s));
+        SG_TRY(amp_launch_cast<T>(p->io.at(), 1, (T *)p->ws_y, ny, s));
         if (true_idx)
             SG_HIP(hipMemcpyAsync(p->ws_true, true_idx, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
         const DecodeArgs a{p->ws_y, B, true_idx ? p->ws_true : nullptr, awgn_var, t_max, rtol, phi_method,
@@ -481,7 +481,7 @@ int sg_amp_apply(sg_amp_plan *p, int transpose, const double *in, int B, double 
     const size_t nin = (size_t)B * (transpose ? p->n : p->LM), nout = (size_t)B * (transpose ? p->LM : p->n);
     SG_TRY(ensure_ws(p, B, 2));
     SG_TRY(ensure_io(p, (nin + nout) * sizeof(double)));
-    double *din = (double *)p->ws_io, *dout = din + nin;
+    double *din = p->io.at<double>(), *dout = din + nin;
     SG_HIP(hipMemcpyAsync(din, in, nin * sizeof(double), hipMemcpyHostToDevice, s));
     SG_TRY(by_precision(p->precision,
                         [&](auto t) { return apply_impl<decltype(t)>(p, transpose, din, 1, B, dout, 1, s); }));
@@ -506,10 +506,11 @@ int sg_amp_stage_profile(sg_amp_plan *p, int kernel, double *mean_cycles, int *n
     SG_CHECK_ARG(p && mean_cycles && nphases && (kernel == 0 || kernel == 1), "bad argument");
     *nphases = 0;
     if (p->last_ran) p = p->last_ran;  // the sub-plan the last decode ran on (maybe the companion)
-    if (!p->tprof) return SG_OK;
+    const uint64_t *tp = p->tprof.at<uint64_t>();
+    if (!tp) return SG_OK;
     std::vector<uint64_t> h(p->tprof_items * 8);
     SG_HIP(hipDeviceSynchronize());
-    SG_HIP(hipMemcpy(h.data(), p->tprof + (size_t)kernel * p->tprof_items * 8, h.size() * 8, hipMemcpyDeviceToHost));
+    SG_HIP(hipMemcpy(h.data(), tp + (size_t)kernel * p->tprof_items * 8, h.size() * 8, hipMemcpyDeviceToHost));
     double sum[8] = {0};
     size_t n = 0;
     for (size_t i = 0; i < p->tprof_items; ++i) {
@@ -526,13 +527,14 @@ int sg_amp_stage_profile(sg_amp_plan *p, int kernel, double *mean_cycles, int *n
 int sg_amp_stage_raw(sg_amp_plan *p, int kernel, uint64_t *out, size_t *items) {
     SG_CHECK_ARG(p && items && (kernel == 0 || kernel == 1), "bad argument");
     if (p->last_ran) p = p->last_ran;
-    *items = p->tprof ? p->tprof_items : 0;
-    if (!p->tprof || !out) return SG_OK;
+    const uint64_t *tp = p->tprof.at<uint64_t>();
+    *items = tp ? p->tprof_items : 0;
+    if (!tp || !out) return SG_OK;
     const size_t ni = p->tprof_items;
     std::vector<uint64_t> cyc(ni * 8), rt(ni * 2);
     SG_HIP(hipDeviceSynchronize());
-    SG_HIP(hipMemcpy(cyc.data(), p->tprof + (size_t)kernel * ni * 8, ni * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    SG_HIP(hipMemcpy(rt.data(), p->tprof + ni * 16 + (size_t)kernel * ni * 2, ni * 2 * sizeof(uint64_t),
+    SG_HIP(hipMemcpy(cyc.data(), tp + (size_t)kernel * ni * 8, ni * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    SG_HIP(hipMemcpy(rt.data(), tp + ni * 16 + (size_t)kernel * ni * 2, ni * 2 * sizeof(uint64_t),
                      hipMemcpyDeviceToHost));
     for (size_t i = 0; i < ni; ++i) {
         std::copy(&cyc[i * 8], &cyc[i * 8] + 8, out + i * 10);
@@ -610,7 +612,7 @@ int sg_amp_llr(sg_amp_plan *p, int B, int l0, int nl, int probs_only, double *ou
     hipStream_t s = lib_stream();
     // staging in the handle's own I/O buffer (not part of the decode state): doubles, then the plan's reals
     SG_TRY(ensure_io(p, nv * 16));
-    double *dd = (double *)p->ws_io;
+    double *dd = p->io.at<double>();
     if (r->precision == SG_F64) {
         SG_TRY(llr_impl<double>(r, B, l0, nl, (int)ld, probs_only, dd, s));
     } else {
@@ -674,12 +676,12 @@ int sg_amp_integrated_decode(sg_amp_plan *p, sg_graph *g, int mode, int K, const
     hipStream_t s = lib_stream();
     const size_t rs = p->precision == SG_F64 ? 8 : 4, ny = (size_t)B * p->n, nt = (size_t)B * t_max;
     const size_t nbits = (size_t)B * (p->L * ilog2(p->M) / N) * K;
-    // The workspace before the staging buffer: growing the workspace frees ws_io too (plan_free_ws), so the
+    // The workspace before the staging buffer: growing the workspace frees io too (plan_free_ws), so the
     // device entry point's own ensure_ws(p, B, 2) below must find it grown and leave the staging alone
     SG_TRY(ensure_ws(p, B, 2));
     // staging: y as doubles, the tau^2 history, y in the plan precision, the bits
     SG_TRY(ensure_io(p, (ny + nt) * 8 + ny * rs + nbits));
-    double *dy = (double *)p->ws_io, *dtau = dy + ny;
+    double *dy = p->io.at<double>(), *dtau = dy + ny;
     void *dyt = dtau + nt;
     uint8_t *dbits = (uint8_t *)dyt + ny * rs;
     SG_HIP(hipMemcpyAsync(dy, y, ny * 8, hipMemcpyHostToDevice, s));

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "amp_cfft.hpp"
+#include "device_mem.hpp"
 
 using namespace sg;
 
@@ -14,13 +15,13 @@ struct sg_camp_plan {
     int device = 0;
     int ndim = 0, L = 0, M = 0, LM = 0, n = 0, Lr = 1, Lc = 1, Mr = 0, Mc = 0, nT = 0;
     int w = 0, P = 0, Q = 0, log2P = 0, log2Q = 0, CT = 0, RT = 0;
-    std::vector<void *> allocs;  // design tables
+    DevPool tables;  // design tables
     int32_t *t_row = nullptr, *t_col = nullptr, *col_ptr = nullptr, *col_t = nullptr, *row_ptr = nullptr,
             *row_t = nullptr, *in0 = nullptr, *in1 = nullptr, *pos0 = nullptr, *pos1 = nullptr;
     double *t_scale = nullptr, *dW = nullptr;
     cxd *twP = nullptr, *twQ = nullptr, *twW = nullptr, *constel = nullptr;
     // workspace of the largest (B, t_max) seen: one allocation carved below
-    void *ws = nullptr;
+    DevMem ws;
     int ws_B = 0, ws_tmax = 0;
     cxd *beta = nullptr, *y = nullptr, *z = nullptr, *buf0 = nullptr, *buf1 = nullptr, *io = nullptr;
     double *phi = nullptr, *tau = nullptr, *sec_sumsq = nullptr, *sec_err = nullptr, *psi = nullptr,
@@ -36,16 +37,6 @@ struct sg_camp_plan {
 };
 
 namespace {
-
-template <typename X>
-int upload(sg_camp_plan *p, X **dst, const std::vector<X> &src) {
-    void *d = nullptr;
-    SG_HIP(hipMalloc(&d, std::max<size_t>(src.size(), 1) * sizeof(X)));
-    p->allocs.push_back(d);
-    if (!src.empty()) SG_HIP(hipMemcpy(d, src.data(), src.size() * sizeof(X), hipMemcpyHostToDevice));
-    *dst = (X *)d;
-    return SG_OK;
-}
 
 std::vector<cxd> twiddles(int len) {  // exp(-2 pi i e / len)
     std::vector<cxd> t(len);
@@ -66,11 +57,10 @@ std::vector<cxd> twiddles(int len) {  // exp(-2 pi i e / len)
 }
 
 int ensure_ws(sg_camp_plan *p, int B, int t_max) {
-    if (p->ws && B <= p->ws_B && t_max <= p->ws_tmax && (!p->soft || p->s_keep)) return SG_OK;
+    if (p->ws.bytes() && B <= p->ws_B && t_max <= p->ws_tmax && (!p->soft || p->s_keep)) return SG_OK;
     B = std::max(B, p->ws_B);
     t_max = std::max(t_max, p->ws_tmax);
-    if (p->ws) hipFree(p->ws);
-    p->ws = nullptr;
+    p->ws.reset();
     p->s_keep = nullptr;
     p->ws_B = p->ws_tmax = 0;
     size_t off = 0;
@@ -90,8 +80,8 @@ int ensure_ws(sg_camp_plan *p, int B, int t_max) {
                  o_sy = take(sB * p->L * 4), o_ti = take(sB * p->L * 4), o_ts = take(sB * p->L * 4),
                  o_tf = take(sB * 4);
     const size_t o_keep = p->soft ? take(sB * p->LM * sizeof(cxd)) : 0;  // 16 LM bytes per codeword, only when on
-    SG_HIP(hipMalloc(&p->ws, off));
-    char *b = (char *)p->ws;
+    SG_TRY(p->ws.ensure(off));
+    char *b = p->ws.at<char>();
     p->beta = (cxd *)(b + o_beta); p->y = (cxd *)(b + o_y); p->z = (cxd *)(b + o_z);
     p->buf0 = (cxd *)(b + o_b0); p->buf1 = (cxd *)(b + o_b1); p->io = (cxd *)(b + o_io);
     p->phi = (double *)(b + o_phi); p->tau = (double *)(b + o_tau);
@@ -152,9 +142,6 @@ int set_constel(sg_camp_plan *p, int K, const double *constel, hipStream_t s) {
 extern "C" {
 
 int sg_camp_plan_destroy(sg_camp_plan *p) {
-    if (!p) return SG_OK;
-    if (p->ws) hipFree(p->ws);
-    for (void *a : p->allocs) hipFree(a);
     delete p;
     return SG_OK;
 }
@@ -235,15 +222,16 @@ int sg_camp_plan_create(int ndim, const double *W, int Lr_in, int Lc_in, int L, 
         }
     }
     sg_camp_plan *q = p.get();
-    SG_TRY(upload(q, &q->t_row, t_row)); SG_TRY(upload(q, &q->t_col, t_col)); SG_TRY(upload(q, &q->t_scale, t_scale));
-    SG_TRY(upload(q, &q->col_ptr, col_ptr)); SG_TRY(upload(q, &q->col_t, col_t));
-    SG_TRY(upload(q, &q->row_ptr, row_ptr)); SG_TRY(upload(q, &q->row_t, row_t));
-    SG_TRY(upload(q, &q->in0, in0)); SG_TRY(upload(q, &q->in1, in1));
-    SG_TRY(upload(q, &q->pos0, pos0)); SG_TRY(upload(q, &q->pos1, pos1));
-    SG_TRY(upload(q, &q->dW, Wv));
-    SG_TRY(upload(q, &q->twP, twiddles(P))); SG_TRY(upload(q, &q->twQ, twiddles(Q)));
-    SG_TRY(upload(q, &q->twW, twiddles(w)));
-    SG_TRY(upload(q, &q->constel, std::vector<cxd>(CAMP_MAX_K, cxd{1.0, 0.0})));
+    DevPool &tb = q->tables;
+    SG_TRY(tb.upload(&q->t_row, t_row)); SG_TRY(tb.upload(&q->t_col, t_col)); SG_TRY(tb.upload(&q->t_scale, t_scale));
+    SG_TRY(tb.upload(&q->col_ptr, col_ptr)); SG_TRY(tb.upload(&q->col_t, col_t));
+    SG_TRY(tb.upload(&q->row_ptr, row_ptr)); SG_TRY(tb.upload(&q->row_t, row_t));
+    SG_TRY(tb.upload(&q->in0, in0)); SG_TRY(tb.upload(&q->in1, in1));
+    SG_TRY(tb.upload(&q->pos0, pos0)); SG_TRY(tb.upload(&q->pos1, pos1));
+    SG_TRY(tb.upload(&q->dW, Wv));
+    SG_TRY(tb.upload(&q->twP, twiddles(P))); SG_TRY(tb.upload(&q->twQ, twiddles(Q)));
+    SG_TRY(tb.upload(&q->twW, twiddles(w)));
+    SG_TRY(tb.upload(&q->constel, std::vector<cxd>(CAMP_MAX_K, cxd{1.0, 0.0})));
     SG_TRY(camp_prepare_fft(tables(q)));
     *out = p.release();
     return SG_OK;
@@ -446,21 +434,15 @@ int sg_section_mmse_psk(const double *x, int L, int M, int K, const double *cons
     const size_t N = (size_t)L * M;
     std::vector<cxd> hx(N);
     for (size_t i = 0; i < N; ++i) hx[i] = x_is_complex ? cxd{x[2 * i], x[2 * i + 1]} : cxd{x[i], 0.0};
-    cxd *d = nullptr;
-    SG_HIP(hipMalloc((void **)&d, (2 * N + CAMP_MAX_K) * sizeof(cxd)));
-    cxd *dout = d + N, *dc = d + 2 * N;
-    int rc = SG_OK;
-    auto run = [&]() -> int {
-        SG_HIP(hipMemcpyAsync(d, hx.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
-        if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
-        SG_TRY(camp_launch_mmse(d, L, M, K, dc, dout, s));
-        SG_HIP(hipMemcpyAsync(out, dout, N * sizeof(cxd), hipMemcpyDeviceToHost, s));
-        SG_HIP(hipStreamSynchronize(s));
-        return SG_OK;
-    };
-    rc = run();
-    hipFree(d);
-    return rc;
+    DevMem mem;
+    SG_TRY(mem.ensure((2 * N + CAMP_MAX_K) * sizeof(cxd)));
+    cxd *d = mem.at<cxd>(), *dout = d + N, *dc = d + 2 * N;
+    SG_HIP(hipMemcpyAsync(d, hx.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
+    if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
+    SG_TRY(camp_launch_mmse(d, L, M, K, dc, dout, s));
+    SG_HIP(hipMemcpyAsync(out, dout, N * sizeof(cxd), hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    return SG_OK;
 }
 
 // s[L*M] as above; idx[L] the MAP location, sym[L] the constellation index
@@ -477,23 +459,18 @@ int sg_section_map_psk(const double *sv, int L, int M, int K, const double *cons
     std::vector<cxd> hs(N);
     for (size_t i = 0; i < N; ++i) hs[i] = s_is_complex ? cxd{sv[2 * i], sv[2 * i + 1]} : cxd{sv[i], 0.0};
     std::vector<int32_t> hsym(L);
-    cxd *d = nullptr;
-    SG_HIP(hipMalloc((void **)&d, (N + CAMP_MAX_K) * sizeof(cxd) + 2 * (size_t)L * sizeof(int32_t)));
-    cxd *dc = d + N;
+    DevMem mem;
+    SG_TRY(mem.ensure((N + CAMP_MAX_K) * sizeof(cxd) + 2 * (size_t)L * sizeof(int32_t)));
+    cxd *d = mem.at<cxd>(), *dc = d + N;
     int32_t *di = (int32_t *)(dc + CAMP_MAX_K), *dsym = di + L;
-    auto run = [&]() -> int {
-        SG_HIP(hipMemcpyAsync(d, hs.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
-        if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
-        SG_TRY(camp_launch_map(d, L, M, K, dc, di, dsym, s));
-        SG_HIP(hipMemcpyAsync(idx, di, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        SG_HIP(hipMemcpyAsync(hsym.data(), dsym, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        SG_HIP(hipStreamSynchronize(s));
-        return SG_OK;
-    };
-    const int rc = run();
-    hipFree(d);
-    if (rc == SG_OK && sym) std::memcpy(sym, hsym.data(), (size_t)L * sizeof(int32_t));
-    return rc;
+    SG_HIP(hipMemcpyAsync(d, hs.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
+    if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
+    SG_TRY(camp_launch_map(d, L, M, K, dc, di, dsym, s));
+    SG_HIP(hipMemcpyAsync(idx, di, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(hsym.data(), dsym, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    if (sym) std::memcpy(sym, hsym.data(), (size_t)L * sizeof(int32_t));
+    return SG_OK;
 }
 
 // ------------------------------------------------------------------ soft output
@@ -552,19 +529,14 @@ int sg_camp_llr(sg_camp_plan *p, int B, int K, const double *constel, int l0, in
     SG_CHECK_ARG(ld <= (size_t)INT32_MAX, "too many bits per codeword");
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = lib_stream();
-    double *d = nullptr;  // staging of its own: the plan's buffers hold the state being read
-    SG_HIP(hipMalloc((void **)&d, nv * sizeof(double)));
-    auto run = [&]() -> int {
-        SG_TRY(set_constel(p, K, constel, s));
-        SG_TRY(camp_launch_llr(p->s_keep, p->tau, B, p->L, p->Lc, p->M, K, p->constel, l0, nl, (int)ld, probs_only, d,
-                               s));
-        SG_HIP(hipMemcpyAsync(out, d, nv * sizeof(double), hipMemcpyDeviceToHost, s));
-        SG_HIP(hipStreamSynchronize(s));
-        return SG_OK;
-    };
-    const int rc = run();
-    hipFree(d);
-    return rc;
+    DevMem mem;  // staging of its own: the plan's buffers hold the state being read
+    SG_TRY(mem.ensure(nv * sizeof(double)));
+    double *d = mem.at<double>();
+    SG_TRY(set_constel(p, K, constel, s));
+    SG_TRY(camp_launch_llr(p->s_keep, p->tau, B, p->L, p->Lc, p->M, K, p->constel, l0, nl, (int)ld, probs_only, d, s));
+    SG_HIP(hipMemcpyAsync(out, d, nv * sizeof(double), hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    return SG_OK;
 }
 
 // x as sg_section_mmse_psk; out [L][log2 M + log2 K]: P(bit = 0) of the section bits, or their clipped LLRs
@@ -584,22 +556,17 @@ int sg_section_llr_psk(const double *x, int L, int M, int K, const double *const
     const size_t N = (size_t)L * M, nout = (size_t)L * per;
     std::vector<cxd> hx(N);
     for (size_t i = 0; i < N; ++i) hx[i] = x_is_complex ? cxd{x[2 * i], x[2 * i + 1]} : cxd{x[i], 0.0};
-    cxd *d = nullptr;
-    SG_HIP(hipMalloc((void **)&d, (N + CAMP_MAX_K) * sizeof(cxd) + nout * sizeof(double)));
-    cxd *dc = d + N;
+    DevMem mem;
+    SG_TRY(mem.ensure((N + CAMP_MAX_K) * sizeof(cxd) + nout * sizeof(double)));
+    cxd *d = mem.at<cxd>(), *dc = d + N;
     double *dout = (double *)(dc + CAMP_MAX_K);
-    auto run = [&]() -> int {
-        SG_HIP(hipMemcpyAsync(d, hx.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
-        if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
-        // one "codeword" of L sections, x given: no tau
-        SG_TRY(camp_launch_llr(d, nullptr, 1, L, 1, M, K, dc, 0, L, (int)nout, probs_only, dout, s));
-        SG_HIP(hipMemcpyAsync(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost, s));
-        SG_HIP(hipStreamSynchronize(s));
-        return SG_OK;
-    };
-    const int rc = run();
-    hipFree(d);
-    return rc;
+    SG_HIP(hipMemcpyAsync(d, hx.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
+    if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
+    // one "codeword" of L sections, x given: no tau
+    SG_TRY(camp_launch_llr(d, nullptr, 1, L, 1, M, K, dc, 0, L, (int)nout, probs_only, dout, s));
+    SG_HIP(hipMemcpyAsync(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    return SG_OK;
 }
 
 int sg_bits_to_psk_sections_strided_device(const uint8_t *d_bits, size_t bit_stride, int B, int L, int logM, int logK,

@@ -7,22 +7,26 @@
 #include <vector>
 
 #include "dense.hpp"
+#include "device_mem.hpp"
 
 struct sg_dense_plan {
     int precision = SG_F32;
     int device = 0;
     int n = 0, npad = 0, L = 0, M = 0, LM = 0, nsplit = 1;
     double P = 0;
-    void *A = nullptr;
+    sg::DevMem A;
+    // batch workspace (grow-only, dense_ensure_ws): the slots of ws; io, the staging of the host entry points,
+    // grows by its own rule and is freed with the workspace
+    sg::DevPool ws;
     int cap_B = 0;
     void *ws_y = nullptr, *ws_z = nullptr, *ws_beta = nullptr, *ws_s = nullptr, *ws_part = nullptr;
     double *ws_tau2 = nullptr, *ws_sec_bsq = nullptr;
     int32_t *ws_idx = nullptr;
-    void *ws_io = nullptr;
-    size_t ws_io_bytes = 0;
+    sg::DevMem io;
     // integrated decoders (integrated.hip): weighted alpha, gamma [B][LM];
     // bit probabilities vk0, vk, LLRs and app [B][L log M]; BP iteration counts;
     // per-section / per-codeword sums of the differentiated eta
+    sg::DevPool wi;
     int cap_Bi = 0;
     void *wi_alpha = nullptr, *wi_gamma = nullptr, *wi_vk0 = nullptr, *wi_vk = nullptr, *wi_llr = nullptr,
          *wi_app = nullptr;
@@ -35,14 +39,9 @@ namespace sg {
 static size_t rsize(const sg_dense_plan *p) { return p->precision == SG_F64 ? 8 : 4; }
 
 static void dense_free_ws(sg_dense_plan *p) {
-    void *bufs[] = {p->ws_y, p->ws_z, p->ws_beta, p->ws_s, p->ws_part, p->ws_tau2, p->ws_sec_bsq, p->ws_idx, p->ws_io};
-    for (void *b : bufs)
-        if (b) hipFree(b);
-    p->ws_y = p->ws_z = p->ws_beta = p->ws_s = p->ws_part = p->ws_io = nullptr;
-    p->ws_tau2 = p->ws_sec_bsq = nullptr;
-    p->ws_idx = nullptr;
+    p->ws.release();
+    p->io.reset();
     p->cap_B = 0;
-    p->ws_io_bytes = 0;
 }
 
 static int dense_ensure_ws(sg_dense_plan *p, int B) {
@@ -50,26 +49,20 @@ static int dense_ensure_ws(sg_dense_plan *p, int B) {
     dense_free_ws(p);
     const size_t rs = rsize(p), Bz = (size_t)B;
     const int nblk = (p->npad + 255) / 256;
-    SG_HIP(hipMalloc(&p->ws_y, Bz * p->n * rs));
-    SG_HIP(hipMalloc(&p->ws_z, Bz * p->npad * rs));
-    SG_HIP(hipMalloc(&p->ws_beta, Bz * p->LM * rs));
-    SG_HIP(hipMalloc(&p->ws_s, Bz * p->LM * rs));
-    SG_HIP(hipMalloc(&p->ws_part, (size_t)p->nsplit * Bz * p->n * rs));
-    SG_HIP(hipMalloc(&p->ws_tau2, Bz * (1 + nblk) * sizeof(double)));
-    SG_HIP(hipMalloc(&p->ws_sec_bsq, Bz * p->L * sizeof(double)));
-    SG_HIP(hipMalloc(&p->ws_idx, Bz * p->L * sizeof(int32_t)));
+    SG_TRY(p->ws.alloc(&p->ws_y, Bz * p->n * rs));
+    SG_TRY(p->ws.alloc(&p->ws_z, Bz * p->npad * rs));
+    SG_TRY(p->ws.alloc(&p->ws_beta, Bz * p->LM * rs));
+    SG_TRY(p->ws.alloc(&p->ws_s, Bz * p->LM * rs));
+    SG_TRY(p->ws.alloc(&p->ws_part, (size_t)p->nsplit * Bz * p->n * rs));
+    SG_TRY(p->ws.alloc(&p->ws_tau2, Bz * (1 + nblk) * sizeof(double)));
+    SG_TRY(p->ws.alloc(&p->ws_sec_bsq, Bz * p->L * sizeof(double)));
+    SG_TRY(p->ws.alloc(&p->ws_idx, Bz * p->L * sizeof(int32_t)));
     p->cap_B = B;
     return SG_OK;
 }
 
 static void integ_free_ws(sg_dense_plan *p) {
-    void *bufs[] = {p->wi_alpha, p->wi_gamma, p->wi_vk0, p->wi_vk, p->wi_llr, p->wi_app, p->wi_it, p->wi_part,
-                    p->wi_ons};
-    for (void *b : bufs)
-        if (b) hipFree(b);
-    p->wi_alpha = p->wi_gamma = p->wi_vk0 = p->wi_vk = p->wi_llr = p->wi_app = nullptr;
-    p->wi_it = nullptr;
-    p->wi_part = p->wi_ons = nullptr;
+    p->wi.release();
     p->cap_Bi = 0;
 }
 
@@ -77,33 +70,23 @@ static int integ_ensure_ws(sg_dense_plan *p, int B, int nbits) {
     if (B <= p->cap_Bi) return SG_OK;
     integ_free_ws(p);
     const size_t rs = rsize(p), Bz = (size_t)B;
-    SG_HIP(hipMalloc(&p->wi_alpha, Bz * p->LM * rs));
-    SG_HIP(hipMalloc(&p->wi_gamma, Bz * p->LM * rs));
-    SG_HIP(hipMalloc(&p->wi_vk0, Bz * nbits * rs));
-    SG_HIP(hipMalloc(&p->wi_vk, Bz * nbits * rs));
-    SG_HIP(hipMalloc(&p->wi_llr, Bz * nbits * rs));
-    SG_HIP(hipMalloc(&p->wi_app, Bz * nbits * rs));
-    SG_HIP(hipMalloc(&p->wi_it, Bz * nbits * sizeof(int32_t)));
-    SG_HIP(hipMalloc(&p->wi_part, Bz * p->L * sizeof(double)));
-    SG_HIP(hipMalloc(&p->wi_ons, Bz * sizeof(double)));
+    SG_TRY(p->wi.alloc(&p->wi_alpha, Bz * p->LM * rs));
+    SG_TRY(p->wi.alloc(&p->wi_gamma, Bz * p->LM * rs));
+    SG_TRY(p->wi.alloc(&p->wi_vk0, Bz * nbits * rs));
+    SG_TRY(p->wi.alloc(&p->wi_vk, Bz * nbits * rs));
+    SG_TRY(p->wi.alloc(&p->wi_llr, Bz * nbits * rs));
+    SG_TRY(p->wi.alloc(&p->wi_app, Bz * nbits * rs));
+    SG_TRY(p->wi.alloc(&p->wi_it, Bz * nbits * sizeof(int32_t)));
+    SG_TRY(p->wi.alloc(&p->wi_part, Bz * p->L * sizeof(double)));
+    SG_TRY(p->wi.alloc(&p->wi_ons, Bz * sizeof(double)));
     p->cap_Bi = B;
-    return SG_OK;
-}
-
-static int dense_ensure_io(sg_dense_plan *p, size_t bytes) {
-    if (bytes <= p->ws_io_bytes) return SG_OK;
-    if (p->ws_io) hipFree(p->ws_io);
-    p->ws_io = nullptr;
-    p->ws_io_bytes = 0;
-    SG_HIP(hipMalloc(&p->ws_io, bytes));
-    p->ws_io_bytes = bytes;
     return SG_OK;
 }
 
 template <typename T>
 static DenseBufs<T> dbufs(const sg_dense_plan *p, int B, const void *y) {
     DenseBufs<T> d;
-    d.A = (const T *)p->A; d.n = p->n; d.npad = p->npad; d.L = p->L; d.M = p->M; d.LM = p->LM; d.B = B; d.P = p->P;
+    d.A = p->A.at<const T>(); d.n = p->n; d.npad = p->npad; d.L = p->L; d.M = p->M; d.LM = p->LM; d.B = B; d.P = p->P;
     d.y = (const T *)(y ? y : p->ws_y); d.z = (T *)p->ws_z; d.beta = (T *)p->ws_beta; d.s = (T *)p->ws_s;
     d.part = (T *)p->ws_part; d.nsplit = p->nsplit; d.tau2 = p->ws_tau2; d.bsq = nullptr;
     d.sec_bsq = p->ws_sec_bsq;
@@ -132,7 +115,7 @@ static int plan_common(int n, int L, int M, double P, int precision, sg_dense_pl
         p->nsplit = (int)ns;
     }
     const size_t bytes = (size_t)n * LM * (precision == SG_F64 ? 8 : 4);
-    if (hipMalloc(&p->A, bytes) != hipSuccess) {
+    if (p->A.ensure(bytes) != SG_OK) {
         delete p;
         return fail(SG_ERR_NOMEM, "cannot allocate the %zu-byte design matrix", bytes);
     }
@@ -190,8 +173,8 @@ static int iteration_impl(sg_dense_plan *p, const double *y, const double *beta,
                           double *beta_out, double *z_out, double *tau_out, hipStream_t s) {
     SG_TRY(dense_ensure_ws(p, 1));
     const size_t n = p->n, LM = p->LM;
-    SG_TRY(dense_ensure_io(p, (LM + 2 * p->npad) * 8));
-    double *io = (double *)p->ws_io;
+    SG_TRY(p->io.ensure((LM + 2 * p->npad) * 8));
+    double *io = p->io.at<double>();
     std::vector<double> zp(p->npad, 0.0);
     std::copy(z, z + n, zp.begin());
     SG_HIP(hipMemcpyAsync(io, beta, LM * 8, hipMemcpyHostToDevice, s));
@@ -285,23 +268,18 @@ static int integ_host_call(int precision, std::initializer_list<std::pair<const 
     SG_TRY(ensure_device());
     hipStream_t s = lib_stream();
     const size_t rs = precision == SG_F64 ? 8 : 4;
-    std::vector<void *> dev;
-    auto cleanup = [&] {
-        for (void *v : dev) hipFree(v);
-    };
+    // every array in the call's precision (a) and as staged doubles (st): the pool's slots, so sized once and
+    // declared before it
+    std::vector<void *> dev(2 * (ins.size() + outs.size()), nullptr);
+    DevPool pool;
+    size_t nd = 0;
     int rc = SG_OK;
     std::vector<void *> din, dout;
     for (auto &in : ins) {
-        void *a = nullptr, *st = nullptr;
-        if (hipMalloc(&a, std::max<size_t>(1, in.second * rs)) != hipSuccess ||
-            hipMalloc(&st, std::max<size_t>(1, in.second * 8)) != hipSuccess) {
-            if (a) hipFree(a);
-            if (st) hipFree(st);
-            cleanup();
+        void *&a = dev[nd], *&st = dev[nd + 1];
+        nd += 2;
+        if (pool.alloc(&a, in.second * rs) != SG_OK || pool.alloc(&st, in.second * 8) != SG_OK)
             return fail(SG_ERR_NOMEM, "device buffers");
-        }
-        dev.push_back(a);
-        dev.push_back(st);
         if (in.first) {
             if (hipMemcpyAsync(st, in.first, in.second * 8, hipMemcpyHostToDevice, s) != hipSuccess) rc = SG_ERR_HIP;
             if (precision == SG_F64)
@@ -313,16 +291,10 @@ static int integ_host_call(int precision, std::initializer_list<std::pair<const 
         din.push_back(in.first ? a : nullptr);
     }
     for (auto &o : outs) {
-        void *a = nullptr, *st = nullptr;
-        if (hipMalloc(&a, std::max<size_t>(1, o.second * rs)) != hipSuccess ||
-            hipMalloc(&st, std::max<size_t>(1, o.second * 8)) != hipSuccess) {
-            if (a) hipFree(a);
-            if (st) hipFree(st);
-            cleanup();
+        void *&a = dev[nd], *&st = dev[nd + 1];
+        nd += 2;
+        if (pool.alloc(&a, o.second * rs) != SG_OK || pool.alloc(&st, o.second * 8) != SG_OK)
             return fail(SG_ERR_NOMEM, "device buffers");
-        }
-        dev.push_back(a);
-        dev.push_back(st);
         dout.push_back(a);
         dout.push_back(st);
     }
@@ -340,7 +312,6 @@ static int integ_host_call(int precision, std::initializer_list<std::pair<const 
         if (hipMemcpyAsync(o.first, st, o.second * 8, hipMemcpyDeviceToHost, s) != hipSuccess) rc = SG_ERR_HIP;
     }
     if (hipStreamSynchronize(s) != hipSuccess && rc == SG_OK) rc = SG_ERR_HIP;
-    cleanup();
     return rc == SG_OK ? SG_OK : fail(rc, "integrated glue call failed");
 }
 
@@ -358,19 +329,19 @@ int sg_dense_plan_create(const double *A, int n, int L, int M, double P, int pre
     hipStream_t s = lib_stream();
     int rc = SG_OK;
     if (precision == SG_F64) {
-        if (hipMemcpy(p->A, A, nn * 8, hipMemcpyHostToDevice) != hipSuccess) rc = SG_ERR_HIP;
+        if (hipMemcpy(p->A.at(), A, nn * 8, hipMemcpyHostToDevice) != hipSuccess) rc = SG_ERR_HIP;
     } else {
         // stream the double matrix through a staging buffer, cast on the device
         const size_t chunk = std::min<size_t>(nn, (size_t)1 << 26);
-        double *stage = nullptr;
-        if (hipMalloc(&stage, chunk * 8) != hipSuccess) rc = SG_ERR_NOMEM;
+        DevMem stage;
+        if (stage.ensure(chunk * 8) != SG_OK) rc = SG_ERR_NOMEM;
         for (size_t o = 0; rc == SG_OK && o < nn; o += chunk) {
             const size_t c = std::min(chunk, nn - o);
-            if (hipMemcpyAsync(stage, A + o, c * 8, hipMemcpyHostToDevice, s) != hipSuccess) rc = SG_ERR_HIP;
-            hipLaunchKernelGGL(cast_to<float>, dim3(grid_for(c)), dim3(256), 0, s, stage, (float *)p->A + o, c);
+            if (hipMemcpyAsync(stage.at(), A + o, c * 8, hipMemcpyHostToDevice, s) != hipSuccess) rc = SG_ERR_HIP;
+            hipLaunchKernelGGL(cast_to<float>, dim3(grid_for(c)), dim3(256), 0, s, stage.at<const double>(),
+                               p->A.at<float>() + o, c);
             if (hipStreamSynchronize(s) != hipSuccess) rc = SG_ERR_HIP;
         }
-        if (stage) hipFree(stage);
     }
     if (rc != SG_OK) {
         sg_dense_plan_destroy(p);
@@ -384,8 +355,8 @@ int sg_dense_plan_create_random(int n, int L, int M, double P, uint64_t seed, in
     sg_dense_plan *p = nullptr;
     SG_TRY(plan_common(n, L, M, P, precision, out, &p));
     hipStream_t s = lib_stream();
-    int rc = precision == SG_F64 ? dense_launch_gen_A<double>((double *)p->A, n, p->LM, seed, s)
-                                 : dense_launch_gen_A<float>((float *)p->A, n, p->LM, seed, s);
+    int rc = precision == SG_F64 ? dense_launch_gen_A<double>(p->A.at<double>(), n, p->LM, seed, s)
+                                 : dense_launch_gen_A<float>(p->A.at<float>(), n, p->LM, seed, s);
     if (rc == SG_OK && hipStreamSynchronize(s) != hipSuccess) rc = SG_ERR_HIP;
     if (rc != SG_OK) {
         sg_dense_plan_destroy(p);
@@ -396,10 +367,6 @@ int sg_dense_plan_create_random(int n, int L, int M, double P, uint64_t seed, in
 }
 
 int sg_dense_plan_destroy(sg_dense_plan *p) {
-    if (!p) return SG_OK;
-    dense_free_ws(p);
-    integ_free_ws(p);
-    if (p->A) hipFree(p->A);
     delete p;
     return SG_OK;
 }
@@ -435,24 +402,22 @@ int sg_dense_amp(sg_dense_plan *p, const double *y, int B, int t_max, double *be
     hipStream_t s = lib_stream();
     SG_TRY(dense_ensure_ws(p, B));
     const size_t ny = (size_t)B * p->n, nb = (size_t)B * p->LM;
-    SG_TRY(dense_ensure_io(p, std::max(ny, nb) * 8));
-    SG_HIP(hipMemcpyAsync(p->ws_io, y, ny * 8, hipMemcpyHostToDevice, s));
+    SG_TRY(p->io.ensure(std::max(ny, nb) * 8));
+    double *io = p->io.at<double>();
+    SG_HIP(hipMemcpyAsync(io, y, ny * 8, hipMemcpyHostToDevice, s));
     if (p->precision == SG_F64) {
-        SG_HIP(hipMemcpyAsync(p->ws_y, p->ws_io, ny * 8, hipMemcpyDeviceToDevice, s));
+        SG_HIP(hipMemcpyAsync(p->ws_y, io, ny * 8, hipMemcpyDeviceToDevice, s));
         SG_TRY(amp_impl<double>(p, p->ws_y, B, t_max, s));
         SG_HIP(hipMemcpyAsync(beta, p->ws_beta, nb * 8, hipMemcpyDeviceToHost, s));
         SG_HIP(hipMemcpyAsync(s_out, p->ws_s, nb * 8, hipMemcpyDeviceToHost, s));
     } else {
-        hipLaunchKernelGGL(cast_to<float>, dim3(grid_for(ny)), dim3(256), 0, s, (const double *)p->ws_io,
-                           (float *)p->ws_y, ny);
+        hipLaunchKernelGGL(cast_to<float>, dim3(grid_for(ny)), dim3(256), 0, s, (const double *)io, (float *)p->ws_y, ny);
         SG_TRY(amp_impl<float>(p, p->ws_y, B, t_max, s));
-        hipLaunchKernelGGL(cast_from<float>, dim3(grid_for(nb)), dim3(256), 0, s, (const float *)p->ws_beta,
-                           (double *)p->ws_io, nb);
-        SG_HIP(hipMemcpyAsync(beta, p->ws_io, nb * 8, hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(cast_from<float>, dim3(grid_for(nb)), dim3(256), 0, s, (const float *)p->ws_beta, io, nb);
+        SG_HIP(hipMemcpyAsync(beta, io, nb * 8, hipMemcpyDeviceToHost, s));
         SG_HIP(hipStreamSynchronize(s));
-        hipLaunchKernelGGL(cast_from<float>, dim3(grid_for(nb)), dim3(256), 0, s, (const float *)p->ws_s,
-                           (double *)p->ws_io, nb);
-        SG_HIP(hipMemcpyAsync(s_out, p->ws_io, nb * 8, hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(cast_from<float>, dim3(grid_for(nb)), dim3(256), 0, s, (const float *)p->ws_s, io, nb);
+        SG_HIP(hipMemcpyAsync(s_out, io, nb * 8, hipMemcpyDeviceToHost, s));
     }
     SG_HIP(hipStreamSynchronize(s));
     return SG_OK;
@@ -509,7 +474,7 @@ int sg_dense_state_device(sg_dense_plan *p, void **d_beta, void **d_s) {
 
 int sg_dense_plan_matrix_device(const sg_dense_plan *p, const void **d_A) {
     SG_CHECK_ARG(p && d_A, "null argument");
-    *d_A = p->A;
+    *d_A = p->A.at();
     return SG_OK;
 }
 
@@ -591,10 +556,10 @@ int sg_integrated_decode(sg_dense_plan *p, sg_graph *g, int mode, int K, const d
     hipStream_t s = lib_stream();
     SG_TRY(dense_ensure_ws(p, B));
     const size_t rs = rsize(p), ny = (size_t)B * p->n;
-    SG_TRY(dense_ensure_io(p, ny * 8 + nbits + (size_t)B * t_max * 8 + 64));
-    double *io = (double *)p->ws_io;
+    SG_TRY(p->io.ensure(ny * 8 + nbits + (size_t)B * t_max * 8 + 64));
+    double *io = p->io.at<double>();
     uint8_t *dbits = (uint8_t *)(io + ny);
-    double *dtau = (double *)((char *)p->ws_io + ((ny * 8 + nbits + 63) / 64) * 64);
+    double *dtau = p->io.at<double>(((ny * 8 + nbits + 63) / 64) * 64);
     SG_HIP(hipMemcpyAsync(io, y, ny * 8, hipMemcpyHostToDevice, s));
     if (p->precision == SG_F32)  // cast into the plan's own y buffer
         hipLaunchKernelGGL(cast_to<float>, dim3(grid_for(ny)), dim3(256), 0, s, (const double *)io, (float *)p->ws_y,
@@ -643,11 +608,12 @@ int sg_differentiated_eta(int precision, int posteriors, const double *beta, con
     while ((1 << logM) < M) ++logM;
     const size_t nn = (size_t)B * L * M, nv = (size_t)B * L * logM;
     SG_TRY(ensure_device());
-    double *dtau = nullptr, *dpart = nullptr;
-    SG_HIP(hipMalloc(&dtau, std::max<size_t>(1, B) * 8));
-    SG_HIP(hipMalloc(&dpart, std::max<size_t>(1, (size_t)B * L) * 8));
+    DevMem mtau, mpart;
+    SG_TRY(mtau.ensure(std::max<size_t>(1, B) * 8));
+    SG_TRY(mpart.ensure(std::max<size_t>(1, (size_t)B * L) * 8));
+    double *dtau = mtau.at<double>(), *dpart = mpart.at<double>();
     hipMemcpy(dtau, tau2, (size_t)B * 8, hipMemcpyHostToDevice);
-    const int rc = integ_host_call(
+    return integ_host_call(
         precision, {{beta, nn}, {gamma, gamma ? nn : 0}, {alpha, nn}, {vk, nv}, {vk0, nv}}, {{out, nn}},
         [&](auto &in, auto &o, hipStream_t s) {
             return precision == SG_F64
@@ -660,9 +626,6 @@ int sg_differentiated_eta(int precision, int posteriors, const double *beta, con
                                                   (const float *)in[4], dtau, B, L, M, sqrt_nPl, dpart, nullptr,
                                                   (float *)o[0], s);
         });
-    hipFree(dtau);
-    hipFree(dpart);
-    return rc;
 }
 
 }  // extern "C"

@@ -6,14 +6,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <list>
 #include <mutex>
 #include <vector>
 
 #include "bp.hpp"
+#include "device_mem.hpp"
 
 // What the layered schedule needs for one layer size of a graph (bp.hpp BpLayArgs)
 struct sg_layer_plan {
     int layer = 0, nlayers = 0, slots = 0;
+    sg::DevPool tables;
     uint16_t *d_evar = nullptr;
     int32_t *d_loff = nullptr;
 };
@@ -21,10 +24,12 @@ struct sg_layer_plan {
 struct sg_graph {
     int device = 0;
     int nv = 0, nc = 0, nmsg = 0, max_cdeg = 0, max_vdeg = 0, slots = 0;
+    sg::DevPool tables;  // d_voff, d_port_slot, d_cdeg and the d_grp_* below
     int32_t *d_voff = nullptr;
     int32_t *d_port_slot = nullptr;
     uint8_t *d_cdeg = nullptr;
     // grow-only staging for the host entry points
+    sg::DevPool staging;
     void *d_ch = nullptr, *d_app = nullptr;
     int32_t *d_it = nullptr;
     size_t cap_bytes = 0;
@@ -35,10 +40,21 @@ struct sg_graph {
     int grp_ntab = 0, grp_msg_bytes = 0, grp_vj = 0, grp_cj = 0;
     int32_t *d_grp_meta = nullptr, *d_grp_vmap = nullptr;
     uint16_t *d_grp_vtab = nullptr;
-    std::vector<sg_layer_plan> layers;  // layered schedule: one plan per layer size used so far
+    // layered schedule: one plan per layer size used so far (a list: a plan's pool must not move)
+    std::list<sg_layer_plan> layers;
 };
 
 namespace sg {
+
+// Allocates each slot in pool and uploads its host vector on stream s, then synchronises:
+// upload_all(pool, s, &slot0, vec0, &slot1, vec1, ...)
+static bool upload_all(DevPool &, hipStream_t s) { return hipStreamSynchronize(s) == hipSuccess; }
+template <class X, class... Rest>
+static bool upload_all(DevPool &pool, hipStream_t s, X **slot, const std::vector<X> &src, Rest &&...rest) {
+    return pool.alloc(slot, sizeof(X) * src.size()) == SG_OK &&
+           hipMemcpyAsync(*slot, src.data(), sizeof(X) * src.size(), hipMemcpyHostToDevice, s) == hipSuccess &&
+           upload_all(pool, s, rest...);
+}
 
 // Longest-processing-time assignment of groups (weights w) to GRP_WAVES waves
 // of at most `cap` groups each; returns the wave and position of every group.
@@ -220,17 +236,9 @@ static bool build_groups(sg_graph *g, const int64_t *vdeg, const int64_t *cdeg, 
     if (!grp_layout(g->nv, g->nc, g->nmsg, g->max_vdeg, g->max_cdeg, vdeg, cdeg, intrlv, voff, coff, grp_pairs(),
                     lay))
         return false;
-    const std::vector<int32_t> &meta = lay.meta, &vmap = lay.vmap;
-    const std::vector<uint16_t> &vtab = lay.vtab;
-    bool ok = hipMalloc(&g->d_grp_meta, sizeof(int32_t) * meta.size()) == hipSuccess &&
-              hipMalloc(&g->d_grp_vmap, sizeof(int32_t) * vmap.size()) == hipSuccess &&
-              hipMalloc(&g->d_grp_vtab, sizeof(uint16_t) * vtab.size()) == hipSuccess;
-    ok = ok && hipMemcpyAsync(g->d_grp_meta, meta.data(), sizeof(int32_t) * meta.size(), hipMemcpyHostToDevice, s) == hipSuccess &&
-         hipMemcpyAsync(g->d_grp_vmap, vmap.data(), sizeof(int32_t) * vmap.size(), hipMemcpyHostToDevice, s) == hipSuccess &&
-         hipMemcpyAsync(g->d_grp_vtab, vtab.data(), sizeof(uint16_t) * vtab.size(), hipMemcpyHostToDevice, s) == hipSuccess &&
-         hipStreamSynchronize(s) == hipSuccess;
-    if (!ok) return false;
-    g->grp_ntab = (int)vtab.size();
+    if (!upload_all(g->tables, s, &g->d_grp_meta, lay.meta, &g->d_grp_vmap, lay.vmap, &g->d_grp_vtab, lay.vtab))
+        return false;
+    g->grp_ntab = (int)lay.vtab.size();
     g->grp_msg_bytes = lay.msg_bytes;
     g->grp_vj = lay.vj;
     g->grp_cj = lay.cj;
@@ -238,39 +246,51 @@ static bool build_groups(sg_graph *g, const int64_t *vdeg, const int64_t *cdeg, 
     return true;
 }
 
-static int build_graph(const int64_t *vdeg, const int64_t *cdeg, const int64_t *intrlv, int nv, int nc,
-                       int nmsg, sg_graph **out) {
-    SG_CHECK_ARG(vdeg && cdeg && intrlv && out, "null graph array");
-    SG_CHECK_ARG(nv > 0 && nc > 0 && nmsg > 0, "empty graph (Nv=%d Nc=%d Nmsg=%d)", nv, nc, nmsg);
-    SG_TRY(ensure_device());
-    std::vector<int32_t> voff(nv + 1), coff(nc + 1);
+// The validation every entry point that takes graph arrays shares, before anything indexes with them: degree
+// ranges, degree sums against Nmsg, intrlv a permutation of [0, Nmsg).  Returns the variables' and the checks'
+// port offsets and the largest degrees.  Host only; the arrays are non-null and the counts positive.
+static int validate_graph(const int64_t *vdeg, const int64_t *cdeg, const int64_t *intrlv, int nv, int nc, int nmsg,
+                          std::vector<int32_t> &voff, std::vector<int32_t> &coff, int *max_vdeg, int *max_cdeg) {
+    voff.assign(nv + 1, 0);
+    coff.assign(nc + 1, 0);
     int max_v = 0, max_c = 0;
-    voff[0] = 0;
     for (int v = 0; v < nv; ++v) {
         SG_CHECK_ARG(vdeg[v] >= 0 && vdeg[v] < 256, "variable degree %lld out of range", (long long)vdeg[v]);
         voff[v + 1] = voff[v] + (int32_t)vdeg[v];
-        if (vdeg[v] > max_v) max_v = (int)vdeg[v];
+        max_v = std::max(max_v, (int)vdeg[v]);
     }
-    coff[0] = 0;
     for (int c = 0; c < nc; ++c) {
         SG_CHECK_ARG(cdeg[c] >= 2 && cdeg[c] < 256, "check degree %lld out of range (need 2..255)", (long long)cdeg[c]);
         coff[c + 1] = coff[c] + (int32_t)cdeg[c];
-        if (cdeg[c] > max_c) max_c = (int)cdeg[c];
+        max_c = std::max(max_c, (int)cdeg[c]);
     }
     SG_CHECK_ARG(voff[nv] == nmsg && coff[nc] == nmsg,
                  "degree sums (%d, %d) do not match Nmsg=%d", voff[nv], coff[nc], nmsg);
-    // message index -> (check, port) -> LDS slot k*nc + c
-    std::vector<int32_t> msg_slot(nmsg);
-    for (int c = 0; c < nc; ++c)
-        for (int k = 0; k < coff[c + 1] - coff[c]; ++k) msg_slot[coff[c] + k] = k * nc + c;
-    std::vector<int32_t> port_slot(nmsg);
     std::vector<uint8_t> seen(nmsg, 0);
     for (int p = 0; p < nmsg; ++p) {
         const int64_t m = intrlv[p];
         SG_CHECK_ARG(m >= 0 && m < nmsg && !seen[m], "intrlv is not a permutation of [0, Nmsg)");
         seen[m] = 1;
-        port_slot[p] = msg_slot[m];
     }
+    *max_vdeg = max_v;
+    *max_cdeg = max_c;
+    return SG_OK;
+}
+
+static int build_graph(const int64_t *vdeg, const int64_t *cdeg, const int64_t *intrlv, int nv, int nc,
+                       int nmsg, sg_graph **out) {
+    SG_CHECK_ARG(vdeg && cdeg && intrlv && out, "null graph array");
+    SG_CHECK_ARG(nv > 0 && nc > 0 && nmsg > 0, "empty graph (Nv=%d Nc=%d Nmsg=%d)", nv, nc, nmsg);
+    SG_TRY(ensure_device());
+    std::vector<int32_t> voff, coff;
+    int max_v = 0, max_c = 0;
+    SG_TRY(validate_graph(vdeg, cdeg, intrlv, nv, nc, nmsg, voff, coff, &max_v, &max_c));
+    // message index -> (check, port) -> LDS slot k*nc + c
+    std::vector<int32_t> msg_slot(nmsg);
+    for (int c = 0; c < nc; ++c)
+        for (int k = 0; k < coff[c + 1] - coff[c]; ++k) msg_slot[coff[c] + k] = k * nc + c;
+    std::vector<int32_t> port_slot(nmsg);
+    for (int p = 0; p < nmsg; ++p) port_slot[p] = msg_slot[intrlv[p]];
     std::vector<uint8_t> cd(nc);
     for (int c = 0; c < nc; ++c) cd[c] = (uint8_t)cdeg[c];
 
@@ -282,15 +302,8 @@ static int build_graph(const int64_t *vdeg, const int64_t *cdeg, const int64_t *
     g->h_cdeg.assign(cdeg, cdeg + nc);
     g->h_intrlv.assign(intrlv, intrlv + nmsg);
     hipStream_t s = lib_stream();
-    bool ok = hipMalloc(&g->d_voff, sizeof(int32_t) * (nv + 1)) == hipSuccess &&
-              hipMalloc(&g->d_port_slot, sizeof(int32_t) * nmsg) == hipSuccess &&
-              hipMalloc(&g->d_cdeg, nc) == hipSuccess;
-    ok = ok && hipMemcpyAsync(g->d_voff, voff.data(), sizeof(int32_t) * (nv + 1), hipMemcpyHostToDevice, s) == hipSuccess &&
-         hipMemcpyAsync(g->d_port_slot, port_slot.data(), sizeof(int32_t) * nmsg, hipMemcpyHostToDevice, s) == hipSuccess &&
-         hipMemcpyAsync(g->d_cdeg, cd.data(), nc, hipMemcpyHostToDevice, s) == hipSuccess &&
-         hipStreamSynchronize(s) == hipSuccess;
-    if (!ok) {
-        sg_ldpc_graph_destroy(g);
+    if (!upload_all(g->tables, s, &g->d_voff, voff, &g->d_port_slot, port_slot, &g->d_cdeg, cd)) {
+        delete g;
         return fail(SG_ERR_NOMEM, "device allocation/upload of the Tanner graph failed");
     }
     build_groups(g, vdeg, cdeg, intrlv, voff, coff, s);  // (optional: the table kernel takes every graph)
@@ -298,30 +311,17 @@ static int build_graph(const int64_t *vdeg, const int64_t *cdeg, const int64_t *
     return SG_OK;
 }
 
-// Variable of every check-ordered message and the checks' message offsets, with graph creation's validation
-// (degree ranges and sums, intrlv a permutation).  Host only.
+// Variable of every check-ordered message and the checks' message offsets, after validate_graph.  Host only.
 static int msg_variables(const int64_t *vdeg, const int64_t *cdeg, const int64_t *intrlv, int nv, int nc, int nmsg,
                          std::vector<int32_t> &coff, std::vector<int32_t> &mvar) {
     SG_CHECK_ARG(vdeg && cdeg && intrlv, "null graph array");
     SG_CHECK_ARG(nv > 0 && nc > 0 && nmsg > 0, "empty graph (Nv=%d Nc=%d Nmsg=%d)", nv, nc, nmsg);
-    coff.assign(nc + 1, 0);
-    for (int c = 0; c < nc; ++c) {
-        SG_CHECK_ARG(cdeg[c] >= 2 && cdeg[c] < 256, "check degree %lld out of range (need 2..255)", (long long)cdeg[c]);
-        SG_CHECK_ARG(coff[c] + cdeg[c] <= nmsg, "check degrees sum past Nmsg=%d", nmsg);
-        coff[c + 1] = coff[c] + (int32_t)cdeg[c];
-    }
-    mvar.assign(nmsg, -1);
-    long p = 0;
-    for (int v = 0; v < nv; ++v) {
-        SG_CHECK_ARG(vdeg[v] >= 0 && vdeg[v] < 256, "variable degree %lld out of range", (long long)vdeg[v]);
-        SG_CHECK_ARG(p + vdeg[v] <= nmsg, "variable degrees sum past Nmsg=%d", nmsg);
-        for (int k = 0; k < (int)vdeg[v]; ++k, ++p) {
-            const int64_t m = intrlv[p];
-            SG_CHECK_ARG(m >= 0 && m < nmsg && mvar[m] < 0, "intrlv is not a permutation of [0, Nmsg)");
-            mvar[m] = v;
-        }
-    }
-    SG_CHECK_ARG(p == nmsg && coff[nc] == nmsg, "degree sums (%ld, %d) do not match Nmsg=%d", p, coff[nc], nmsg);
+    std::vector<int32_t> voff;
+    int max_v = 0, max_c = 0;
+    SG_TRY(validate_graph(vdeg, cdeg, intrlv, nv, nc, nmsg, voff, coff, &max_v, &max_c));
+    mvar.resize(nmsg);
+    for (int v = 0; v < nv; ++v)
+        for (int p = voff[v]; p < voff[v + 1]; ++p) mvar[intrlv[p]] = v;
     return SG_OK;
 }
 
@@ -355,36 +355,30 @@ static int layer_plan(sg_graph *g, int layer, const sg_layer_plan **out) {
         return fail(SG_ERR_UNSUPPORTED, "check degree %d exceeds the supported maximum of %d", g->max_cdeg, LAY_MAXDC);
     if (g->nv > 65536)
         return fail(SG_ERR_UNSUPPORTED, "graph with %d variables exceeds the layered decoder's 16-bit LDS table", g->nv);
-    sg_layer_plan p;
-    p.layer = layer;
-    p.nlayers = g->nc / layer;
-    std::vector<int32_t> loff(p.nlayers);
+    const int nlayers = g->nc / layer;
+    std::vector<int32_t> loff(nlayers);
     long slots = 0;
-    for (int l = 0; l < p.nlayers; ++l) {
+    for (int l = 0; l < nlayers; ++l) {
         int dmax = 0;
         for (int i = 0; i < layer; ++i) dmax = std::max(dmax, (int)g->h_cdeg[l * layer + i]);
         loff[l] = (int32_t)slots;
         slots += (long)dmax * layer;
     }
-    p.slots = (int)slots;
     std::vector<uint16_t> evar(slots, 0);
     for (int c = 0; c < g->nc; ++c)
         for (int k = 0; k < coff[c + 1] - coff[c]; ++k)
             evar[loff[c / layer] + (long)k * layer + c % layer] = (uint16_t)mvar[coff[c] + k];
     hipStream_t s = lib_stream();
     SG_HIP(hipSetDevice(g->device));
-    bool ok = hipMalloc(&p.d_evar, sizeof(uint16_t) * evar.size()) == hipSuccess &&
-              hipMalloc(&p.d_loff, sizeof(int32_t) * loff.size()) == hipSuccess;
-    ok = ok && hipMemcpyAsync(p.d_evar, evar.data(), sizeof(uint16_t) * evar.size(), hipMemcpyHostToDevice, s) == hipSuccess &&
-         hipMemcpyAsync(p.d_loff, loff.data(), sizeof(int32_t) * loff.size(), hipMemcpyHostToDevice, s) == hipSuccess &&
-         hipStreamSynchronize(s) == hipSuccess;
-    if (!ok) {
-        if (p.d_evar) hipFree(p.d_evar);
-        if (p.d_loff) hipFree(p.d_loff);
+    sg_layer_plan &p = g->layers.emplace_back();  // in place: the plan's pool records its members' addresses
+    p.layer = layer;
+    p.nlayers = nlayers;
+    p.slots = (int)slots;
+    if (!upload_all(p.tables, s, &p.d_evar, evar, &p.d_loff, loff)) {
+        g->layers.pop_back();
         return fail(SG_ERR_NOMEM, "device allocation/upload of the layer tables failed");
     }
-    g->layers.push_back(p);
-    *out = &g->layers.back();
+    *out = &p;
     return SG_OK;
 }
 
@@ -479,16 +473,12 @@ static int decode_device(sg_graph *g, int dectype, int precision, const void *d_
 static int ensure_staging(sg_graph *g, int B) {
     const size_t need = (size_t)B * g->nv * sizeof(double);
     if (need <= g->cap_bytes && B <= g->cap_b) return SG_OK;
-    if (g->d_ch) hipFree(g->d_ch);
-    if (g->d_app) hipFree(g->d_app);
-    if (g->d_it) hipFree(g->d_it);
-    g->d_ch = g->d_app = nullptr;
-    g->d_it = nullptr;
+    g->staging.release();
     g->cap_bytes = 0;
     g->cap_b = 0;
-    SG_HIP(hipMalloc(&g->d_ch, need));
-    SG_HIP(hipMalloc(&g->d_app, need));
-    SG_HIP(hipMalloc(&g->d_it, sizeof(int32_t) * B));
+    SG_TRY(g->staging.alloc(&g->d_ch, need));
+    SG_TRY(g->staging.alloc(&g->d_app, need));
+    SG_TRY(g->staging.alloc(&g->d_it, sizeof(int32_t) * B));
     g->cap_bytes = need;
     g->cap_b = B;
     return SG_OK;
@@ -596,20 +586,6 @@ int sg_ldpc_graph_create(const int64_t *vdeg, const int64_t *cdeg, const int64_t
 }
 
 int sg_ldpc_graph_destroy(sg_graph *g) {
-    if (!g) return SG_OK;
-    if (g->d_voff) hipFree(g->d_voff);
-    if (g->d_port_slot) hipFree(g->d_port_slot);
-    if (g->d_cdeg) hipFree(g->d_cdeg);
-    if (g->d_grp_meta) hipFree(g->d_grp_meta);
-    if (g->d_grp_vmap) hipFree(g->d_grp_vmap);
-    if (g->d_grp_vtab) hipFree(g->d_grp_vtab);
-    if (g->d_ch) hipFree(g->d_ch);
-    if (g->d_app) hipFree(g->d_app);
-    if (g->d_it) hipFree(g->d_it);
-    for (sg_layer_plan &p : g->layers) {
-        hipFree(p.d_evar);
-        hipFree(p.d_loff);
-    }
     delete g;
     return SG_OK;
 }
@@ -630,28 +606,9 @@ int sg_ldpc_grouped_layout(const int64_t *vdeg, const int64_t *cdeg, const int64
     using namespace sg;
     SG_CHECK_ARG(vdeg && cdeg && intrlv && info, "null argument");
     SG_CHECK_ARG(nv > 0 && nc > 0 && nmsg > 0, "empty graph (Nv=%d Nc=%d Nmsg=%d)", nv, nc, nmsg);
-    std::vector<int32_t> voff(nv + 1, 0), coff(nc + 1, 0);
+    std::vector<int32_t> voff, coff;
     int max_v = 0, max_c = 0;
-    for (int v = 0; v < nv; ++v) {
-        SG_CHECK_ARG(vdeg[v] >= 0 && vdeg[v] < 256, "variable degree %lld out of range", (long long)vdeg[v]);
-        voff[v + 1] = voff[v] + (int32_t)vdeg[v];
-        max_v = std::max(max_v, (int)vdeg[v]);
-    }
-    for (int c = 0; c < nc; ++c) {
-        SG_CHECK_ARG(cdeg[c] >= 2 && cdeg[c] < 256, "check degree %lld out of range (need 2..255)", (long long)cdeg[c]);
-        coff[c + 1] = coff[c] + (int32_t)cdeg[c];
-        max_c = std::max(max_c, (int)cdeg[c]);
-    }
-    SG_CHECK_ARG(voff[nv] == nmsg && coff[nc] == nmsg, "degree sums (%d, %d) do not match Nmsg=%d", voff[nv],
-                 coff[nc], nmsg);
-    {  // the same permutation check as graph creation: grp_layout indexes msg_addr[intrlv[p]]
-        std::vector<uint8_t> seen(nmsg, 0);
-        for (int p = 0; p < nmsg; ++p) {
-            const int64_t m = intrlv[p];
-            SG_CHECK_ARG(m >= 0 && m < nmsg && !seen[m], "intrlv is not a permutation of [0, Nmsg)");
-            seen[m] = 1;
-        }
-    }
+    SG_TRY(validate_graph(vdeg, cdeg, intrlv, nv, nc, nmsg, voff, coff, &max_v, &max_c));
     GrpLayout lay;
     const bool ok = grp_layout(nv, nc, nmsg, max_v, max_c, vdeg, cdeg, intrlv, voff, coff, pairs != 0, lay);
     const int32_t v[10] = {ok ? 1 : 0, lay.vj, lay.cj, ok ? grp_kvj(lay.vj, lay.cj) : 0,
@@ -771,15 +728,14 @@ int minsum(double *ch, long *vdeg, long *cdeg, long *intrlv, int Nv, int Nc, int
 double Lxfb(double *L, long dc, int corr_flag) {
     if (!L || dc < 2 || dc > 64 || ensure_device() != SG_OK) return NAN;
     hipStream_t s = lib_stream();
-    double *d = nullptr;
-    if (hipMalloc(&d, sizeof(double) * (dc + 1)) != hipSuccess) return NAN;
-    double agg = NAN;
+    DevMem mem;
+    if (mem.ensure(sizeof(double) * (dc + 1)) != SG_OK) return NAN;
+    double *d = mem.at<double>(), agg = NAN;
     bool ok = hipMemcpyAsync(d, L, sizeof(double) * dc, hipMemcpyHostToDevice, s) == hipSuccess &&
               lxfb_launch(d, (int)dc, corr_flag ? 1 : 0, d + dc, s) == SG_OK &&
               hipMemcpyAsync(L, d, sizeof(double) * dc, hipMemcpyDeviceToHost, s) == hipSuccess &&
               hipMemcpyAsync(&agg, d + dc, sizeof(double), hipMemcpyDeviceToHost, s) == hipSuccess &&
               hipStreamSynchronize(s) == hipSuccess;
-    hipFree(d);
     return ok ? agg : NAN;
 }
 

@@ -8,12 +8,12 @@
 #include <algorithm>
 #include <vector>
 
-#include "common.hpp"
+#include "device_mem.hpp"
 #include "philox.hpp"
 
 struct sg_ldpc_encoder {
     int K = 0, N = 0, Kw = 0;  // information bits, codeword bits, 64-bit words per info word
-    uint64_t *pt = nullptr;    // [N-K][Kw] parity bit j = parity of popcount(pt[j] & info)
+    sg::DevMem pt;             // [N-K][Kw] 64-bit words: parity bit j = parity of popcount(pt[j] & info)
 };
 
 namespace sg {
@@ -188,12 +188,11 @@ int sg_ldpc_encoder_create(const uint8_t *parity, int K, int N, sg_ldpc_encoder 
             if (parity[(size_t)k * R + j] & 1) pt[(size_t)j * Kw + k / 64] |= (uint64_t)1 << (k % 64);
     sg_ldpc_encoder *e = new sg_ldpc_encoder();
     e->K = K; e->N = N; e->Kw = Kw;
-    if (hipMalloc(&e->pt, pt.size() * 8) != hipSuccess) {
+    if (e->pt.ensure(pt.size() * 8) != SG_OK) {
         delete e;
         return fail(SG_ERR_NOMEM, "encoder table");
     }
-    if (hipMemcpy(e->pt, pt.data(), pt.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(e->pt);
+    if (hipMemcpy(e->pt.at(), pt.data(), pt.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
         delete e;
         return fail(SG_ERR_HIP, "encoder upload");
     }
@@ -202,8 +201,6 @@ int sg_ldpc_encoder_create(const uint8_t *parity, int K, int N, sg_ldpc_encoder 
 }
 
 int sg_ldpc_encoder_destroy(sg_ldpc_encoder *e) {
-    if (!e) return SG_OK;
-    if (e->pt) hipFree(e->pt);
     delete e;
     return SG_OK;
 }
@@ -213,7 +210,7 @@ int sg_ldpc_encode_device(sg_ldpc_encoder *e, const uint8_t *d_info, int B, uint
     if (B <= 0) return SG_OK;
     SG_TRY(ensure_device());
     hipStream_t s = pick_stream(stream);
-    hipLaunchKernelGGL(ldpc_encode_kernel, dim3(B), dim3(256), (size_t)e->Kw * 8, s, e->pt, e->K, e->N, e->Kw, d_info,
+    hipLaunchKernelGGL(ldpc_encode_kernel, dim3(B), dim3(256), (size_t)e->Kw * 8, s, e->pt.at<const uint64_t>(), e->K, e->N, e->Kw, d_info,
                        d_cw);
     SG_HIP(hipGetLastError());
     return SG_OK;

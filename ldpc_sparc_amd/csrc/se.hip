@@ -21,15 +21,16 @@
 #include <cmath>
 #include <vector>
 
-#include "common.hpp"
+#include "device_mem.hpp"
 
 constexpr int SE_MAX_K = 64;  // largest PSK constellation, as the complex AMP engine
 
 struct sg_se_samples {
     int mc = 0, M = 0;
     bool cplx = false;       // u holds interleaved complex samples
-    double *u = nullptr;     // [mc][M], or [mc][M][2]
-    double *constel = nullptr;  // [SE_MAX_K][2] K-PSK constellation of the last K >= 8 call
+    sg::DevMem u;            // doubles [mc][M], or [mc][M][2]
+    sg::DevMem constel;      // doubles [SE_MAX_K][2]: K-PSK constellation of the last K >= 8 call
+    sg::DevPool ws;          // part, taus, E: grow together with nt_cap
     double *part = nullptr;  // [nt_cap][nblk]
     int nt_cap = 0;
     double *taus = nullptr, *E = nullptr;
@@ -141,12 +142,11 @@ static int se_samples_create(const double *u, int mc, int M, bool cplx, sg_se_sa
     h->M = M;
     h->cplx = cplx;
     const size_t bytes = (size_t)mc * M * (cplx ? 16 : 8);
-    if (hipMalloc(&h->u, bytes) != hipSuccess) {
+    if (h->u.ensure(bytes) != SG_OK) {
         delete h;
         return fail(SG_ERR_NOMEM, "cannot allocate %zu bytes of samples", bytes);
     }
-    if (hipMemcpy(h->u, u, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(h->u);
+    if (hipMemcpy(h->u.at(), u, bytes, hipMemcpyHostToDevice) != hipSuccess) {
         delete h;
         return fail(SG_ERR_HIP, "sample upload failed");
     }
@@ -163,9 +163,6 @@ int sg_se_samples_create_complex(const double *u, int mc, int M, sg_se_samples *
 }
 
 int sg_se_samples_destroy(sg_se_samples *h) {
-    if (!h) return SG_OK;
-    for (void *p : {(void *)h->u, (void *)h->part, (void *)h->taus, (void *)h->E, (void *)h->constel})
-        if (p) hipFree(p);
     delete h;
     return SG_OK;
 }
@@ -179,32 +176,30 @@ int sg_se_expectation(sg_se_samples *h, int K, const double *taus, int nt, doubl
     SG_TRY(ensure_device());
     const int nblk = (h->mc + SE_WAVES - 1) / SE_WAVES;
     if (nt > h->nt_cap) {
-        for (void *p : {(void *)h->part, (void *)h->taus, (void *)h->E})
-            if (p) hipFree(p);
-        h->part = h->taus = h->E = nullptr;
+        h->ws.release();
         h->nt_cap = 0;
-        SG_HIP(hipMalloc(&h->part, (size_t)nt * nblk * 8));
-        SG_HIP(hipMalloc(&h->taus, (size_t)nt * 8));
-        SG_HIP(hipMalloc(&h->E, (size_t)nt * 8));
+        SG_TRY(h->ws.alloc(&h->part, (size_t)nt * nblk * 8));
+        SG_TRY(h->ws.alloc(&h->taus, (size_t)nt * 8));
+        SG_TRY(h->ws.alloc(&h->E, (size_t)nt * 8));
         h->nt_cap = nt;
     }
     hipStream_t s = lib_stream();
     SG_HIP(hipMemcpyAsync(h->taus, taus, (size_t)nt * 8, hipMemcpyHostToDevice, s));
     std::vector<double> c;  // psk_constel, sparc.py:225-239 (alive until the synchronize below)
     if (K >= 8) {
-        if (!h->constel) SG_HIP(hipMalloc(&h->constel, (size_t)SE_MAX_K * 16));
+        SG_TRY(h->constel.ensure((size_t)SE_MAX_K * 16));
         for (int k = 0; k < K; ++k) {
             const double theta = 2.0 * M_PI * k / K;
             c.push_back(std::cos(theta));
             c.push_back(std::sin(theta));
         }
-        SG_HIP(hipMemcpyAsync(h->constel, c.data(), c.size() * 8, hipMemcpyHostToDevice, s));
+        SG_HIP(hipMemcpyAsync(h->constel.at(), c.data(), c.size() * 8, hipMemcpyHostToDevice, s));
     }
     if (h->cplx)
-        hipLaunchKernelGGL(se_E_cplx_kernel, dim3(nblk, nt), dim3(256), 0, s, (const double2 *)h->u, h->mc, h->M, K,
-                           (const double2 *)h->constel, h->taus, h->part, nblk);
+        hipLaunchKernelGGL(se_E_cplx_kernel, dim3(nblk, nt), dim3(256), 0, s, h->u.at<const double2>(), h->mc, h->M, K,
+                           h->constel.at<const double2>(), h->taus, h->part, nblk);
     else
-        hipLaunchKernelGGL(se_E_kernel, dim3(nblk, nt), dim3(256), 0, s, h->u, h->mc, h->M, K, h->taus, h->part, nblk);
+        hipLaunchKernelGGL(se_E_kernel, dim3(nblk, nt), dim3(256), 0, s, h->u.at<const double>(), h->mc, h->M, K, h->taus, h->part, nblk);
     hipLaunchKernelGGL(se_finish_kernel, dim3(nt), dim3(256), 0, s, h->part, nblk, h->mc, h->E);
     SG_HIP(hipGetLastError());
     SG_HIP(hipMemcpyAsync(E, h->E, (size_t)nt * 8, hipMemcpyDeviceToHost, s));

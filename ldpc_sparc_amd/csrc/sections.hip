@@ -2,7 +2,7 @@
 // msg_vector_map_estimator API of sparc.py:402-512 and sparc_new.py:1040-1116),
 // double precision, one wavefront per section.  The fused decoder (eta_kernel
 // in amp_dct.hip) does not use these.
-#include "common.hpp"
+#include "device_mem.hpp"
 
 namespace sg {
 
@@ -50,14 +50,14 @@ int sg_section_softmax(const double *x, int L, int M, double scale, double *out)
     SG_TRY(ensure_device());
     hipStream_t s = lib_stream();
     const size_t bytes = (size_t)L * M * sizeof(double);
-    double *d = nullptr;
-    SG_HIP(hipMalloc(&d, 2 * bytes));
+    DevMem mem;
+    SG_TRY(mem.ensure(2 * bytes));
+    double *d = mem.at<double>();
     SG_HIP(hipMemcpyAsync(d, x, bytes, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(section_softmax_kernel, dim3((L + 3) / 4), dim3(256), 0, s, d, L, M, scale, d + (size_t)L * M);
     SG_HIP(hipGetLastError());
     SG_HIP(hipMemcpyAsync(out, d + (size_t)L * M, bytes, hipMemcpyDeviceToHost, s));
     SG_HIP(hipStreamSynchronize(s));
-    SG_HIP(hipFree(d));
     return SG_OK;
 }
 
@@ -68,15 +68,14 @@ int sg_section_argmax(const double *x, int L, int M, int32_t *idx) {
     SG_TRY(ensure_device());
     hipStream_t s = lib_stream();
     const size_t bytes = (size_t)L * M * sizeof(double);
-    void *d = nullptr;
-    SG_HIP(hipMalloc(&d, bytes + (size_t)L * 4));
-    SG_HIP(hipMemcpyAsync(d, x, bytes, hipMemcpyHostToDevice, s));
-    int32_t *di = (int32_t *)((char *)d + bytes);
-    hipLaunchKernelGGL(section_argmax_kernel, dim3((L + 3) / 4), dim3(256), 0, s, (const double *)d, L, M, di);
+    DevMem mem;
+    SG_TRY(mem.ensure(bytes + (size_t)L * 4));
+    SG_HIP(hipMemcpyAsync(mem.at(), x, bytes, hipMemcpyHostToDevice, s));
+    int32_t *di = mem.at<int32_t>(bytes);
+    hipLaunchKernelGGL(section_argmax_kernel, dim3((L + 3) / 4), dim3(256), 0, s, mem.at<const double>(), L, M, di);
     SG_HIP(hipGetLastError());
     SG_HIP(hipMemcpyAsync(idx, di, (size_t)L * 4, hipMemcpyDeviceToHost, s));
     SG_HIP(hipStreamSynchronize(s));
-    SG_HIP(hipFree(d));
     return SG_OK;
 }
 
