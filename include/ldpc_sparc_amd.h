@@ -141,6 +141,17 @@ int sg_beta_to_llr_device(int precision, const void *d_beta, int B, int L, int M
 int sg_concat_count_errors_device(int precision, const int32_t *d_map_idx, const int32_t *d_true_idx, int B,
                                   int L, int L_unprotected, int logM, const void *d_app, const uint8_t *d_info,
                                   int mults, int N, int K, int64_t *d_counts, void *stream);
+/* BP result -> known sections of the three-stage concatenated decoder (AMP -> BP -> AMP with the BP-decoded
+ * sections known, sg_amp_decode_partial_device): from the BP output d_app [B*mults][N] (`precision`) and its
+ * stopping iterations d_it [B*mults] of a decode with `max_it` iterations, d_known_idx [B][L] = -1 for the
+ * L_unprotected first sections; for protected section l the MSB-first index formed from the hard decisions
+ * app < 0 of its logM bits (bit i of section l is bit (l - L_unprotected) logM + i of the codeword's mults*N
+ * protected bits), provided every LDPC block that holds one of those bits stopped on its syndrome
+ * (it < max_it) -- a section straddles two blocks when logM does not divide N -- and -1 otherwise.  Needs no
+ * graph handle.  SG_ERR_INVALID when the protected sections do not fit the blocks. */
+int sg_concat_known_sections_device(int precision, const void *d_app, const int32_t *d_it, int max_it, int B,
+                                    int mults, int N, int L, int L_unprotected, int logM, int32_t *d_known_idx,
+                                    void *stream);
 
 /* ------------------------------------------------------------- multi-GPU */
 /* One RCCL communicator per process (one process per GPU).  Rank 0 creates
@@ -378,6 +389,32 @@ int sg_amp_decode_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *
                          double awgn_var, int t_max, double rtol, int phi_method,
                          int32_t *d_map_idx, int32_t *d_t_final, double *d_nmse, double *d_psi,
                          void *stream);
+/* AMP with known sections (amp_partial.hip): sg_amp_decode_device's loop (sparc.py:883-999) in which some
+ * sections of a codeword are given.  d_known_idx [B][L] holds a section's index in [0, M), or -1 for a section
+ * to decode; the known set is per codeword.  The denoiser of a known section returns the one-hot of its index (it
+ * adds 1 to sum beta^2, 0 to psi, and 0 to the NMSE where it agrees with d_true_idx); the start is beta0 = the
+ * known one-hots, z0 = y - Ab(beta0), psi0_c = the share of unknown sections of column block c, so gamma0 = W psi0
+ * (flat) or dot(W, psi0) / Lc (power allocation), and iteration 0 has no Onsager term.  Everything else -- phi by
+ * either phi_method, tau, s = beta + tau Az(z / phi), the psi stopping rule, the final MAP on s -- is the
+ * reference loop; a known section reports its known index in d_map_idx.  With every entry -1 this is
+ * sg_amp_decode_device's arithmetic.  Outputs as there (any may be NULL).  Every check precedes any launch or
+ * allocation: SG_ERR_UNSUPPORTED for a spatially coupled plan (W of ndim 2) and for M not a power of two in
+ * [2, 2048] (one wavefront per section, up to 32 entries per lane); SG_ERR_INVALID for bad t_max, rtol,
+ * phi_method, awgn_var as sg_amp_decode_device; B <= 0 returns SG_OK with nothing done.  The device variant treats
+ * a known index outside [-1, M) as unknown.  Works in the plan's workspace on the plan's own operators (never the
+ * companion plan): clears the last-decode state (a following sg_amp_llr* answers SG_ERR_BAD_ARG, as after
+ * sg_amp_apply*) and leaves the plan fit for sg_amp_decode*.  The partial buffers are allocated once per
+ * (plan, B) and freed with the plan; the loop itself enqueues on the stream and polls the active flags as
+ * sg_amp_decode_device does.  A codeword's results do not depend on the batch it is decoded in. */
+int sg_amp_decode_partial_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_known_idx,
+                                 const int32_t *d_true_idx, double awgn_var, int t_max, double rtol,
+                                 int phi_method, int32_t *d_map_idx, int32_t *d_t_final, double *d_nmse,
+                                 double *d_psi, void *stream);
+/* Host variant: arrays as sg_amp_decode plus known_idx [B][L]; blocking.  It scans known_idx: an entry outside
+ * [-1, M) is SG_ERR_INVALID, before anything is launched. */
+int sg_amp_decode_partial(sg_amp_plan *p, const double *y, int B, const int32_t *known_idx,
+                          const int32_t *true_idx, double awgn_var, int t_max, double rtol, int phi_method,
+                          int32_t *map_idx, int32_t *t_final, double *nmse, double *psi);
 /* Soft output of the last decode through this plan (sg_amp_decode_device or
  * sg_amp_decode), in the plan precision: for sections [l0, l0 + nl) of each of
  * the B codewords, P(bit = 0) of the log2 M section bits, MSB first, from the

@@ -88,6 +88,13 @@ SIGNATURES = [
                                  vp, vp, vp, vp]),
     ("sg_amp_decode_device", ct.c_int, [vp, vp, ct.c_int, vp, ct.c_double, ct.c_int, ct.c_double,
                                         ct.c_int, vp, vp, vp, vp, vp]),
+    # AMP with known sections and the BP -> known-sections glue (three-stage concatenated decoder)
+    ("sg_amp_decode_partial", ct.c_int, [vp, vp, ct.c_int, vp, vp, ct.c_double, ct.c_int, ct.c_double, ct.c_int,
+                                         vp, vp, vp, vp]),
+    ("sg_amp_decode_partial_device", ct.c_int, [vp, vp, ct.c_int, vp, vp, ct.c_double, ct.c_int, ct.c_double,
+                                                ct.c_int, vp, vp, vp, vp, vp]),
+    ("sg_concat_known_sections_device", ct.c_int, [ct.c_int, vp, vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                                   ct.c_int, ct.c_int, vp, vp]),
     ("sg_amp_llr_device", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp, vp]),
     ("sg_amp_llr", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp]),
     ("sg_amp_apply", ct.c_int, [vp, ct.c_int, vp, ct.c_int, vp]),

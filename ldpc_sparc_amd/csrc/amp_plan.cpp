@@ -121,6 +121,25 @@ int integ_ensure_ws(sg_amp_plan *p, int B, int nbits) {
     return SG_OK;
 }
 
+int partial_ensure_ws(sg_amp_plan *p, int B) {
+    if (B <= p->cap_Bp) return SG_OK;
+    p->wp.release();
+    p->cap_Bp = 0;
+    const size_t rs = p->precision == SG_F64 ? 8 : 4, Bz = (size_t)B;
+    SG_TRY(p->wp.alloc(&p->wp_u, Bz * p->LM * rs));
+    SG_TRY(p->wp.alloc(&p->wp_r, Bz * p->n * rs));
+    SG_TRY(p->wp.alloc(&p->wp_z, Bz * p->n * rs));
+    SG_TRY(p->wp.alloc(&p->wp_zz, Bz * PART_MAX * sizeof(double)));
+    SG_TRY(p->wp.alloc(&p->wp_bsq, Bz * p->L * sizeof(double)));
+    SG_TRY(p->wp.alloc(&p->wp_err, Bz * p->L * sizeof(double)));
+    SG_TRY(p->wp.alloc(&p->wp_phi, Bz * sizeof(double)));
+    SG_TRY(p->wp.alloc(&p->wp_tau, Bz * p->Lc * sizeof(double)));
+    SG_TRY(p->wp.alloc(&p->wp_active, Bz * sizeof(int32_t)));
+    SG_TRY(p->wp.alloc(&p->wp_known, Bz * p->L * sizeof(int32_t)));
+    p->cap_Bp = B;
+    return SG_OK;
+}
+
 static void plan_free_ws(sg_amp_plan *p) {
     p->ws.release();
     p->io.reset();  // (its own grow rule, ensure_io; freed with the workspace)

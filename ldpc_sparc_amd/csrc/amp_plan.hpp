@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "amp.hpp"
+#include "amp_partial.hpp"
 #include "device_mem.hpp"
 
 using cd = std::complex<double>;
@@ -112,6 +113,16 @@ struct sg_amp_plan {
          *wi_llr = nullptr, *wi_app = nullptr;
     int32_t *wi_it = nullptr;
     double *wi_part = nullptr, *wi_ons = nullptr;
+    // AMP with known sections (amp_partial.hip), grow-only per (plan, B) like the integrated buffers
+    // (partial_ensure_ws): u = Az(z / phi) [B][LM]; r = Ab(beta) and z [B][n]; partial sums of z^2 [B][PART_MAX];
+    // per-section sum beta^2 and squared error [B][L]; phi [B], tau [B][Lc]; the loop's own active flags [B] (the
+    // general engine's operators want ws_active all ones) and the known indices of the host variant [B][L].
+    // beta, z / phi and the per-codeword scalars live in the batch workspace.
+    sg::DevPool wp;
+    int cap_Bp = 0;
+    void *wp_u = nullptr, *wp_r = nullptr, *wp_z = nullptr;
+    double *wp_zz = nullptr, *wp_bsq = nullptr, *wp_err = nullptr, *wp_phi = nullptr, *wp_tau = nullptr;
+    int32_t *wp_active = nullptr, *wp_known = nullptr;
 };
 
 #pragma GCC visibility push(hidden)  // shared between the library's objects, not exported from it
@@ -175,6 +186,7 @@ int build_block2(sg_amp_plan *p, const uint32_t *order0, const uint32_t *order1,
 int ensure_ws(sg_amp_plan *p, int B, int t_max);
 int ensure_io(sg_amp_plan *p, size_t bytes);
 int integ_ensure_ws(sg_amp_plan *p, int B, int nbits);
+int partial_ensure_ws(sg_amp_plan *p, int B);
 
 // ---- kernel-facing views of a plan and its workspace (T: float, double), each beside its engine's builder
 template <typename T> AmpTables<T> tables(const sg_amp_plan *p);

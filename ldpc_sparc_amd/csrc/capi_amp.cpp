@@ -58,6 +58,7 @@ struct ActivePoll {
     int B;
     hipStream_t s;
     bool pending = false;
+    const int32_t *flags = nullptr;  // the flags polled: the plan's ws_active, or a loop's own
     int request() {  // behind the launches already on the stream
         if (!p->poll_ev) SG_HIP(hipEventCreateWithFlags(&p->poll_ev, hipEventDisableTiming));
         if (p->h_active_cap < B) {
@@ -69,7 +70,8 @@ struct ActivePoll {
             SG_HIP(hipHostMalloc((void **)&p->h_active, sizeof(int32_t) * B, hipHostMallocDefault));
             p->h_active_cap = B;
         }
-        SG_HIP(hipMemcpyAsync(p->h_active, p->ws_active, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+        SG_HIP(hipMemcpyAsync(p->h_active, flags ? flags : p->ws_active, sizeof(int32_t) * B, hipMemcpyDeviceToHost,
+                              s));
         SG_HIP(hipEventRecord(p->poll_ev, s));
         pending = true;
         return SG_OK;
@@ -353,6 +355,68 @@ static int integ_dct_impl(sg_amp_plan *p, sg_graph *g, int mode, int N, int K, c
     return SG_OK;
 }
 
+// AMP with known sections (amp_partial.hip): sparc_amp with the plan's operators on natural-order vectors, as
+// integ_dct_impl runs them.  beta lives in the plan's [B][LM] workspace (ws_s of a regular plan, ws_beta of a
+// general one) and z / phi in ws_z, where apply_enqueue reads them without a copy; z, r = Ab(beta), u = Az(z / phi)
+// and the section sums in the partial buffers; the per-codeword scalars and results in the batch workspace's slots,
+// so copy_results ends the call.  Nothing but launches inside the loop; the loop's own active flags are polled
+// like a decode's.
+template <typename T>
+static int partial_impl(sg_amp_plan *p, const DecodeArgs &a, const int32_t *d_known, hipStream_t s) {
+    const int B = a.B, t_max = a.t_max;
+    SG_TRY(ensure_ws(p, B, t_max));
+    SG_TRY(partial_ensure_ws(p, B));
+    PartBufs<T> pb{};
+    pb.B = B; pb.L = p->L; pb.M = p->M; pb.LM = p->LM; pb.n = p->n; pb.Lc = p->Lc; pb.ndim = p->ndim;
+    pb.t_max = t_max; pb.np = part_count(p->n);
+    pb.y = (const T *)a.d_y;
+    pb.beta = p->regular ? (T *)p->ws_s : (T *)p->ws_beta;
+    pb.u = (T *)p->wp_u; pb.r = (T *)p->wp_r; pb.z = (T *)p->wp_z; pb.zs = (T *)p->ws_z;
+    pb.known = d_known; pb.true_idx = a.d_true;
+    pb.zz = p->wp_zz; pb.bsq = p->wp_bsq; pb.err = p->wp_err; pb.map = p->ws_argmax;
+    pb.psi = p->ws_psi; pb.psi_prev = p->ws_psi_prev; pb.gamma = p->ws_gamma; pb.bco = p->ws_bco;
+    pb.phi = p->wp_phi; pb.tau = p->wp_tau; pb.nmse = p->ws_nmse;
+    pb.active = p->wp_active; pb.t_final = p->ws_tfinal;
+    pb.W = p->dW; pb.awgn_var = a.awgn_var; pb.rtol = a.rtol;
+    pb.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
+    pb.phi_method = a.phi_method;
+    SG_HIP(hipMemsetAsync(pb.beta, 0, (size_t)B * p->LM * sizeof(T), s));
+    if (!p->regular) SG_TRY(idct_launch_ones(p->ws_active, B, p->ws_phi, B * p->Lr, s));
+    SG_TRY(part_launch_init<T>(pb, s));
+    ActivePoll poll{p, B, s, false, p->wp_active};
+    for (int t = 0; t < t_max - 1; ++t) {
+        SG_TRY(apply_enqueue<T>(p, 0, pb.beta, B, pb.r, s));  // r = Ab(beta) (t = 0: of the known one-hots)
+        SG_TRY(part_launch_residual<T>(pb, t, s));
+        SG_TRY(part_launch_control<T>(pb, 0, t, s));
+        SG_TRY(apply_enqueue<T>(p, 1, pb.zs, B, pb.u, s));  // u = Az(z / phi)
+        SG_TRY(part_launch_section<T>(pb, s));
+        SG_TRY(part_launch_control<T>(pb, 1, t, s));
+        // skip the remaining launches once every codeword stopped (ActivePoll: the flags after iterations 3, 7,
+        // 11, ..., read one iteration later)
+        int na = -1;
+        SG_TRY(poll.collect(&na));
+        if (na == 0) break;
+        if (t % 4 == 3 && t + 2 < t_max - 1) SG_TRY(poll.request());
+    }
+    if (poll.pending) SG_HIP(hipEventSynchronize(p->poll_ev));
+    return copy_results(p, a, s);
+}
+
+// Every refusal of the partial decode that needs no device (header, sg_amp_decode_partial_device)
+static int partial_checks(const sg_amp_plan *p, double awgn_var, int t_max, double rtol, int phi_method) {
+    if (p->ndim == 2)
+        return fail(SG_ERR_UNSUPPORTED, "AMP with known sections takes a flat or power-allocated design (W of ndim 0 "
+                    "or 1), not a spatially coupled one");
+    if (p->M < 2 || (p->M & (p->M - 1)) != 0 || p->M > 2048)
+        return fail(SG_ERR_UNSUPPORTED, "section size M = %d: the partial section kernel takes a power of two in "
+                    "[2, 2048]", p->M);
+    SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
+    SG_CHECK_ARG(rtol > 0 && rtol < 1, "rtol must be in (0, 1)");
+    SG_CHECK_ARG(phi_method == 1 || phi_method == 2, "phi_est_method must be 1 or 2");
+    SG_CHECK_ARG(awgn_var >= 0, "awgn_var must be >= 0");
+    return SG_OK;
+}
+
 }  // namespace sg
 
 using namespace sg;
@@ -468,6 +532,74 @@ int sg_amp_decode(sg_amp_plan *p, const double *y, int B, const int32_t *true_id
     SG_HIP(hipStreamSynchronize(s));
     handle->last_B = B;
     return SG_OK;
+}
+
+int sg_amp_decode_partial_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_known_idx,
+                                 const int32_t *d_true_idx, double awgn_var, int t_max, double rtol, int phi_method,
+                                 int32_t *d_map_idx, int32_t *d_t_final, double *d_nmse, double *d_psi, void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    reset_last(p);  // (the loop runs in the workspace that holds a decode's final state)
+    SG_TRY(sg::partial_checks(p, awgn_var, t_max, rtol, phi_method));
+    if (B <= 0) return SG_OK;
+    SG_CHECK_ARG(d_y && d_known_idx, "d_y or d_known_idx is NULL");
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = pick_stream(stream);
+    const DecodeArgs a{d_y, B, d_true_idx, awgn_var, t_max, rtol, phi_method, d_map_idx, d_t_final, d_nmse, d_psi};
+    return by_precision(p->precision, [&](auto t) { return partial_impl<decltype(t)>(p, a, d_known_idx, s); });
+}
+
+int sg_amp_decode_partial(sg_amp_plan *p, const double *y, int B, const int32_t *known_idx, const int32_t *true_idx,
+                          double awgn_var, int t_max, double rtol, int phi_method, int32_t *map_idx, int32_t *t_final,
+                          double *nmse, double *psi) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    reset_last(p);
+    SG_TRY(sg::partial_checks(p, awgn_var, t_max, rtol, phi_method));
+    if (B <= 0) return SG_OK;
+    SG_CHECK_ARG(y && known_idx && map_idx && t_final && nmse && psi, "null host buffer");
+    for (size_t i = 0; i < (size_t)B * p->L; ++i)
+        SG_CHECK_ARG(known_idx[i] >= -1 && known_idx[i] < p->M, "known_idx[%zu] = %d outside [-1, %d)", i,
+                     (int)known_idx[i], p->M);
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = lib_stream();
+    // (the workspace before the staging buffer: growing the workspace frees io too)
+    SG_TRY(ensure_ws(p, B, t_max));
+    SG_TRY(partial_ensure_ws(p, B));
+    const size_t ny = (size_t)B * p->n;
+    SG_TRY(ensure_io(p, ny * sizeof(double)));
+    SG_HIP(hipMemcpyAsync(p->io.at(), y, ny * sizeof(double), hipMemcpyHostToDevice, s));
+    SG_HIP(hipMemcpyAsync(p->wp_known, known_idx, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
+    if (true_idx) SG_HIP(hipMemcpyAsync(p->ws_true, true_idx, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
+    SG_TRY(by_precision(p->precision, [&](auto t) {
+        using T = decltype(t);
+        SG_TRY(amp_launch_cast<T>(p->io.at(), 1, (T *)p->ws_y, ny, s));
+        const DecodeArgs a{p->ws_y, B, true_idx ? p->ws_true : nullptr, awgn_var, t_max, rtol, phi_method,
+                           nullptr, nullptr, nullptr, nullptr};
+        return partial_impl<T>(p, a, p->wp_known, s);
+    }));
+    SG_HIP(hipMemcpyAsync(map_idx, p->ws_argmax, sizeof(int32_t) * B * p->L, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(t_final, p->ws_tfinal, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(nmse, p->ws_nmse, sizeof(double) * B * t_max * p->Lc, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(psi, p->ws_psi, sizeof(double) * B * p->Lc, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    return SG_OK;
+}
+
+int sg_concat_known_sections_device(int precision, const void *d_app, const int32_t *d_it, int max_it, int B, int mults,
+                                    int N, int L, int L_unprotected, int logM, int32_t *d_known_idx, void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(d_app && d_it && d_known_idx, "null device buffer");
+    SG_CHECK_ARG(L > 0 && L_unprotected >= 0 && L_unprotected <= L && logM >= 1 && logM <= 30 && N > 0 && mults >= 0,
+                 "bad lengths");
+    SG_CHECK_ARG((long long)(L - L_unprotected) * logM <= (long long)mults * N,
+                 "%d protected sections of %d bits do not fit %d blocks of %d bits", L - L_unprotected, logM, mults, N);
+    if (B <= 0) return SG_OK;
+    hipStream_t s = pick_stream(stream);
+    return precision == SG_F64 ? part_launch_known<double>((const double *)d_app, d_it, max_it, B, mults, N, L,
+                                                           L_unprotected, logM, d_known_idx, s)
+                               : part_launch_known<float>((const float *)d_app, d_it, max_it, B, mults, N, L,
+                                                          L_unprotected, logM, d_known_idx, s);
 }
 
 int sg_amp_apply(sg_amp_plan *p, int transpose, const double *in, int B, double *out) {

@@ -494,6 +494,7 @@ class ConcatTrial:
 
 def concat_checkpoint_tag(L, M, n, design="dense", K=1):
     """Checkpoint tag of a concat_ber_sweep: concat_L.. (dense), concat_dct_L.. (DCT design),
+    concat_dct3_L.. (DCT design with the final AMP pass, design "dct3"),
     concat_fft_L.._M.._K.. (complex FFT design with K-PSK; K = 1 unmodulated)."""
     if design == "fft":
         return f"concat_fft_L{L}_M{M}_K{K}_n{n}"
@@ -503,7 +504,8 @@ def concat_checkpoint_tag(L, M, n, design="dense", K=1):
 def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, block=256, blocks_per_round=None,
                      rank=0, world=1, agg=None, design_seed=0, seed=0, t_max=25, bp_its=200, precision="f32",
                      ldpc=("802.11n", "1/2", 81), min_errors=None, checkpoint_dir=None, npz_file=None, rng="device",
-                     trial=None, max_rounds=None, on_point=None, design="dense", K=1, granule=None):
+                     trial=None, max_rounds=None, on_point=None, design="dense", K=1, granule=None, final_amp=False,
+                     final_t_max=None):
     """BER / FER of concatenated SPARC + LDPC against Eb/N0 (the experiment of
     ldpc_sparc/performance_plots_general.py:100-138 for the plain concatenated
     decoder), `codewords` per point sharded over the ranks.  Eb/N0 to noise as
@@ -532,10 +534,19 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
     parameters, so a resumed real or dense sweep never reads them.  `granule`
     (ConcatTrial) fixes the size of the batches a block is drawn in, which
     makes the counters independent of `block`; it then is part of the
-    checkpointed parameters."""
+    checkpointed parameters.  `final_amp` (with design="dct" only; off by
+    default) runs the three-stage decoder AMP -> BP -> AMP with the BP-decoded
+    sections known (pipeline.DctConcat3Pipeline, its last pass up to
+    `final_t_max` - 1 iterations, default t_max); its checkpoints live under
+    concat_dct3_L.. with "design": "dct3" and final_t_max in the parameters,
+    so a two-stage sweep never resumes them."""
     from .ldpc import code
     if design not in ("dense", "dct", "fft"):
         raise ValueError(f"design must be 'dense', 'dct' or 'fft', not {design!r}")
+    if final_amp and design != "dct":
+        raise ValueError("final_amp needs the DCT design: design='dct'")
+    ftm = int(t_max if final_t_max is None else final_t_max)
+    key = "dct3" if final_amp else design  # what names the campaign in checkpoint tag and parameters
     K = int(K)
     if design != "fft" and K != 1:
         raise ValueError("K-PSK modulation needs the complex design: design='fft'")
@@ -549,10 +560,13 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
     else:
         vars_ = [P / (2 * r_overall * 10 ** (e / 10)) for e in ebn0_db]
     if trial is None:
-        from .pipeline import ConcatPipeline, CsparcConcatPipeline, DctConcatPipeline
+        from .pipeline import ConcatPipeline, CsparcConcatPipeline, DctConcat3Pipeline, DctConcatPipeline
         if design == "fft":
             pipe = CsparcConcatPipeline(L, M, K, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed,
                                         precision=precision, t_max=t_max, bp_its=bp_its)
+        elif final_amp:
+            pipe = DctConcat3Pipeline(L, M, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed,
+                                      precision=precision, t_max=t_max, bp_its=bp_its, final_t_max=ftm)
         else:
             make = DctConcatPipeline if design == "dct" else ConcatPipeline
             pipe = make(L, M, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed, precision=precision,
@@ -572,14 +586,16 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
             # ends at `codewords`, a multiple of the block, at any round size)
             params["blocks_per_round"] = bpr
         if design != "dense":  # (dense sweeps keep the parameters their checkpoints were written with)
-            params["design"] = design
+            params["design"] = key
+        if final_amp:
+            params["final_t_max"] = ftm
         if design == "fft":
             params["K"] = K
         if granule is not None:
             params["granule"] = int(granule)
         tot = run_point(trial, point, block=block, blocks_per_round=bpr, rank=rank, world=world, agg=agg,
                         min_errors=min_errors, max_units=codewords, checkpoint_dir=checkpoint_dir,
-                        tag=concat_checkpoint_tag(L, M, n, design, K), params=params, max_rounds=max_rounds)
+                        tag=concat_checkpoint_tag(L, M, n, key, K), params=params, max_rounds=max_rounds)
         out.append({"ebn0_db": float(e), "awgn_var": vars_[point], "codewords": int(tot[0]),
                     "ber": float(tot[1]) / (tot[0] * user_bits) if tot[0] else None,
                     "fer": float(tot[2]) / tot[0] if tot[0] else None,

@@ -196,6 +196,55 @@ class DctConcatPipeline(ConcatPipeline):
                                                         self.mults, c.N, c.K, self.d_cnt.ptr, None))
 
 
+class DctConcat3Pipeline(DctConcatPipeline):
+    """The three-stage decoder AMP -> BP -> AMP of the concatenated scheme on
+    the DCT design.  decode() runs DctConcatPipeline's AMP, soft output and BP,
+    then turns the BP result into known sections
+    (sg_concat_known_sections_device: the hard decisions of every protected
+    section whose LDPC blocks stopped on their syndrome) and decodes the same
+    received words again with them given (sg_amp_decode_partial_device, up to
+    `final_t_max` - 1 iterations, default t_max): the unprotected sections
+    then face the residual y - A beta_known at L_unprotected / L of the rate.
+    Errors are counted with the second pass's map_idx for the unprotected
+    sections and the same BP output for the protected bits.  Same methods,
+    device buffers and counter layout as ConcatPipeline, so
+    montecarlo.ConcatTrial takes it unchanged.  Flat and power-allocated
+    designs (a spatially coupled `op` raises ValueError)."""
+
+    def __init__(self, *args, final_t_max=None, **kw):
+        super().__init__(*args, **kw)
+        if self.op.W.ndim == 2:
+            raise ValueError("the final AMP pass takes a flat or power-allocated design, not a spatially coupled one")
+        self.final_t_max = self.t_max if final_t_max is None else int(final_t_max)
+
+    def _ensure(self, B):
+        if B <= self._cap:
+            return
+        super()._ensure(B)
+        self.d_known = _native.DeviceBuffer(B * self.L * 4)
+
+    def decode(self):
+        """One batch: returns nothing; counters accumulate in d_cnt."""
+        lib, c, B = _native.lib(), self.c, self.B
+        _native.check(lib.sg_amp_decode_device(self.plan, self.d_y.ptr, B, None, self.awgn_var, self.t_max,
+                                               self.rtol, self.phi_method, self.d_idx.ptr, None, None, None, None))
+        ld = self.mults * c.N
+        _native.check(lib.sg_amp_llr_device(self.plan, B, self.L_unp, self.L - self.L_unp, ld, 0, self.d_llr.ptr,
+                                            None))
+        _native.check(lib.sg_ldpc_decode_device(self.graph, _native.DECTYPES[self.bp_dectype], self.prec,
+                                                self.d_llr.ptr, B * self.mults, self.bp_its, 0.7, self.d_app.ptr,
+                                                self.d_it.ptr, None))
+        _native.check(lib.sg_concat_known_sections_device(self.prec, self.d_app.ptr, self.d_it.ptr, self.bp_its, B,
+                                                          self.mults, c.N, self.L, self.L_unp, self.logM,
+                                                          self.d_known.ptr, None))
+        _native.check(lib.sg_amp_decode_partial_device(self.plan, self.d_y.ptr, B, self.d_known.ptr, None,
+                                                       self.awgn_var, self.final_t_max, self.rtol, self.phi_method,
+                                                       self.d_idx.ptr, None, None, None, None))
+        _native.check(lib.sg_concat_count_errors_device(self.prec, self.d_idx.ptr, self.d_true.ptr, B, self.L,
+                                                        self.L_unp, self.logM, self.d_app.ptr, self.d_info.ptr,
+                                                        self.mults, c.N, c.K, self.d_cnt.ptr, None))
+
+
 class DctIntegratedPipeline(DctConcatPipeline):
     """The AMP <-> BP integrated decoders (sparc_new.py:257-282, :411-439, :472-502, :675-705) on the flat
     sub-sampled DCT design: `bp_its` BP iterations inside each of the t_max AMP iterations and a final

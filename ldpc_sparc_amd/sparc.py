@@ -712,6 +712,39 @@ def amp_decode_batch(Y, op, awgn_var, t_max, rtol=1e-6, phi_est_method=1, true_i
     return map_idx, t_final, nmse, psi
 
 
+def amp_decode_partial_batch(Y, op, known_idx, awgn_var, t_max, rtol=1e-6, phi_est_method=1, true_idx=None,
+                             precision=_native.SG_F64):
+    """amp_decode_batch with some sections of each codeword given: known_idx
+    [B, L] holds a section's index in [0, M), or -1 for a section to decode
+    (the set is per codeword).  A known section's estimate is the one-hot of
+    its index from the start, the residual starts at y - A beta_known, and the
+    state evolution starts at the share of unknown sections; map_idx reports
+    the known index there.  With every entry -1 this is amp_decode_batch.
+    Flat and power-allocated designs, M <= 2048.  Same returns: (map_idx
+    [B, L], t_final [B], nmse [B, t_max, Lc], psi [B, Lc])."""
+    if op.csparc:
+        raise NotImplementedError("AMP with known sections is implemented for real (DCT design) SPARCs only")
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    if Y.ndim != 2 or Y.shape[1] != op.n:
+        raise ValueError(f"received words must have shape [B, {op.n}]")
+    B = Y.shape[0]
+    known = np.ascontiguousarray(known_idx, dtype=np.int32)
+    if known.shape != (B, op.L):
+        raise ValueError(f"known_idx must have shape [{B}, {op.L}]")
+    ti = None
+    if true_idx is not None:
+        ti = np.ascontiguousarray(true_idx, dtype=np.int32).reshape(B, op.L)
+    map_idx = np.empty((B, op.L), dtype=np.int32)
+    t_final = np.empty(B, dtype=np.int32)
+    nmse = np.empty((B, t_max, op.Lc))
+    psi = np.empty((B, op.Lc))
+    _native.check(_native.lib().sg_amp_decode_partial(
+        op.plan(precision), _native.ptr(Y), B, _native.ptr(known), _native.ptr(ti), float(awgn_var), int(t_max),
+        float(rtol), int(phi_est_method), _native.ptr(map_idx), _native.ptr(t_final), _native.ptr(nmse),
+        _native.ptr(psi)))
+    return map_idx, t_final, nmse, psi
+
+
 def amp_llr(op, B, l0, nl, probs_only=False, precision=_native.SG_F64):
     """Soft output of the last amp_decode_batch of B codewords through `op` at
     this precision: for sections [l0, l0 + nl), the LLRs log p - log(1 - p) of
