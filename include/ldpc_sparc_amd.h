@@ -148,7 +148,10 @@ int sg_concat_count_errors_device(int precision, const int32_t *d_map_idx, const
  * app < 0 of its logM bits (bit i of section l is bit (l - L_unprotected) logM + i of the codeword's mults*N
  * protected bits), provided every LDPC block that holds one of those bits stopped on its syndrome
  * (it < max_it) -- a section straddles two blocks when logM does not divide N -- and -1 otherwise.  Needs no
- * graph handle.  SG_ERR_INVALID when the protected sections do not fit the blocks. */
+ * graph handle.  SG_ERR_INVALID when the protected sections do not fit the blocks.  For a K-PSK codeword call it
+ * with logM = log2 M + log2 K: it then yields the known section words in the layout sg_psk_pack_sections_device
+ * writes (sg_psk_unpack_sections_device turns them into the known_idx / known_sym of
+ * sg_camp_decode_partial_device). */
 int sg_concat_known_sections_device(int precision, const void *d_app, const int32_t *d_it, int max_it, int B,
                                     int mults, int N, int L, int L_unprotected, int logM, int32_t *d_known_idx,
                                     void *stream);
@@ -626,6 +629,56 @@ int sg_bits_to_psk_sections_strided_device(const uint8_t *d_bits, size_t bit_str
  * with logM + logK in the place of logM. */
 int sg_psk_pack_sections_device(const int32_t *d_idx, const int32_t *d_sym, int B, int L, int logK,
                                 int32_t *d_word, void *stream);
+/* Its inverse: a word < 0 gives d_idx = -1 and d_sym = 0 (the "unknown" of
+ * sg_concat_known_sections_device), any other d_idx = word >> logK and
+ * d_sym = gray2bin(word & (K - 1)).  logK = 0: d_sym may be NULL, and is
+ * written as zero otherwise. */
+int sg_psk_unpack_sections_device(const int32_t *d_word, int B, int L, int logK, int32_t *d_idx, int32_t *d_sym,
+                                  void *stream);
+
+/* Complex AMP with known sections: sg_camp_decode_device with some sections of
+ * each codeword given (the final pass of the three-stage concatenated K-PSK
+ * decoder AMP -> BP -> AMP).  d_known_idx [B][L] holds a section's location in
+ * [0, M), or -1 for a section to decode; d_known_sym [B][L] its constellation
+ * index in [0, K) (may be NULL for K = 1); the set is per codeword.  A known
+ * section's estimate is the one-hot c[sym] at idx throughout: it adds 1 to sum
+ * |beta|^2 (0 to psi), and 0 to the NMSE where (idx, sym) agrees with
+ * d_true_idx / d_true_sym.  The start is beta0 = the known one-hots,
+ * z0 = y - Ab(beta0), psi0_c = the share of unknown sections of column block
+ * c, gamma0 formed from psi0 as the loop forms gamma from psi (W psi for ndim
+ * 0, dot(W, psi) / Lc otherwise), and iteration 0 has no Onsager term.
+ * Everything else -- phi by either phi_method, tau, s = beta + tau Az(z / phi),
+ * the K-PSK MMSE estimate of an unknown section, the psi stopping rule, the
+ * final MAP of s -- is sg_camp_decode_device's, for W of ndim 0, 1 and 2 and
+ * any M it takes; d_map_idx / d_map_sym report the known (idx, sym) of a known
+ * section.  With every entry -1 this is sg_camp_decode_device's arithmetic.
+ * Outputs as there (any may be NULL).
+ *   Every check precedes any launch or allocation and is
+ * sg_camp_decode_device's: SG_ERR_INVALID for bad t_max, rtol, phi_method,
+ * awgn_var, K, B > 65535, a NULL d_known_idx, or K > 1 with a NULL
+ * d_known_sym; SG_ERR_UNSUPPORTED for K > 64; B <= 0 returns SG_OK with
+ * nothing done.  The device variant treats a location outside [0, M) as
+ * unknown and reduces d_known_sym modulo K.
+ *   Works in the plan's workspace: clears the last-decode state (a following
+ * sg_camp_llr* answers SG_ERR_BAD_ARG; the soft-output buffer is not written)
+ * and leaves the plan fit for sg_camp_decode*.  The loop enqueues on the
+ * stream and polls the active flags as sg_camp_decode_device does.  A
+ * codeword's results do not depend on the batch it is decoded in. */
+int sg_camp_decode_partial_device(sg_camp_plan *p, const void *d_y, int B, int K, const double *constel,
+                                  const int32_t *d_known_idx, const int32_t *d_known_sym,
+                                  const int32_t *d_true_idx, const int32_t *d_true_sym, double awgn_var,
+                                  int t_max, double rtol, int phi_method, int32_t *d_map_idx,
+                                  int32_t *d_map_sym, int32_t *d_t_final, double *d_nmse, double *d_psi,
+                                  void *stream);
+/* Host variant: arrays as sg_camp_decode plus known_idx / known_sym [B][L];
+ * blocking.  It scans them: a known_idx outside [-1, M), or a known_sym outside
+ * [0, K) on a known section, is SG_ERR_INVALID before anything is launched.
+ * The device copies of the known arrays are allocated once per (plan, B) and
+ * freed with the plan. */
+int sg_camp_decode_partial(sg_camp_plan *p, const double *y, int B, int K, const double *constel,
+                           const int32_t *known_idx, const int32_t *known_sym, const int32_t *true_idx,
+                           const int32_t *true_sym, double awgn_var, int t_max, double rtol, int phi_method,
+                           int32_t *map_idx, int32_t *map_sym, int32_t *t_final, double *nmse, double *psi);
 
 #ifdef __cplusplus
 }

@@ -126,6 +126,12 @@ SIGNATURES = [
     ("sg_bits_to_psk_sections_strided_device", ct.c_int,
      [vp, ct.c_size_t, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp, vp, ct.c_size_t, vp]),
     ("sg_psk_pack_sections_device", ct.c_int, [vp, vp, ct.c_int, ct.c_int, ct.c_int, vp, vp]),
+    # complex AMP with known sections (three-stage concatenated K-PSK decoder)
+    ("sg_psk_unpack_sections_device", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, vp, vp, vp]),
+    ("sg_camp_decode_partial", ct.c_int, [vp, vp, ct.c_int, ct.c_int, vp, vp, vp, vp, vp, ct.c_double, ct.c_int,
+                                          ct.c_double, ct.c_int, vp, vp, vp, vp, vp]),
+    ("sg_camp_decode_partial_device", ct.c_int, [vp, vp, ct.c_int, ct.c_int, vp, vp, vp, vp, vp, ct.c_double,
+                                                 ct.c_int, ct.c_double, ct.c_int, vp, vp, vp, vp, vp, vp]),
     ("Lxfb", ct.c_double, [dp, ct.c_long, ct.c_int]),
     ("sg_device_synchronize", ct.c_int, []),
     ("sg_profile_enable", ct.c_int, [ct.c_int]),

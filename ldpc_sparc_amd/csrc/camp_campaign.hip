@@ -10,16 +10,10 @@
 //       the transmitted (location, constellation index) pairs.
 #include <algorithm>
 
-#include "amp_cfft.hpp"
+#include "camp_section.hpp"
 
 namespace sg {
 namespace {
-
-__device__ __forceinline__ int gray_to_bin(int g) {  // sparc.py:214-223
-    for (int m = g >> 1; m; m >>= 1) g ^= m;
-    return g;
-}
-__device__ __forceinline__ int bin_to_gray(int b) { return b ^ (b >> 1); }  // sparc.py:206-211
 
 __global__ __launch_bounds__(256) void bits_to_psk_sections_kernel(const uint8_t *__restrict__ bits, int L, int logM,
                                                                    int logK, int32_t *__restrict__ idx,

@@ -13,7 +13,7 @@
 // (sparc_new.py:1167-1169).
 #include <algorithm>
 
-#include "amp_cfft.hpp"
+#include "camp_section.hpp"
 
 namespace sg {
 namespace {
@@ -21,10 +21,8 @@ namespace {
 constexpr int LLR_HI = 5;   // location bits above the six lane bits (M <= 2048)
 constexpr int LLR_SYM = 6;  // symbol bits (K <= 64)
 
-__device__ __forceinline__ int bin_to_gray(int b) { return b ^ (b >> 1); }  // sparc.py:206-211
-
 // exponent argument of (entry x, symbol k): Re x for K = 1, else Re(x conj c_k).  The host's constellation is
-// exact for K = 2 and K = 4, so this one form equals the specialised ones of psk_terms (amp_cfft.hip).
+// exact for K = 2 and K = 4, so this one form equals the specialised ones of psk_terms (camp_section.hpp).
 __device__ __forceinline__ double llr_arg(int K, const cxd *__restrict__ c, cxd x, int k) {
     return K == 1 ? x.x : x.x * c[k].x + x.y * c[k].y;
 }
@@ -100,10 +98,6 @@ __global__ __launch_bounds__(256) void camp_llr_kernel(const cxd *__restrict__ s
 
 // bits_to_psk_sections_kernel (camp_campaign.hip) with row strides: codeword b's bits at bits + b * bit_stride,
 // its L locations / constellation indices at idx / sym + b * idx_stride
-__device__ __forceinline__ int gray_to_bin(int g) {  // sparc.py:214-223
-    for (int m = g >> 1; m; m >>= 1) g ^= m;
-    return g;
-}
 __global__ __launch_bounds__(256) void bits_to_psk_strided_kernel(const uint8_t *__restrict__ bits, size_t bit_stride,
                                                                   int L, int logM, int logK, int32_t *__restrict__ idx,
                                                                   int32_t *__restrict__ sym, size_t idx_stride) {

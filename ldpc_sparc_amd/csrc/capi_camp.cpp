@@ -34,6 +34,10 @@ struct sg_camp_plan {
     bool soft = false;
     cxd *s_keep = nullptr;
     int last_B = 0, last_K = 0;
+    // known sections of sg_camp_decode_partial's host arrays [B][L], grow-only per (plan, B) (ensure_known)
+    DevPool part;
+    int part_B = 0;
+    int32_t *known_idx = nullptr, *known_sym = nullptr;
 };
 
 namespace {
@@ -96,6 +100,16 @@ int ensure_ws(sg_camp_plan *p, int B, int t_max) {
     return SG_OK;
 }
 
+int ensure_known(sg_camp_plan *p, int B) {
+    if (B <= p->part_B) return SG_OK;
+    p->part.release();
+    p->part_B = 0;
+    SG_TRY(p->part.alloc(&p->known_idx, sizeof(int32_t) * B * p->L));
+    SG_TRY(p->part.alloc(&p->known_sym, sizeof(int32_t) * B * p->L));
+    p->part_B = B;
+    return SG_OK;
+}
+
 CampTables tables(const sg_camp_plan *p) {
     CampTables tb;
     tb.nT = p->nT; tb.w = p->w; tb.P = p->P; tb.Q = p->Q; tb.log2P = p->log2P; tb.log2Q = p->log2Q;
@@ -134,6 +148,19 @@ int set_constel(sg_camp_plan *p, int K, const double *constel, hipStream_t s) {
     SG_HIP(hipStreamSynchronize(s));  // an earlier upload may still read h_constel
     p->h_constel.assign(c, c + K);
     SG_HIP(hipMemcpyAsync(p->constel, p->h_constel.data(), (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
+    return SG_OK;
+}
+
+// Every refusal of the partial decode that its two variants share: sg_camp_decode_device's, before any launch
+int partial_checks(int B, int K, const double *constel, double awgn_var, int t_max, double rtol, int phi_method) {
+    SG_CHECK_ARG(B <= CAMP_MAX_B, "batch must be at most 65535");
+    SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
+    SG_CHECK_ARG(rtol > 0 && rtol < 1, "rtol must be in (0, 1)");
+    SG_CHECK_ARG(phi_method == 1 || phi_method == 2, "phi_est_method must be 1 or 2");
+    SG_CHECK_ARG(awgn_var >= 0, "awgn_var must be >= 0");
+    SG_CHECK_ARG(psk_order_ok(K), "K must be 1 or a power of two");
+    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    SG_CHECK_ARG(K == 1 || constel, "K > 1 needs the constellation");
     return SG_OK;
 }
 
@@ -590,6 +617,122 @@ int sg_psk_pack_sections_device(const int32_t *d_idx, const int32_t *d_sym, int 
     SG_CHECK_ARG(logK >= 0 && logK <= 30, "bad logK");
     SG_CHECK_ARG(logK == 0 || d_sym, "logK > 0 needs d_sym");
     return camp_launch_pack(d_idx, logK ? d_sym : nullptr, B, L, logK, d_word, pick_stream(stream));
+}
+
+// sg_camp_decode_device's loop with the known sections given (camp_partial.hip): iteration 0 runs the forward
+// transform of beta0 too, and has its own residual kernel.
+int sg_camp_decode_partial_device(sg_camp_plan *p, const void *d_y, int B, int K, const double *constel,
+                                  const int32_t *d_known_idx, const int32_t *d_known_sym, const int32_t *d_true_idx,
+                                  const int32_t *d_true_sym, double awgn_var, int t_max, double rtol, int phi_method,
+                                  int32_t *d_map_idx, int32_t *d_map_sym, int32_t *d_t_final, double *d_nmse,
+                                  double *d_psi, void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    p->last_B = p->last_K = 0;  // the loop overwrites the state a decode left; s_keep is not refilled
+    SG_TRY(partial_checks(B, K, constel, awgn_var, t_max, rtol, phi_method));
+    if (B <= 0) return SG_OK;
+    SG_CHECK_ARG(d_y && d_known_idx, "d_y or d_known_idx is NULL");
+    SG_CHECK_ARG(K == 1 || d_known_sym, "K > 1 needs d_known_sym");
+    SG_CHECK_ARG(K == 1 || !d_true_idx || d_true_sym, "K > 1 with true_idx needs true_sym");
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = pick_stream(stream);
+    SG_TRY(ensure_ws(p, B, t_max));
+    SG_TRY(set_constel(p, K, constel, s));
+    const CampTables tb = tables(p);
+    CampBufs bf = bufs(p, B, K);
+    bf.y = (const cxd *)d_y;
+    bf.sec_idx = d_map_idx ? d_map_idx : p->sec_idx;
+    bf.sec_sym = d_map_sym ? d_map_sym : p->sec_sym;
+    bf.true_idx = d_true_idx;
+    bf.true_sym = (K > 1 && d_true_idx) ? d_true_sym : nullptr;
+    const int32_t *ksym = K > 1 ? d_known_sym : nullptr;
+    AmpScalars sc;
+    sc.psi = d_psi ? d_psi : p->psi; sc.psi_prev = p->psi_prev; sc.phi_prev = p->phi_prev; sc.gamma = p->gamma;
+    sc.bcoef = p->bco;
+    sc.nmse = d_nmse ? d_nmse : p->nmse; sc.t_final = d_t_final ? d_t_final : p->t_final;
+    AmpParams pr;
+    pr.W = p->dW; pr.awgn_var = awgn_var; pr.rtol = rtol;
+    pr.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
+    pr.phi_method = phi_method; pr.t_max = t_max;
+    SG_HIP(hipMemsetAsync(p->beta, 0, (size_t)B * p->LM * sizeof(cxd), s));
+    SG_HIP(hipMemsetAsync(bf.sec_idx, 0, sizeof(int32_t) * B * p->L, s));
+    SG_HIP(hipMemsetAsync(bf.sec_sym, 0, sizeof(int32_t) * B * p->L, s));
+    SG_TRY(camp_part_launch_init(tb, bf, sc, pr, d_known_idx, ksym, s));
+    std::vector<int32_t> act(B);
+    for (int t = 0; t < t_max - 1; ++t) {
+        SG_TRY(camp_launch_fft(tb, bf, false, s));
+        if (t == 0) SG_TRY(camp_part_launch_start(tb, bf, sc, pr, s));
+        else SG_TRY(camp_launch_control(tb, bf, sc, pr, 0, t, s));
+        SG_TRY(camp_launch_fft(tb, bf, true, s));
+        SG_TRY(camp_part_launch_eta(tb, bf, d_known_idx, ksym, s));
+        SG_TRY(camp_launch_control(tb, bf, sc, pr, 1, t, s));
+        if (t % 4 == 3 && t + 1 < t_max - 1) {  // skip the remaining launches once every codeword stopped
+            SG_HIP(hipMemcpyAsync(act.data(), p->active, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+            SG_HIP(hipStreamSynchronize(s));
+            int na = 0;
+            for (int b = 0; b < B; ++b) na += act[b] != 0;
+            if (na == 0) break;
+        }
+    }
+    return SG_OK;
+}
+
+// upload -> sg_camp_decode_partial_device on the plan's own buffers -> download
+int sg_camp_decode_partial(sg_camp_plan *p, const double *y, int B, int K, const double *constel,
+                           const int32_t *known_idx, const int32_t *known_sym, const int32_t *true_idx,
+                           const int32_t *true_sym, double awgn_var, int t_max, double rtol, int phi_method,
+                           int32_t *map_idx, int32_t *map_sym, int32_t *t_final, double *nmse, double *psi) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    p->last_B = p->last_K = 0;
+    SG_TRY(partial_checks(B, K, constel, awgn_var, t_max, rtol, phi_method));
+    if (B <= 0) return SG_OK;
+    SG_CHECK_ARG(y && known_idx && map_idx && t_final && nmse && psi, "null host buffer");
+    SG_CHECK_ARG(K == 1 || (known_sym && map_sym), "K > 1 needs known_sym and map_sym");
+    SG_CHECK_ARG(K == 1 || !true_idx || true_sym, "K > 1 with true_idx needs true_sym");
+    const size_t nsec = (size_t)B * p->L;
+    for (size_t i = 0; i < nsec; ++i) {
+        SG_CHECK_ARG(known_idx[i] >= -1 && known_idx[i] < p->M, "known_idx[%zu] = %d outside [-1, %d)", i,
+                     (int)known_idx[i], p->M);
+        SG_CHECK_ARG(K == 1 || known_idx[i] < 0 || (known_sym[i] >= 0 && known_sym[i] < K),
+                     "known_sym[%zu] = %d outside [0, %d)", i, K > 1 ? (int)known_sym[i] : 0, K);
+        if (true_idx) {
+            SG_CHECK_ARG(true_idx[i] >= 0 && true_idx[i] < p->M, "true_idx out of range");
+            SG_CHECK_ARG(K == 1 || (true_sym[i] >= 0 && true_sym[i] < K), "true_sym out of range");
+        }
+    }
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = lib_stream();
+    SG_TRY(ensure_ws(p, B, t_max));
+    SG_TRY(ensure_known(p, B));
+    SG_HIP(hipMemcpyAsync(p->y, y, (size_t)B * p->n * sizeof(cxd), hipMemcpyHostToDevice, s));
+    SG_HIP(hipMemcpyAsync(p->known_idx, known_idx, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
+    if (K > 1) SG_HIP(hipMemcpyAsync(p->known_sym, known_sym, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
+    if (true_idx) {
+        SG_HIP(hipMemcpyAsync(p->true_idx, true_idx, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
+        if (K > 1) SG_HIP(hipMemcpyAsync(p->true_sym, true_sym, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
+    }
+    SG_TRY(sg_camp_decode_partial_device(p, p->y, B, K, constel, p->known_idx, p->known_sym,
+                                         true_idx ? p->true_idx : nullptr, (true_idx && K > 1) ? p->true_sym : nullptr,
+                                         awgn_var, t_max, rtol, phi_method, p->sec_idx, p->sec_sym, p->t_final, p->nmse,
+                                         p->psi, nullptr));
+    SG_HIP(hipMemcpyAsync(map_idx, p->sec_idx, sizeof(int32_t) * nsec, hipMemcpyDeviceToHost, s));
+    if (map_sym) SG_HIP(hipMemcpyAsync(map_sym, p->sec_sym, sizeof(int32_t) * nsec, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(t_final, p->t_final, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(nmse, p->nmse, sizeof(double) * B * t_max * p->Lc, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(psi, p->psi, sizeof(double) * B * p->Lc, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    return SG_OK;
+}
+
+int sg_psk_unpack_sections_device(const int32_t *d_word, int B, int L, int logK, int32_t *d_idx, int32_t *d_sym,
+                                  void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(d_word && d_idx, "null device buffer");
+    SG_CHECK_ARG(B >= 0 && L >= 0, "bad (B, L)");
+    SG_CHECK_ARG(logK >= 0 && logK <= 30, "bad logK");
+    SG_CHECK_ARG(logK == 0 || d_sym, "logK > 0 needs d_sym");
+    return camp_launch_unpack(d_word, B, L, logK, d_idx, d_sym, pick_stream(stream));
 }
 
 }  // extern "C"

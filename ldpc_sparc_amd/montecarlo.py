@@ -495,9 +495,10 @@ class ConcatTrial:
 def concat_checkpoint_tag(L, M, n, design="dense", K=1):
     """Checkpoint tag of a concat_ber_sweep: concat_L.. (dense), concat_dct_L.. (DCT design),
     concat_dct3_L.. (DCT design with the final AMP pass, design "dct3"),
-    concat_fft_L.._M.._K.. (complex FFT design with K-PSK; K = 1 unmodulated)."""
-    if design == "fft":
-        return f"concat_fft_L{L}_M{M}_K{K}_n{n}"
+    concat_fft_L.._M.._K.. (complex FFT design with K-PSK; K = 1 unmodulated),
+    concat_fft3_L.._M.._K.. (the same with the final AMP pass, design "fft3")."""
+    if design in ("fft", "fft3"):
+        return f"concat_{design}_L{L}_M{M}_K{K}_n{n}"
     return f"concat_L{L}_M{M}_n{n}" if design == "dense" else f"concat_{design}_L{L}_M{M}_n{n}"
 
 
@@ -534,19 +535,20 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
     parameters, so a resumed real or dense sweep never reads them.  `granule`
     (ConcatTrial) fixes the size of the batches a block is drawn in, which
     makes the counters independent of `block`; it then is part of the
-    checkpointed parameters.  `final_amp` (with design="dct" only; off by
+    checkpointed parameters.  `final_amp` (with design="dct" or "fft"; off by
     default) runs the three-stage decoder AMP -> BP -> AMP with the BP-decoded
-    sections known (pipeline.DctConcat3Pipeline, its last pass up to
-    `final_t_max` - 1 iterations, default t_max); its checkpoints live under
-    concat_dct3_L.. with "design": "dct3" and final_t_max in the parameters,
-    so a two-stage sweep never resumes them."""
+    sections known (pipeline.DctConcat3Pipeline or CsparcConcat3Pipeline, its
+    last pass up to `final_t_max` - 1 iterations, default t_max); its
+    checkpoints live under concat_dct3_L.. / concat_fft3_L.._M.._K.. with
+    "design": "dct3" / "fft3" and final_t_max in the parameters, so a two-stage
+    sweep never resumes them."""
     from .ldpc import code
     if design not in ("dense", "dct", "fft"):
         raise ValueError(f"design must be 'dense', 'dct' or 'fft', not {design!r}")
-    if final_amp and design != "dct":
-        raise ValueError("final_amp needs the DCT design: design='dct'")
+    if final_amp and design == "dense":
+        raise ValueError("final_amp needs the DCT or FFT design: design='dct' or 'fft'")
     ftm = int(t_max if final_t_max is None else final_t_max)
-    key = "dct3" if final_amp else design  # what names the campaign in checkpoint tag and parameters
+    key = design + "3" if final_amp else design  # what names the campaign in checkpoint tag and parameters
     K = int(K)
     if design != "fft" and K != 1:
         raise ValueError("K-PSK modulation needs the complex design: design='fft'")
@@ -560,8 +562,12 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
     else:
         vars_ = [P / (2 * r_overall * 10 ** (e / 10)) for e in ebn0_db]
     if trial is None:
-        from .pipeline import ConcatPipeline, CsparcConcatPipeline, DctConcat3Pipeline, DctConcatPipeline
-        if design == "fft":
+        from .pipeline import (ConcatPipeline, CsparcConcat3Pipeline, CsparcConcatPipeline, DctConcat3Pipeline,
+                               DctConcatPipeline)
+        if design == "fft" and final_amp:
+            pipe = CsparcConcat3Pipeline(L, M, K, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed,
+                                         precision=precision, t_max=t_max, bp_its=bp_its, final_t_max=ftm)
+        elif design == "fft":
             pipe = CsparcConcatPipeline(L, M, K, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed,
                                         precision=precision, t_max=t_max, bp_its=bp_its)
         elif final_amp:

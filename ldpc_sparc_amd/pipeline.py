@@ -420,8 +420,8 @@ class CsparcConcatPipeline(ConcatPipeline):
                                          float(np.sqrt(awgn_var / 2)), self.d_y.ptr, None))
         self.B, self.awgn_var = B, float(awgn_var)
 
-    def decode(self):
-        """One batch: returns nothing; counters accumulate in d_cnt."""
+    def _decode_to_bp(self):
+        """AMP, section words, soft output and BP of one batch: d_idx, d_app and d_it."""
         lib, c, B = _native.lib(), self.c, self.B
         cs = _native.ptr(self.constel)
         _native.check(lib.sg_camp_decode_device(self.plan, self.d_y.ptr, B, self.K, cs, None, None, self.awgn_var,
@@ -435,6 +435,61 @@ class CsparcConcatPipeline(ConcatPipeline):
         _native.check(lib.sg_ldpc_decode_device(self.graph, _native.DECTYPES[self.bp_dectype], self.prec,
                                                 self.d_llr.ptr, B * self.mults, self.bp_its, 0.7, self.d_app.ptr,
                                                 self.d_it.ptr, None))
-        _native.check(lib.sg_concat_count_errors_device(self.prec, self.d_idx.ptr, self.d_true.ptr, B, self.L,
-                                                        self.L_unp, self.bits_per_section, self.d_app.ptr,
-                                                        self.d_info.ptr, self.mults, c.N, c.K, self.d_cnt.ptr, None))
+
+    def _count(self):
+        """d_cnt += the errors of the section words in d_idx and of the BP output in d_app."""
+        c = self.c
+        _native.check(_native.lib().sg_concat_count_errors_device(
+            self.prec, self.d_idx.ptr, self.d_true.ptr, self.B, self.L, self.L_unp, self.bits_per_section,
+            self.d_app.ptr, self.d_info.ptr, self.mults, c.N, c.K, self.d_cnt.ptr, None))
+
+    def decode(self):
+        """One batch: returns nothing; counters accumulate in d_cnt."""
+        self._decode_to_bp()
+        self._count()
+
+
+class CsparcConcat3Pipeline(CsparcConcatPipeline):
+    """The three-stage decoder AMP -> BP -> AMP of the concatenated scheme on
+    the complex K-PSK design.  decode() runs CsparcConcatPipeline's AMP, soft
+    output and BP, then turns the BP result into known section words
+    (sg_concat_known_sections_device with bits_per_section: the hard decisions
+    of every protected section whose LDPC blocks stopped on their syndrome),
+    the words into (location, symbol) pairs (sg_psk_unpack_sections_device),
+    and decodes the same received words again with them given
+    (sg_camp_decode_partial_device, up to `final_t_max` - 1 iterations, default
+    t_max): the unprotected sections then face the residual y - A beta_known
+    at L_unprotected / L of the rate.  Errors are counted with the final pass's
+    section words for the unprotected sections and the same BP output for the
+    protected bits.  Flat, power-allocated and spatially coupled designs.  Same
+    methods, device buffers and counter layout as ConcatPipeline, so
+    montecarlo.ConcatTrial takes it unchanged."""
+
+    def __init__(self, *args, final_t_max=None, **kw):
+        super().__init__(*args, **kw)
+        self.final_t_max = self.t_max if final_t_max is None else int(final_t_max)
+
+    def _ensure(self, B):
+        if B <= self._cap:
+            return
+        super()._ensure(B)
+        self.d_known = _native.DeviceBuffer(B * self.L * 4)  # known section words; their (location, symbol)
+        self.d_kidx = _native.DeviceBuffer(B * self.L * 4)
+        self.d_ksym = _native.DeviceBuffer(B * self.L * 4)
+
+    def decode(self):
+        """One batch: returns nothing; counters accumulate in d_cnt."""
+        lib, c, B = _native.lib(), self.c, self.B
+        self._decode_to_bp()
+        _native.check(lib.sg_concat_known_sections_device(self.prec, self.d_app.ptr, self.d_it.ptr, self.bp_its, B,
+                                                          self.mults, c.N, self.L, self.L_unp, self.bits_per_section,
+                                                          self.d_known.ptr, None))
+        _native.check(lib.sg_psk_unpack_sections_device(self.d_known.ptr, B, self.L, self.logK, self.d_kidx.ptr,
+                                                        self.d_ksym.ptr, None))
+        _native.check(lib.sg_camp_decode_partial_device(self.plan, self.d_y.ptr, B, self.K, _native.ptr(self.constel),
+                                                        self.d_kidx.ptr, self.d_ksym.ptr, None, None, self.awgn_var,
+                                                        self.final_t_max, self.rtol, self.phi_method, self.d_midx.ptr,
+                                                        self.d_msym.ptr, None, None, None, None))
+        _native.check(lib.sg_psk_pack_sections_device(self.d_midx.ptr, self.d_msym.ptr, B, self.L, self.logK,
+                                                      self.d_idx.ptr, None))
+        self._count()

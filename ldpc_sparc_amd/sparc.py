@@ -791,6 +791,52 @@ def camp_decode_batch(Y, op, awgn_var, t_max, rtol=1e-6, phi_est_method=1, K=1, 
     return map_idx, map_sym, t_final, nmse, psi
 
 
+def camp_decode_partial_batch(Y, op, known_idx, known_sym, awgn_var, t_max, rtol=1e-6, phi_est_method=1, K=1,
+                              true_idx=None, true_sym=None):
+    """camp_decode_batch with some sections of each codeword given: known_idx
+    [B, L] holds a section's location in [0, M), or -1 for a section to decode,
+    and known_sym [B, L] its constellation index in [0, K) (ignored, and may be
+    None, for K = 1); the set is per codeword.  A known section's estimate is
+    the one-hot c[sym] at idx from the start, the residual starts at
+    y - A beta_known, and the state evolution starts at the share of unknown
+    sections; map_idx / map_sym report the known pair there.  With every entry
+    -1 this is camp_decode_batch.  Flat, power-allocated and spatially coupled
+    designs.  Same returns: (map_idx [B, L], map_sym [B, L], t_final [B], nmse
+    [B, t_max, Lc], psi [B, Lc])."""
+    if not op.csparc:
+        raise ValueError("camp_decode_partial_batch needs a ComplexDesignOperator (real designs: "
+                         "amp_decode_partial_batch)")
+    _check_psk(K)
+    Y = np.ascontiguousarray(Y, dtype=np.complex128)
+    if Y.ndim != 2 or Y.shape[1] != op.n:
+        raise ValueError(f"received words must have shape [B, {op.n}]")
+    B = Y.shape[0]
+    ki = np.ascontiguousarray(known_idx, dtype=np.int32)
+    if ki.shape != (B, op.L):
+        raise ValueError(f"known_idx must have shape [{B}, {op.L}]")
+    ks = None
+    if K != 1:
+        ks = np.ascontiguousarray(known_sym, dtype=np.int32)
+        if ks.shape != (B, op.L):
+            raise ValueError(f"known_sym must have shape [{B}, {op.L}]")
+    ti = ts = None
+    if true_idx is not None:
+        ti = np.ascontiguousarray(true_idx, dtype=np.int32).reshape(B, op.L)
+        if K != 1:
+            ts = np.ascontiguousarray(true_sym, dtype=np.int32).reshape(B, op.L)
+    map_idx = np.empty((B, op.L), dtype=np.int32)
+    map_sym = np.zeros((B, op.L), dtype=np.int32)
+    t_final = np.empty(B, dtype=np.int32)
+    nmse = np.empty((B, t_max, op.Lc))
+    psi = np.empty((B, op.Lc))
+    c = _interleaved(psk_constel(K)) if K != 1 else None
+    _native.check(_native.lib().sg_camp_decode_partial(
+        op.plan(), _native.ptr(Y), B, int(K), _native.ptr(c), _native.ptr(ki), _native.ptr(ks), _native.ptr(ti),
+        _native.ptr(ts), float(awgn_var), int(t_max), float(rtol), int(phi_est_method), _native.ptr(map_idx),
+        _native.ptr(map_sym), _native.ptr(t_final), _native.ptr(nmse), _native.ptr(psi)))
+    return map_idx, map_sym, t_final, nmse, psi
+
+
 def camp_llr(op, B, K, l0, nl, probs_only=False):
     """Soft output of the last camp_decode_batch of B codewords at PSK order K
     through the complex operator `op`, decoded after op.soft_output(): for
