@@ -377,6 +377,13 @@ int sg_amp_plan_engine(const sg_amp_plan *p, int B);
  * engine left to the staged engine (-1: no hand-over), *on_companion 1 when
  * the decode ran on the P = 16384 companion plan (may be NULL). */
 int sg_amp_last_decode(const sg_amp_plan *p, int *engine, int *handover_iter, int *on_companion);
+/* The CU count the engine choice of this plan's decodes assumes instead of the device's (0: the device's): with
+ * cus = 1 every batch runs the per-codeword engines, and the f32 split engine pipelines every batch of two or
+ * more codewords.  For tests of the full-batch paths at small B. */
+int sg_amp_plan_set_cus(sg_amp_plan *p, int cus);
+/* *pipelined 1 when the last decode through this plan ran split-engine iterations as two half-batches on two
+ * streams (B >= the CU count and at least 2; SG_AMP_PIPE=0 keeps one stream). */
+int sg_amp_last_pipelined(const sg_amp_plan *p, int *pipelined);
 
 /* Batched AMP decode (sparc.py:883-999, one call per codeword in the
  * reference): y[B][n] received words sharing the plan's design; true_idx

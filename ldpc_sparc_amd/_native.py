@@ -84,6 +84,8 @@ SIGNATURES = [
     ("sg_amp_plan_info", ct.c_int, [vp] + [ct.POINTER(ct.c_int)] * 6),
     ("sg_amp_plan_engine", ct.c_int, [vp, ct.c_int]),
     ("sg_amp_last_decode", ct.c_int, [vp, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), ct.POINTER(ct.c_int)]),
+    ("sg_amp_plan_set_cus", ct.c_int, [vp, ct.c_int]),
+    ("sg_amp_last_pipelined", ct.c_int, [vp, ct.POINTER(ct.c_int)]),
     ("sg_amp_decode", ct.c_int, [vp, vp, ct.c_int, vp, ct.c_double, ct.c_int, ct.c_double, ct.c_int,
                                  vp, vp, vp, vp]),
     ("sg_amp_decode_device", ct.c_int, [vp, vp, ct.c_int, vp, ct.c_double, ct.c_int, ct.c_double,

@@ -255,8 +255,9 @@ struct Cw2Tables {
     float4 *part;             // [B][2][Lblk] partial section statistics (max, R1, R2, s of the true entry or NaN)
     uint64_t *tprof;          // diagnostics (SG_AMP_TPROF): [2 B][64] shader-clock stamps (Ab 0-31, Az 32-63), or null
 };
+// (after_ctrl: an event to record behind the control kernel, or null)
 int cw2_launch_iter(const Cw2Tables &tb, const RegBufs<float> &bf, const AmpScalars &sc, const AmpParams &pr, int t,
-                    hipStream_t s);
+                    hipStream_t s, hipEvent_t after_ctrl = nullptr);
 // z in natural order from the split engine's slot-order copy (before a hand-over to the staged engine)
 int cw2_launch_z_natural(const Cw2Tables &tb, const RegBufs<float> &bf, hipStream_t s);
 // The same engine in double precision (amp_cw2d.hip): the split engine's slot and class tables, double

@@ -944,7 +944,7 @@ int cw2_launch_z_natural(const Cw2Tables &tb, const RegBufs<float> &bf, hipStrea
 
 template <int OT>
 static int cw2_launch(const Cw2Tables &tb, const RegBufs<float> &bf, const AmpScalars &sc, const AmpParams &pr,
-                      int t, hipStream_t s) {
+                      int t, hipStream_t s, hipEvent_t after_ctrl) {
     const size_t lds = C2_LDS_BYTES;  // the P-point image (also the class copy: fpad(maxcls + 16) < 2 P), stM, stI
     static const int ready = []() -> int {  // the image addresses assume no static LDS (c2_at)
         hipFuncAttributes fa, fz;
@@ -967,6 +967,7 @@ static int cw2_launch(const Cw2Tables &tb, const RegBufs<float> &bf, const AmpSc
         ProfScope ps(SG_PH_CW2_CTRL, s);
         hipLaunchKernelGGL((cw2_ctrl<OT>), gB, dim3(C2_T), 0, s, tb, bf, sc, pr, t);
     }
+    if (after_ctrl) SG_HIP(hipEventRecord(after_ctrl, s));
     {
         ProfScope ps(SG_PH_CW2_AZ, s);
         hipLaunchKernelGGL((cw2_az<OT>), g2, dim3(C2_T), lds, s, tb, bf, t);
@@ -979,17 +980,17 @@ static int cw2_launch(const Cw2Tables &tb, const RegBufs<float> &bf, const AmpSc
 }
 
 int cw2_launch_iter(const Cw2Tables &tb, const RegBufs<float> &bf, const AmpScalars &sc, const AmpParams &pr, int t,
-                    hipStream_t s) {
+                    hipStream_t s, hipEvent_t after_ctrl) {
     if (bf.B <= 0) return SG_OK;
     if (tb.Q % 2 || tb.L > 1024 || tb.Lblk > 2 * C2_T || tb.maxcls > C2_NC * C2_SC * C2_T ||
         fpad(tb.maxcls + 16) >= 2 * C2_P || tb.N2 != C2_P * tb.Q)
         return fail(SG_ERR_UNSUPPORTED, "split per-codeword engine: sizes outside its compile-time bounds");
     ProfScope ps(SG_PH_AMP_CW, s);
     switch (tb.OT) {
-    case 12: SG_TRY(cw2_launch<12>(tb, bf, sc, pr, t, s)); break;
-    case 13: SG_TRY(cw2_launch<13>(tb, bf, sc, pr, t, s)); break;
-    case 14: SG_TRY(cw2_launch<14>(tb, bf, sc, pr, t, s)); break;
-    case 16: SG_TRY(cw2_launch<16>(tb, bf, sc, pr, t, s)); break;
+    case 12: SG_TRY(cw2_launch<12>(tb, bf, sc, pr, t, s, after_ctrl)); break;
+    case 13: SG_TRY(cw2_launch<13>(tb, bf, sc, pr, t, s, after_ctrl)); break;
+    case 14: SG_TRY(cw2_launch<14>(tb, bf, sc, pr, t, s, after_ctrl)); break;
+    case 16: SG_TRY(cw2_launch<16>(tb, bf, sc, pr, t, s, after_ctrl)); break;
     default: return fail(SG_ERR_UNSUPPORTED, "split per-codeword engine: %d outputs per thread", tb.OT);
     }
     SG_HIP(hipGetLastError());

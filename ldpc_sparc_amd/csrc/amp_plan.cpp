@@ -450,6 +450,12 @@ int sg_amp_plan_destroy(sg_amp_plan *p) {
         hipEventDestroy(p->poll_ev);
     }
     if (p->h_active) hipHostFree(p->h_active);
+    if (p->pipe_stream) {
+        hipStreamSynchronize(p->pipe_stream);
+        hipStreamDestroy(p->pipe_stream);
+    }
+    for (hipEvent_t e : p->pipe_ev)
+        if (e) hipEventDestroy(e);
     delete p;
     return SG_OK;
 }

@@ -64,6 +64,14 @@ struct sg_amp_plan {
     // active-flag poll (ActivePoll): pinned host copy and its completion event
     int32_t *h_active = nullptr; int h_active_cap = 0;
     hipEvent_t poll_ev = nullptr;
+    // pipelined split engine (capi_amp.cpp Cw2Pipe): the second half-batch's stream and the fork / join / lag /
+    // poll events, created at the first pipelined decode and destroyed with the plan
+    hipStream_t pipe_stream = nullptr;
+    hipEvent_t pipe_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // CU count the engine choice of a decode assumes (0: the device's; sg_amp_plan_set_cus, tests of the
+    // full-batch paths at small B)
+    int cus_assumed = 0;
+    int last_piped = 0;  // the last decode ran iterations as two half-batches on two streams (sg_amp_last_pipelined)
     void *ws_s = nullptr, *ws_tu = nullptr, *ws_xn = nullptr, *ws_part = nullptr, *ws_stM = nullptr,
          *ws_stI = nullptr;
     double *ws_tau_prev = nullptr;

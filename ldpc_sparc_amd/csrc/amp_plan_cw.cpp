@@ -299,7 +299,8 @@ int build_cw2(sg_amp_plan *p, const uint32_t *o0, double sc, const std::vector<i
     std::vector<uint32_t> last_word(T, 0u);
     for (int tid = 0; tid < T; ++tid) {
         int j = 0;
-        if (own[tid].empty()) return SG_OK;  // (amp_cw2.hip's rows write where the thread's last pair is)
+        // (f32 only: amp_cw2.hip's rows write where the thread's last pair is; the f64 form has no padding-slot rows)
+        if (p->precision != SG_F64 && own[tid].empty()) return SG_OK;
         for (int r : own[tid]) {
             const auto &lst = pair_of[r];
             for (size_t q = 0; q < lst.size(); ++q, ++j) {

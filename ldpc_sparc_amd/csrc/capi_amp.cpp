@@ -31,7 +31,7 @@ static bool use_cw(const sg_amp_plan *p, int B) {
     // one workgroup per codeword and CU: worth it when the batch fills whole
     // waves of the CUs (at B = CUs it is ~11 % ahead of the staged engine,
     // which keeps every CU busy at any B)
-    const int cu = std::max(device_cu_count(), 1);
+    const int cu = std::max(p->cus_assumed > 0 ? p->cus_assumed : device_cu_count(), 1);
     const int waves = (B + cu - 1) / cu;
     return B >= cu && (double)B / ((double)waves * cu) >= 0.9;
 }
@@ -59,7 +59,13 @@ struct ActivePoll {
     hipStream_t s;
     bool pending = false;
     const int32_t *flags = nullptr;  // the flags polled: the plan's ws_active, or a loop's own
-    int request() {  // behind the launches already on the stream
+    // pipelined decode (Cw2Pipe): each half's flags are copied on the half's own stream, behind its iteration t
+    // and before its iteration t + 1 as on one stream; the second stream, which runs behind, then waits for
+    // the first half's copy (ev2) and records the one event the host waits for
+    hipStream_t s2 = nullptr;
+    hipEvent_t ev2 = nullptr;
+    int nA = 0;  // codewords of the first half
+    int request() {  // behind the launches already on the stream (both streams of a pipelined decode)
         if (!p->poll_ev) SG_HIP(hipEventCreateWithFlags(&p->poll_ev, hipEventDisableTiming));
         if (p->h_active_cap < B) {
             if (p->h_active) {
@@ -70,9 +76,15 @@ struct ActivePoll {
             SG_HIP(hipHostMalloc((void **)&p->h_active, sizeof(int32_t) * B, hipHostMallocDefault));
             p->h_active_cap = B;
         }
-        SG_HIP(hipMemcpyAsync(p->h_active, flags ? flags : p->ws_active, sizeof(int32_t) * B, hipMemcpyDeviceToHost,
-                              s));
-        SG_HIP(hipEventRecord(p->poll_ev, s));
+        const int32_t *src = flags ? flags : p->ws_active;
+        const int n1 = s2 ? nA : B;
+        SG_HIP(hipMemcpyAsync(p->h_active, src, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, s));
+        if (s2) {
+            SG_HIP(hipEventRecord(ev2, s));
+            SG_HIP(hipMemcpyAsync(p->h_active + n1, src + n1, sizeof(int32_t) * (B - n1), hipMemcpyDeviceToHost, s2));
+            SG_HIP(hipStreamWaitEvent(s2, ev2, 0));
+        }
+        SG_HIP(hipEventRecord(p->poll_ev, s2 ? s2 : s));
         pending = true;
         return SG_OK;
     }
@@ -85,6 +97,82 @@ struct ActivePoll {
         int na = 0;
         for (int b = 0; b < B; ++b) na += p->h_active[b] != 0;
         *n_active = na;
+        return SG_OK;
+    }
+};
+
+// Pipelined split engine: the f32 split engine's iterations as two half-batches in flight on two streams, so
+// that one half's control kernels, launch prologues and drain tails run under the other half's transforms
+// (DESIGN.md "Split per-codeword engine").  Half A (the first ceil(B / 2) codewords) runs on the caller's
+// stream, half B on the plan's second stream; both through the unchanged kernels on views of the per-codeword
+// workspaces offset by the half's first codeword.  Every batch-level decision (poll, np 2 -> 4, hand-over, early
+// end) is taken once for the whole batch at the same iteration index as on one stream, and no codeword reads
+// another's state, so the results do not depend on the split.  Half B starts one launch behind: its first
+// control kernel waits for half A's (a whole iteration 0 behind, so that A's cw2_ab meets B's cw2_az, measured
+// 0.8 % slower: profiles/pipe_bench_ab_d194c7cc_28d51ff2.txt).  SG_AMP_PIPE=0 keeps one stream (A/B tests).
+static bool use_pipe(const sg_amp_plan *p, int B) {
+    const char *e = std::getenv("SG_AMP_PIPE");
+    if (e && std::strcmp(e, "0") == 0) return false;
+    // each half's launch (two workgroups per codeword) still puts a workgroup on every CU
+    const int cu = std::max(p->cus_assumed > 0 ? p->cus_assumed : device_cu_count(), 1);
+    return B >= 2 && 2 * (B / 2) >= cu;
+}
+
+struct Cw2Pipe {
+    sg_amp_plan *p;
+    int B, nA;
+    hipStream_t sa, sb;
+    bool on = false;
+    enum { EV_FORK, EV_JOIN, EV_LAG, EV_POLL };
+    int start() {  // after the decode's initialisation on sa
+        if (!p->pipe_stream) SG_HIP(hipStreamCreateWithFlags(&p->pipe_stream, hipStreamNonBlocking));
+        for (hipEvent_t &e : p->pipe_ev)
+            if (!e) SG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        sb = p->pipe_stream;
+        nA = (B + 1) / 2;
+        prof_pipe_begin(sa);
+        SG_HIP(hipEventRecord(p->pipe_ev[EV_FORK], sa));
+        SG_HIP(hipStreamWaitEvent(sb, p->pipe_ev[EV_FORK], 0));
+        on = true;
+        p->last_piped = 1;
+        return SG_OK;
+    }
+    // the views of codewords [c0, c0 + nb): every per-codeword array moved to its first codeword.  The partial
+    // outputs and statistics keep CW2_NP parts per codeword between the halves whatever np the launch uses, so a
+    // half one iteration ahead with np = 4 never writes where the other still reads with np = 2.
+    void views(int c0, int nb, int t_max, Cw2Tables *tb, RegBufs<float> *bf, AmpScalars *sc) const {
+        const size_t c = (size_t)c0, T = CW2_THREADS, OT = tb->OT;
+        bf->B = nb;
+        bf->s += c * tb->LM; bf->stM += c * tb->L; bf->stI += c * tb->L; bf->y += c * tb->n; bf->z += c * tb->n;
+        bf->phi += c; bf->tau += c; bf->tau_prev += c; bf->active += c; bf->map += c * tb->L;
+        if (bf->true_idx) bf->true_idx += c * tb->L;
+        sc->psi += c; sc->psi_prev += c; sc->phi_prev += c; sc->gamma += c; sc->bcoef += c;
+        sc->nmse += c * t_max; sc->t_final += c;
+        tb->xr += c * CW2_NP * OT * T; tb->part += c * CW2_NP * tb->Lblk;
+        tb->vz += c * (cw2_vz_tm((int)OT) ? cw2_otp((int)OT) : 2 * OT) * T;
+        tb->ys += c * OT * T; tb->zs += c * OT * T;
+        if (tb->tprof) tb->tprof += c * tb->np * 64;
+    }
+    int launch_iter(const RegBufs<float> &bf0, const AmpScalars &sc0, const AmpParams &pr, int t) {
+        for (int h = 0; h < 2; ++h) {
+            Cw2Tables tb = c2tables(p, B);
+            RegBufs<float> bf = bf0;
+            AmpScalars sc = sc0;
+            views(h ? nA : 0, h ? B - nA : nA, pr.t_max, &tb, &bf, &sc);
+            if (t == 0 && h == 1) SG_HIP(hipStreamWaitEvent(sb, p->pipe_ev[EV_LAG], 0));
+            prof_pipe_half(h);
+            const int rc = cw2_launch_iter(tb, bf, sc, pr, t, h ? sb : sa,
+                                           t == 0 && h == 0 ? p->pipe_ev[EV_LAG] : nullptr);
+            prof_pipe_half(-1);
+            SG_TRY(rc);
+        }
+        return SG_OK;
+    }
+    int join() {  // half B's launches into the caller's stream; one stream from here on
+        if (!on) return SG_OK;
+        SG_HIP(hipEventRecord(p->pipe_ev[EV_JOIN], sb));
+        SG_HIP(hipStreamWaitEvent(sa, p->pipe_ev[EV_JOIN], 0));
+        on = false;
         return SG_OK;
     }
 };
@@ -141,6 +229,15 @@ static int decode_regular(sg_amp_plan *p, const DecodeArgs &a, hipStream_t s) {
     bool cw = use_cw(p, B) && (std::is_same<T, float>::value || use_cw2(p));
     p->last_engine = cw ? 2 : 1;
     p->last_handover = -1;
+    p->last_piped = 0;
+    Cw2Pipe pipe{p, B, 0, s, nullptr};
+    if constexpr (std::is_same<T, float>::value)
+        if (cw && use_cw2(p) && use_pipe(p, B) && t_max > 2) {
+            SG_TRY(pipe.start());
+            poll.s2 = pipe.sb;
+            poll.nA = pipe.nA;
+            poll.ev2 = p->pipe_ev[Cw2Pipe::EV_POLL];
+        }
     const char *eng = std::getenv("SG_AMP_ENGINE");
     const bool cw_forced = eng && std::strcmp(eng, "cw") == 0;
     double handover = 0.5;  // active fraction below which the staged engine takes over
@@ -149,7 +246,8 @@ static int decode_regular(sg_amp_plan *p, const DecodeArgs &a, hipStream_t s) {
     for (int t = 0; t < t_max - 1; ++t) {
         if constexpr (std::is_same<T, float>::value) {
             if (cw) {
-                if (use_cw2(p)) SG_TRY(cw2_launch_iter(c2tables(p, B), bf, sc, pr, t, s));
+                if (pipe.on) SG_TRY(pipe.launch_iter(bf, sc, pr, t));
+                else if (use_cw2(p)) SG_TRY(cw2_launch_iter(c2tables(p, B), bf, sc, pr, t, s));
                 else SG_TRY(cw_launch_iter(ctables(p, B), bf, sc, pr, t, s));
             }
         } else {
@@ -176,12 +274,15 @@ static int decode_regular(sg_amp_plan *p, const DecodeArgs &a, hipStream_t s) {
         if (na > 0 && cw && !cw_forced && na < handover * B) {
             cw = false;
             p->last_handover = t + 1;  // first iteration on the staged engine
+            SG_TRY(pipe.join());
+            poll.s2 = nullptr;
             if constexpr (std::is_same<T, float>::value)  // (the split engine keeps z in slot order only)
                 if (use_cw2(p)) SG_TRY(cw2_launch_z_natural(c2tables(p, B), bf, s));
         }
         if (t % 4 == 3 && t + 2 < t_max - 1 && !tb.skip) SG_TRY(poll.request());
     }
     if (poll.pending) SG_HIP(hipEventSynchronize(p->poll_ev));
+    SG_TRY(pipe.join());
     SG_HIP(hipMemsetAsync(p->ws_argmax, 0x7f, sizeof(int32_t) * B * p->L, s));
     SG_TRY(reg_launch_map<T>(tb, bf, s));
     return copy_results(p, a, s);
@@ -455,6 +556,7 @@ static void reset_last(sg_amp_plan *p) {
         q->last_ran = nullptr;
         q->last_engine = -1;
         q->last_handover = -1;
+        q->last_piped = 0;
         q->last_B = 0;
     }
 }
@@ -465,6 +567,20 @@ int sg_amp_plan_engine(const sg_amp_plan *p, int B) {
     SG_CHECK_ARG(p, "plan is NULL");
     if (p->regular) return (sg::use_cw(p, B) && (p->precision == SG_F32 || sg::use_cw2(p))) ? 2 : 1;
     return (p->block || p->block2) ? 3 : 0;
+}
+
+int sg_amp_plan_set_cus(sg_amp_plan *p, int cus) {
+    SG_CHECK_ARG(p && cus >= 0, "plan is NULL or negative CU count");
+    for (sg_amp_plan *q : {p, p->alt})
+        if (q) q->cus_assumed = cus;
+    return SG_OK;
+}
+
+int sg_amp_last_pipelined(const sg_amp_plan *p, int *pipelined) {
+    SG_CHECK_ARG(p && pipelined, "null argument");
+    const sg_amp_plan *r = p->last_ran ? p->last_ran : p;
+    *pipelined = r->last_piped;
+    return SG_OK;
 }
 
 int sg_amp_last_decode(const sg_amp_plan *p, int *engine, int *handover_iter, int *on_companion) {

@@ -25,6 +25,13 @@ int device_cu_count();
 // stream a phase is launched on, resolved by sg_profile_collect.
 int prof_begin(int phase, hipStream_t s);
 void prof_end(int token, hipStream_t s);
+// A decode that runs as two halves on two streams (capi_amp.cpp, pipelined split engine): prof_pipe_begin
+// records the base event of the decode on s (before the fork); between prof_pipe_half(h) and prof_pipe_half(-1)
+// every scope belongs to half h.  sg_profile_collect pairs the k-th scope of a phase in half 0 with the k-th in
+// half 1, counts the pair once, and adds the part of the union of the two intervals (on the base event's time
+// line) that no earlier pair of the phase covered, so overlapped time is counted once.
+void prof_pipe_begin(hipStream_t s);
+void prof_pipe_half(int half);
 struct ProfScope {
     int tok;
     hipStream_t s;

@@ -1,4 +1,5 @@
 // Runtime entry points of the C ABI: errors, devices, streams, memory, events.
+#include <algorithm>
 #include <mutex>
 #include <vector>
 
@@ -84,11 +85,16 @@ int device_cu_count() {
 struct ProfRec {
     int phase;
     hipEvent_t a, b;
+    hipEvent_t base = nullptr;  // a half of a two-stream scope (prof_pipe_begin): the decode's base event
+    int half = -1;
 };
 static bool g_prof_on = false;
 static int g_prof_level = 1;  // 2: the per-iteration scope only (no per-kernel events inside it)
 static std::vector<ProfRec> g_prof_pending;
 static std::vector<hipEvent_t> g_ev_pool;
+static std::vector<hipEvent_t> g_prof_bases;  // base events of the pending two-stream decodes
+static hipEvent_t g_pipe_base = nullptr;
+static int g_pipe_half = -1;
 static double g_prof_ms[SG_PH_COUNT] = {0};
 static int64_t g_prof_n[SG_PH_COUNT] = {0};
 
@@ -113,6 +119,10 @@ int prof_begin(int phase, hipStream_t s) {
     std::lock_guard<std::mutex> lk(g_mu);
     ProfRec r{phase, ev_get(), ev_get()};
     if (!r.a || !r.b) return -1;
+    if (g_pipe_half >= 0 && g_pipe_base) {
+        r.base = g_pipe_base;
+        r.half = g_pipe_half;
+    }
     hipEventRecord(r.a, s);
     g_prof_pending.push_back(r);
     return (int)g_prof_pending.size() - 1;
@@ -122,6 +132,23 @@ void prof_end(int tok, hipStream_t s) {
     if (tok < 0) return;
     std::lock_guard<std::mutex> lk(g_mu);
     if (tok < (int)g_prof_pending.size()) hipEventRecord(g_prof_pending[tok].b, s);
+}
+
+void prof_pipe_begin(hipStream_t s) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_pipe_base = nullptr;
+    g_pipe_half = -1;
+    if (!g_prof_on) return;
+    hipEvent_t e = ev_get();
+    if (!e) return;
+    hipEventRecord(e, s);
+    g_prof_bases.push_back(e);
+    g_pipe_base = e;
+}
+
+void prof_pipe_half(int half) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_pipe_half = half;
 }
 
 }  // namespace sg
@@ -227,10 +254,37 @@ int sg_profile_enable(int on) {
 
 int sg_profile_collect(double *total_ms, int64_t *launches) {
     std::lock_guard<std::mutex> lk(g_mu);
+    // two-stream scopes: the open half-0 scopes of each phase (begin, end on the base event's time line, ms) and
+    // the time up to which the phase's earlier pairs already counted, per base event
+    struct Open { hipEvent_t base; float a, b; };
+    std::vector<Open> open[SG_PH_COUNT];
+    size_t head[SG_PH_COUNT] = {0};
+    hipEvent_t cov_base[SG_PH_COUNT] = {nullptr};
+    float cov_end[SG_PH_COUNT] = {0.f};
     for (auto &r : g_prof_pending) {
         float ms = 0.f;
-        if (hipEventSynchronize(r.b) == hipSuccess && hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess &&
-            r.phase >= 0 && r.phase < SG_PH_COUNT) {
+        const bool ok = r.phase >= 0 && r.phase < SG_PH_COUNT && hipEventSynchronize(r.b) == hipSuccess;
+        if (ok && r.base) {
+            float a = 0.f, b = 0.f;
+            if (hipEventElapsedTime(&a, r.base, r.a) == hipSuccess &&
+                hipEventElapsedTime(&b, r.base, r.b) == hipSuccess) {
+                auto &q = open[r.phase];
+                size_t &h = head[r.phase];
+                if (r.half == 0) {
+                    q.push_back({r.base, a, b});
+                } else if (h < q.size() && q[h].base == r.base) {
+                    const float lo = std::min(a, q[h].a), hi = std::max(b, q[h].b);
+                    ++h;
+                    if (cov_base[r.phase] != r.base) {
+                        cov_base[r.phase] = r.base;
+                        cov_end[r.phase] = lo;
+                    }
+                    g_prof_ms[r.phase] += std::max(0.f, hi - std::max(lo, cov_end[r.phase]));
+                    g_prof_n[r.phase] += 1;
+                    cov_end[r.phase] = std::max(cov_end[r.phase], hi);
+                }
+            }
+        } else if (ok && hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
             g_prof_ms[r.phase] += ms;
             g_prof_n[r.phase] += 1;
         }
@@ -238,6 +292,9 @@ int sg_profile_collect(double *total_ms, int64_t *launches) {
         g_ev_pool.push_back(r.b);
     }
     g_prof_pending.clear();
+    for (hipEvent_t e : g_prof_bases) g_ev_pool.push_back(e);
+    g_prof_bases.clear();
+    g_pipe_base = nullptr;
     for (int i = 0; i < SG_PH_COUNT; ++i) {
         if (total_ms) total_ms[i] = g_prof_ms[i];
         if (launches) launches[i] = g_prof_n[i];
