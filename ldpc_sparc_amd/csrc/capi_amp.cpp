@@ -99,6 +99,19 @@ struct ActivePoll {
         *n_active = na;
         return SG_OK;
     }
+    // One iteration of a loop that only stops on the poll: collects the flags requested an iteration ago
+    // (*stopped: every codeword had stopped) and, if `due`, requests the flags behind this iteration's launches
+    int step(bool due, bool *stopped) {
+        int na = -1;
+        SG_TRY(collect(&na));
+        *stopped = na == 0;
+        if (due && !*stopped) SG_TRY(request());
+        return SG_OK;
+    }
+    // no copy into the plan's h_active outlives the loop, whichever way it is left
+    ~ActivePoll() {
+        if (pending) (void)hipEventSynchronize(p->poll_ev);
+    }
 };
 
 // Pipelined split engine: the f32 split engine's iterations as two half-batches in flight on two streams, so
@@ -281,7 +294,6 @@ static int decode_regular(sg_amp_plan *p, const DecodeArgs &a, hipStream_t s) {
         }
         if (t % 4 == 3 && t + 2 < t_max - 1 && !tb.skip) SG_TRY(poll.request());
     }
-    if (poll.pending) SG_HIP(hipEventSynchronize(p->poll_ev));
     SG_TRY(pipe.join());
     SG_HIP(hipMemsetAsync(p->ws_argmax, 0x7f, sizeof(int32_t) * B * p->L, s));
     SG_TRY(reg_launch_map<T>(tb, bf, s));
@@ -325,12 +337,10 @@ static int decode_impl(sg_amp_plan *p, const DecodeArgs &a, hipStream_t s) {
         }
         // skip the remaining launches once every codeword stopped (ActivePoll: the flags after
         // iterations 3, 7, 11, ..., read one iteration later)
-        int na = -1;
-        SG_TRY(poll.collect(&na));
-        if (na == 0) break;
-        if (t % 4 == 3 && t + 2 < t_max - 1) SG_TRY(poll.request());
+        bool stopped = false;
+        SG_TRY(poll.step(t % 4 == 3 && t + 2 < t_max - 1, &stopped));
+        if (stopped) break;
     }
-    if (poll.pending) SG_HIP(hipEventSynchronize(p->poll_ev));
     return copy_results(p, a, s);
 }
 
@@ -494,13 +504,20 @@ static int partial_impl(sg_amp_plan *p, const DecodeArgs &a, const int32_t *d_kn
         SG_TRY(part_launch_control<T>(pb, 1, t, s));
         // skip the remaining launches once every codeword stopped (ActivePoll: the flags after iterations 3, 7,
         // 11, ..., read one iteration later)
-        int na = -1;
-        SG_TRY(poll.collect(&na));
-        if (na == 0) break;
-        if (t % 4 == 3 && t + 2 < t_max - 1) SG_TRY(poll.request());
+        bool stopped = false;
+        SG_TRY(poll.step(t % 4 == 3 && t + 2 < t_max - 1, &stopped));
+        if (stopped) break;
     }
-    if (poll.pending) SG_HIP(hipEventSynchronize(p->poll_ev));
     return copy_results(p, a, s);
+}
+
+// The refusals of a decode's scalar parameters
+static int param_checks(double awgn_var, int t_max, double rtol, int phi_method) {
+    SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
+    SG_CHECK_ARG(rtol > 0 && rtol < 1, "rtol must be in (0, 1)");
+    SG_CHECK_ARG(phi_method == 1 || phi_method == 2, "phi_est_method must be 1 or 2");
+    SG_CHECK_ARG(awgn_var >= 0, "awgn_var must be >= 0");
+    return SG_OK;
 }
 
 // Every refusal of the partial decode that needs no device (header, sg_amp_decode_partial_device)
@@ -511,10 +528,36 @@ static int partial_checks(const sg_amp_plan *p, double awgn_var, int t_max, doub
     if (p->M < 2 || (p->M & (p->M - 1)) != 0 || p->M > 2048)
         return fail(SG_ERR_UNSUPPORTED, "section size M = %d: the partial section kernel takes a power of two in "
                     "[2, 2048]", p->M);
-    SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
-    SG_CHECK_ARG(rtol > 0 && rtol < 1, "rtol must be in (0, 1)");
-    SG_CHECK_ARG(phi_method == 1 || phi_method == 2, "phi_est_method must be 1 or 2");
-    SG_CHECK_ARG(awgn_var >= 0, "awgn_var must be >= 0");
+    return param_checks(awgn_var, t_max, rtol, phi_method);
+}
+
+// The host side of a decode, after the entry point's refusals: y (and the known and true sections) into the plan's
+// buffers, the decode there, the results back.  known_idx null: decode_impl; given: partial_impl.
+static int decode_host(sg_amp_plan *p, const double *y, int B, const int32_t *known_idx, const int32_t *true_idx,
+                       double awgn_var, int t_max, double rtol, int phi_method, int32_t *map_idx, int32_t *t_final,
+                       double *nmse, double *psi) {
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = lib_stream();
+    // (the workspace before the staging buffer: growing the workspace frees io too)
+    SG_TRY(ensure_ws(p, B, t_max));
+    if (known_idx) SG_TRY(partial_ensure_ws(p, B));
+    const size_t ny = (size_t)B * p->n, nsec = (size_t)B * p->L;
+    SG_TRY(ensure_io(p, ny * sizeof(double)));
+    SG_HIP(hipMemcpyAsync(p->io.at(), y, ny * sizeof(double), hipMemcpyHostToDevice, s));
+    if (known_idx) SG_HIP(hipMemcpyAsync(p->wp_known, known_idx, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
+    if (true_idx) SG_HIP(hipMemcpyAsync(p->ws_true, true_idx, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
+    SG_TRY(by_precision(p->precision, [&](auto t) {
+        using T = decltype(t);
+        SG_TRY(amp_launch_cast<T>(p->io.at(), 1, (T *)p->ws_y, ny, s));
+        const DecodeArgs a{p->ws_y, B, true_idx ? p->ws_true : nullptr, awgn_var, t_max, rtol, phi_method,
+                           nullptr, nullptr, nullptr, nullptr};
+        return known_idx ? partial_impl<T>(p, a, p->wp_known, s) : decode_impl<T>(p, a, s);
+    }));
+    SG_HIP(hipMemcpyAsync(map_idx, p->ws_argmax, sizeof(int32_t) * nsec, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(t_final, p->ws_tfinal, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(nmse, p->ws_nmse, sizeof(double) * B * t_max * p->Lc, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(psi, p->ws_psi, sizeof(double) * B * p->Lc, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
     return SG_OK;
 }
 
@@ -597,10 +640,7 @@ int sg_amp_decode_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *
                          double *d_nmse, double *d_psi, void *stream) {
     SG_CHECK_ARG(p, "plan is NULL");
     reset_last(p);
-    SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
-    SG_CHECK_ARG(rtol > 0 && rtol < 1, "rtol must be in (0, 1)");
-    SG_CHECK_ARG(phi_method == 1 || phi_method == 2, "phi_est_method must be 1 or 2");
-    SG_CHECK_ARG(awgn_var >= 0, "awgn_var must be >= 0");
+    SG_TRY(sg::param_checks(awgn_var, t_max, rtol, phi_method));
     SG_CHECK_ARG(B >= 0, "negative batch");
     if (B == 0) return SG_OK;
     SG_CHECK_ARG(d_y, "d_y is NULL");
@@ -626,26 +666,7 @@ int sg_amp_decode(sg_amp_plan *p, const double *y, int B, const int32_t *true_id
     sg_amp_plan *const handle = p;
     p = p->last_ran = sg::decode_plan(p, B);
     SG_TRY(ensure_device());
-    SG_HIP(hipSetDevice(p->device));
-    hipStream_t s = lib_stream();
-    SG_TRY(ensure_ws(p, B, t_max));
-    const size_t ny = (size_t)B * p->n;
-    SG_TRY(ensure_io(p, ny * sizeof(double)));
-    SG_HIP(hipMemcpyAsync(p->io.at(), y, ny * sizeof(double), hipMemcpyHostToDevice, s));
-    SG_TRY(by_precision(p->precision, [&](auto t) {
-        using T = decltype(t);
-        SG_TRY(amp_launch_cast<T>(p->io.at(), 1, (T *)p->ws_y, ny, s));
-        if (true_idx)
-            SG_HIP(hipMemcpyAsync(p->ws_true, true_idx, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
-        const DecodeArgs a{p->ws_y, B, true_idx ? p->ws_true : nullptr, awgn_var, t_max, rtol, phi_method,
-                           nullptr, nullptr, nullptr, nullptr};
-        return decode_impl<T>(p, a, s);
-    }));
-    SG_HIP(hipMemcpyAsync(map_idx, p->ws_argmax, sizeof(int32_t) * B * p->L, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(t_final, p->ws_tfinal, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(nmse, p->ws_nmse, sizeof(double) * B * t_max * p->Lc, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(psi, p->ws_psi, sizeof(double) * B * p->Lc, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipStreamSynchronize(s));
+    SG_TRY(sg::decode_host(p, y, B, nullptr, true_idx, awgn_var, t_max, rtol, phi_method, map_idx, t_final, nmse, psi));
     handle->last_B = B;
     return SG_OK;
 }
@@ -677,29 +698,8 @@ int sg_amp_decode_partial(sg_amp_plan *p, const double *y, int B, const int32_t 
     for (size_t i = 0; i < (size_t)B * p->L; ++i)
         SG_CHECK_ARG(known_idx[i] >= -1 && known_idx[i] < p->M, "known_idx[%zu] = %d outside [-1, %d)", i,
                      (int)known_idx[i], p->M);
-    SG_HIP(hipSetDevice(p->device));
-    hipStream_t s = lib_stream();
-    // (the workspace before the staging buffer: growing the workspace frees io too)
-    SG_TRY(ensure_ws(p, B, t_max));
-    SG_TRY(partial_ensure_ws(p, B));
-    const size_t ny = (size_t)B * p->n;
-    SG_TRY(ensure_io(p, ny * sizeof(double)));
-    SG_HIP(hipMemcpyAsync(p->io.at(), y, ny * sizeof(double), hipMemcpyHostToDevice, s));
-    SG_HIP(hipMemcpyAsync(p->wp_known, known_idx, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
-    if (true_idx) SG_HIP(hipMemcpyAsync(p->ws_true, true_idx, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
-    SG_TRY(by_precision(p->precision, [&](auto t) {
-        using T = decltype(t);
-        SG_TRY(amp_launch_cast<T>(p->io.at(), 1, (T *)p->ws_y, ny, s));
-        const DecodeArgs a{p->ws_y, B, true_idx ? p->ws_true : nullptr, awgn_var, t_max, rtol, phi_method,
-                           nullptr, nullptr, nullptr, nullptr};
-        return partial_impl<T>(p, a, p->wp_known, s);
-    }));
-    SG_HIP(hipMemcpyAsync(map_idx, p->ws_argmax, sizeof(int32_t) * B * p->L, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(t_final, p->ws_tfinal, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(nmse, p->ws_nmse, sizeof(double) * B * t_max * p->Lc, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(psi, p->ws_psi, sizeof(double) * B * p->Lc, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipStreamSynchronize(s));
-    return SG_OK;
+    return sg::decode_host(p, y, B, known_idx, true_idx, awgn_var, t_max, rtol, phi_method, map_idx, t_final, nmse,
+                           psi);
 }
 
 int sg_concat_known_sections_device(int precision, const void *d_app, const int32_t *d_it, int max_it, int B, int mults,

@@ -136,6 +136,51 @@ CampBufs bufs(const sg_camp_plan *p, int B, int K) {
 
 bool psk_order_ok(int K) { return K >= 1 && (K & (K - 1)) == 0; }
 
+int psk_max_check(int K) {
+    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    return SG_OK;
+}
+
+int psk_order_checks(int K) {
+    SG_CHECK_ARG(psk_order_ok(K), "K must be 1 or a power of two");
+    return psk_max_check(K);
+}
+
+// The refusals every decode shares: the scalar parameters, then the PSK order
+int decode_param_checks(int K, double awgn_var, int t_max, double rtol, int phi_method) {
+    SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
+    SG_CHECK_ARG(rtol > 0 && rtol < 1, "rtol must be in (0, 1)");
+    SG_CHECK_ARG(phi_method == 1 || phi_method == 2, "phi_est_method must be 1 or 2");
+    SG_CHECK_ARG(awgn_var >= 0, "awgn_var must be >= 0");
+    return psk_order_checks(K);
+}
+
+int bits_per_section(int M, int K) {  // log2 M + log2 K
+    int per = 0;
+    while ((1 << per) < M) ++per;
+    for (int k = 1; k < K; k <<= 1) ++per;
+    return per;
+}
+
+// Staging of the sg_section_*_psk host functions: x[L*M] (interleaved complex if is_complex, else real) as cxd in
+// d and the constellation in dc, uploaded on s, with `extra` bytes for the results behind them (res).  It holds the
+// host copy the upload reads, so it lives until the caller has synchronised s.
+struct SectionStage {
+    std::vector<cxd> hx;
+    DevMem mem;
+    cxd *d = nullptr, *dc = nullptr;
+    void *res = nullptr;
+    int upload(const double *x, size_t N, int is_complex, int K, const double *constel, size_t extra, hipStream_t s) {
+        hx.resize(N);
+        for (size_t i = 0; i < N; ++i) hx[i] = is_complex ? cxd{x[2 * i], x[2 * i + 1]} : cxd{x[i], 0.0};
+        SG_TRY(mem.ensure((N + CAMP_MAX_K) * sizeof(cxd) + extra));
+        d = mem.at<cxd>(); dc = d + N; res = dc + CAMP_MAX_K;
+        SG_HIP(hipMemcpyAsync(d, hx.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
+        if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
+        return SG_OK;
+    }
+};
+
 constexpr int CAMP_MAX_B = 65535;  // the batch is a grid dimension of every kernel
 
 // The plan's device constellation, uploaded from the plan's own host copy (an
@@ -154,13 +199,101 @@ int set_constel(sg_camp_plan *p, int K, const double *constel, hipStream_t s) {
 // Every refusal of the partial decode that its two variants share: sg_camp_decode_device's, before any launch
 int partial_checks(int B, int K, const double *constel, double awgn_var, int t_max, double rtol, int phi_method) {
     SG_CHECK_ARG(B <= CAMP_MAX_B, "batch must be at most 65535");
-    SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
-    SG_CHECK_ARG(rtol > 0 && rtol < 1, "rtol must be in (0, 1)");
-    SG_CHECK_ARG(phi_method == 1 || phi_method == 2, "phi_est_method must be 1 or 2");
-    SG_CHECK_ARG(awgn_var >= 0, "awgn_var must be >= 0");
-    SG_CHECK_ARG(psk_order_ok(K), "K must be 1 or a power of two");
-    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    SG_TRY(decode_param_checks(K, awgn_var, t_max, rtol, phi_method));
     SG_CHECK_ARG(K == 1 || constel, "K > 1 needs the constellation");
+    return SG_OK;
+}
+
+// What a decode is asked for, in the order of sg_camp_decode_partial_device's arguments (results: null if not
+// wanted).  d_known_idx null is the plain decode; given (with d_known_sym for K > 1), those sections are known.
+struct CampArgs {
+    const void *d_y; int B, K; const double *constel;
+    const int32_t *d_known_idx, *d_known_sym, *d_true_idx, *d_true_sym;
+    double awgn_var; int t_max; double rtol; int phi_method;
+    int32_t *d_map_idx, *d_map_sym, *d_t_final; double *d_nmse, *d_psi;
+};
+
+// The AMP decode on device arrays, after the entry point's refusals.  With known sections (camp_partial.hip) the
+// initialisation builds beta0 from them, iteration 0 runs the forward transform of beta0 too and has its own
+// residual kernel, and the eta kernel keeps them fixed; s_keep is then not refilled.
+int decode_impl(sg_camp_plan *p, const CampArgs &a, hipStream_t s) {
+    const int B = a.B, K = a.K, t_max = a.t_max;
+    const bool part = a.d_known_idx != nullptr;
+    const int32_t *ksym = K > 1 ? a.d_known_sym : nullptr;
+    SG_TRY(ensure_ws(p, B, t_max));
+    SG_TRY(set_constel(p, K, a.constel, s));
+    const CampTables tb = tables(p);
+    // y is only read (z = y at t = 0); outputs the caller does not want land in the workspace
+    CampBufs bf = bufs(p, B, K);
+    bf.y = (const cxd *)a.d_y;
+    bf.sec_idx = a.d_map_idx ? a.d_map_idx : p->sec_idx;
+    bf.sec_sym = a.d_map_sym ? a.d_map_sym : p->sec_sym;
+    bf.true_idx = a.d_true_idx;
+    bf.true_sym = (K > 1 && a.d_true_idx) ? a.d_true_sym : nullptr;
+    bf.s_keep = (p->soft && !part) ? p->s_keep : nullptr;
+    AmpScalars sc;
+    sc.psi = a.d_psi ? a.d_psi : p->psi; sc.psi_prev = p->psi_prev; sc.phi_prev = p->phi_prev; sc.gamma = p->gamma;
+    sc.bcoef = p->bco;
+    sc.nmse = a.d_nmse ? a.d_nmse : p->nmse; sc.t_final = a.d_t_final ? a.d_t_final : p->t_final;
+    AmpParams pr;
+    pr.W = p->dW; pr.awgn_var = a.awgn_var; pr.rtol = a.rtol;
+    pr.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
+    pr.phi_method = a.phi_method; pr.t_max = t_max;
+    SG_HIP(hipMemsetAsync(p->beta, 0, (size_t)B * p->LM * sizeof(cxd), s));
+    SG_HIP(hipMemsetAsync(bf.sec_idx, 0, sizeof(int32_t) * B * p->L, s));
+    SG_HIP(hipMemsetAsync(bf.sec_sym, 0, sizeof(int32_t) * B * p->L, s));
+    if (part) SG_TRY(camp_part_launch_init(tb, bf, sc, pr, a.d_known_idx, ksym, s));
+    else SG_TRY(camp_launch_control(tb, bf, sc, pr, 2, 0, s));
+    std::vector<int32_t> act(B);
+    for (int t = 0; t < t_max - 1; ++t) {
+        if (t > 0 || part) SG_TRY(camp_launch_fft(tb, bf, false, s));
+        if (t == 0 && part) SG_TRY(camp_part_launch_start(tb, bf, sc, pr, s));
+        else SG_TRY(camp_launch_control(tb, bf, sc, pr, 0, t, s));
+        SG_TRY(camp_launch_fft(tb, bf, true, s));
+        if (part) SG_TRY(camp_part_launch_eta(tb, bf, a.d_known_idx, ksym, s));
+        else SG_TRY(camp_launch_eta(tb, bf, s));
+        SG_TRY(camp_launch_control(tb, bf, sc, pr, 1, t, s));
+        if (t % 4 == 3 && t + 1 < t_max - 1) {  // skip the remaining launches once every codeword stopped
+            SG_HIP(hipMemcpyAsync(act.data(), p->active, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+            SG_HIP(hipStreamSynchronize(s));
+            int na = 0;
+            for (int b = 0; b < B; ++b) na += act[b] != 0;
+            if (na == 0) break;
+        }
+    }
+    return SG_OK;
+}
+
+// upload -> decode_impl on the plan's own buffers -> download, after the entry point's refusals; known_idx null is
+// the plain decode
+int decode_host(sg_camp_plan *p, const double *y, int B, int K, const double *constel, const int32_t *known_idx,
+                const int32_t *known_sym, const int32_t *true_idx, const int32_t *true_sym, double awgn_var, int t_max,
+                double rtol, int phi_method, int32_t *map_idx, int32_t *map_sym, int32_t *t_final, double *nmse,
+                double *psi) {
+    const size_t nsec = (size_t)B * p->L;
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = lib_stream();
+    SG_TRY(ensure_ws(p, B, t_max));
+    if (known_idx) SG_TRY(ensure_known(p, B));
+    SG_HIP(hipMemcpyAsync(p->y, y, (size_t)B * p->n * sizeof(cxd), hipMemcpyHostToDevice, s));
+    if (known_idx) {
+        SG_HIP(hipMemcpyAsync(p->known_idx, known_idx, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
+        if (K > 1) SG_HIP(hipMemcpyAsync(p->known_sym, known_sym, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
+    }
+    if (true_idx) {
+        SG_HIP(hipMemcpyAsync(p->true_idx, true_idx, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
+        if (K > 1) SG_HIP(hipMemcpyAsync(p->true_sym, true_sym, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
+    }
+    const CampArgs a{p->y, B, K, constel, known_idx ? p->known_idx : nullptr, known_idx ? p->known_sym : nullptr,
+                     true_idx ? p->true_idx : nullptr, (true_idx && K > 1) ? p->true_sym : nullptr, awgn_var, t_max,
+                     rtol, phi_method, p->sec_idx, p->sec_sym, p->t_final, p->nmse, p->psi};
+    SG_TRY(decode_impl(p, a, s));
+    SG_HIP(hipMemcpyAsync(map_idx, p->sec_idx, sizeof(int32_t) * nsec, hipMemcpyDeviceToHost, s));
+    if (map_sym) SG_HIP(hipMemcpyAsync(map_sym, p->sec_sym, sizeof(int32_t) * nsec, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(t_final, p->t_final, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(nmse, p->nmse, sizeof(double) * B * t_max * p->Lc, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipMemcpyAsync(psi, p->psi, sizeof(double) * B * p->Lc, hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
     return SG_OK;
 }
 
@@ -310,59 +443,38 @@ int sg_camp_decode_device(sg_camp_plan *p, const void *d_y, int B, int K, const 
     SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B, "batch must be in [0, 65535]");
     if (B == 0) return SG_OK;
     SG_CHECK_ARG(d_y, "null received words");
-    SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
-    SG_CHECK_ARG(rtol > 0 && rtol < 1, "rtol must be in (0, 1)");
-    SG_CHECK_ARG(phi_method == 1 || phi_method == 2, "phi_est_method must be 1 or 2");
-    SG_CHECK_ARG(awgn_var >= 0, "awgn_var must be >= 0");
-    SG_CHECK_ARG(psk_order_ok(K), "K must be 1 or a power of two");
-    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    SG_TRY(decode_param_checks(K, awgn_var, t_max, rtol, phi_method));
     SG_CHECK_ARG(K == 1 || constel, "K > 1 needs the constellation");
     SG_CHECK_ARG(K == 1 || !d_true_idx || d_true_sym, "K > 1 with true_idx needs true_sym");
     SG_HIP(hipSetDevice(p->device));
-    hipStream_t s = pick_stream(stream);
-    SG_TRY(ensure_ws(p, B, t_max));
-    SG_TRY(set_constel(p, K, constel, s));
-    const CampTables tb = tables(p);
-    // y is only read (z = y at t = 0); outputs the caller does not want land in the workspace
-    CampBufs bf = bufs(p, B, K);
-    bf.y = (const cxd *)d_y;
-    bf.sec_idx = d_map_idx ? d_map_idx : p->sec_idx;
-    bf.sec_sym = d_map_sym ? d_map_sym : p->sec_sym;
-    bf.true_idx = d_true_idx;
-    bf.true_sym = (K > 1 && d_true_idx) ? d_true_sym : nullptr;
-    bf.s_keep = p->soft ? p->s_keep : nullptr;
-    AmpScalars sc;
-    sc.psi = d_psi ? d_psi : p->psi; sc.psi_prev = p->psi_prev; sc.phi_prev = p->phi_prev; sc.gamma = p->gamma;
-    sc.bcoef = p->bco;
-    sc.nmse = d_nmse ? d_nmse : p->nmse; sc.t_final = d_t_final ? d_t_final : p->t_final;
-    AmpParams pr;
-    pr.W = p->dW; pr.awgn_var = awgn_var; pr.rtol = rtol;
-    pr.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
-    pr.phi_method = phi_method; pr.t_max = t_max;
-    SG_HIP(hipMemsetAsync(p->beta, 0, (size_t)B * p->LM * sizeof(cxd), s));
-    SG_HIP(hipMemsetAsync(bf.sec_idx, 0, sizeof(int32_t) * B * p->L, s));
-    SG_HIP(hipMemsetAsync(bf.sec_sym, 0, sizeof(int32_t) * B * p->L, s));
-    SG_TRY(camp_launch_control(tb, bf, sc, pr, 2, 0, s));
-    std::vector<int32_t> act(B);
-    for (int t = 0; t < t_max - 1; ++t) {
-        if (t > 0) SG_TRY(camp_launch_fft(tb, bf, false, s));
-        SG_TRY(camp_launch_control(tb, bf, sc, pr, 0, t, s));
-        SG_TRY(camp_launch_fft(tb, bf, true, s));
-        SG_TRY(camp_launch_eta(tb, bf, s));
-        SG_TRY(camp_launch_control(tb, bf, sc, pr, 1, t, s));
-        if (t % 4 == 3 && t + 1 < t_max - 1) {  // skip the remaining launches once every codeword stopped
-            SG_HIP(hipMemcpyAsync(act.data(), p->active, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-            SG_HIP(hipStreamSynchronize(s));
-            int na = 0;
-            for (int b = 0; b < B; ++b) na += act[b] != 0;
-            if (na == 0) break;
-        }
-    }
+    const CampArgs a{d_y, B, K, constel, nullptr, nullptr, d_true_idx, d_true_sym, awgn_var, t_max, rtol, phi_method,
+                     d_map_idx, d_map_sym, d_t_final, d_nmse, d_psi};
+    SG_TRY(decode_impl(p, a, pick_stream(stream)));
     if (p->soft) { p->last_B = B; p->last_K = K; }
     return SG_OK;
 }
 
-// upload -> sg_camp_decode_device on the plan's own buffers -> download
+// The decode with the known sections given: sg_camp_decode_device's driver; the soft-output state stays cleared
+// (the loop overwrites what a decode left, and s_keep is not refilled)
+int sg_camp_decode_partial_device(sg_camp_plan *p, const void *d_y, int B, int K, const double *constel,
+                                  const int32_t *d_known_idx, const int32_t *d_known_sym, const int32_t *d_true_idx,
+                                  const int32_t *d_true_sym, double awgn_var, int t_max, double rtol, int phi_method,
+                                  int32_t *d_map_idx, int32_t *d_map_sym, int32_t *d_t_final, double *d_nmse,
+                                  double *d_psi, void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    p->last_B = p->last_K = 0;
+    SG_TRY(partial_checks(B, K, constel, awgn_var, t_max, rtol, phi_method));
+    if (B <= 0) return SG_OK;
+    SG_CHECK_ARG(d_y && d_known_idx, "d_y or d_known_idx is NULL");
+    SG_CHECK_ARG(K == 1 || d_known_sym, "K > 1 needs d_known_sym");
+    SG_CHECK_ARG(K == 1 || !d_true_idx || d_true_sym, "K > 1 with true_idx needs true_sym");
+    SG_HIP(hipSetDevice(p->device));
+    const CampArgs a{d_y, B, K, constel, d_known_idx, d_known_sym, d_true_idx, d_true_sym, awgn_var, t_max, rtol,
+                     phi_method, d_map_idx, d_map_sym, d_t_final, d_nmse, d_psi};
+    return decode_impl(p, a, pick_stream(stream));
+}
+
 int sg_camp_decode(sg_camp_plan *p, const double *y, int B, int K, const double *constel, const int32_t *true_idx,
                    const int32_t *true_sym, double awgn_var, int t_max, double rtol, int phi_method, int32_t *map_idx,
                    int32_t *map_sym, int32_t *t_final, double *nmse, double *psi) {
@@ -372,12 +484,7 @@ int sg_camp_decode(sg_camp_plan *p, const double *y, int B, int K, const double 
     SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B, "batch must be in [0, 65535]");
     if (B == 0) return SG_OK;
     SG_CHECK_ARG(y && map_idx && t_final && nmse && psi, "null host buffer");
-    SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
-    SG_CHECK_ARG(rtol > 0 && rtol < 1, "rtol must be in (0, 1)");
-    SG_CHECK_ARG(phi_method == 1 || phi_method == 2, "phi_est_method must be 1 or 2");
-    SG_CHECK_ARG(awgn_var >= 0, "awgn_var must be >= 0");
-    SG_CHECK_ARG(psk_order_ok(K), "K must be 1 or a power of two");
-    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    SG_TRY(decode_param_checks(K, awgn_var, t_max, rtol, phi_method));
     SG_CHECK_ARG(K == 1 || (constel && map_sym), "K > 1 needs the constellation and map_sym");
     SG_CHECK_ARG(K == 1 || !true_idx || true_sym, "K > 1 with true_idx needs true_sym");
     if (true_idx)
@@ -385,24 +492,36 @@ int sg_camp_decode(sg_camp_plan *p, const double *y, int B, int K, const double 
             SG_CHECK_ARG(true_idx[i] >= 0 && true_idx[i] < p->M, "true_idx out of range");
             SG_CHECK_ARG(K == 1 || (true_sym[i] >= 0 && true_sym[i] < K), "true_sym out of range");
         }
-    SG_HIP(hipSetDevice(p->device));
-    hipStream_t s = lib_stream();
-    SG_TRY(ensure_ws(p, B, t_max));
-    SG_HIP(hipMemcpyAsync(p->y, y, (size_t)B * p->n * sizeof(cxd), hipMemcpyHostToDevice, s));
-    if (true_idx) {
-        SG_HIP(hipMemcpyAsync(p->true_idx, true_idx, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
-        if (K > 1) SG_HIP(hipMemcpyAsync(p->true_sym, true_sym, sizeof(int32_t) * B * p->L, hipMemcpyHostToDevice, s));
-    }
-    SG_TRY(sg_camp_decode_device(p, p->y, B, K, constel, true_idx ? p->true_idx : nullptr,
-                                 (true_idx && K > 1) ? p->true_sym : nullptr, awgn_var, t_max, rtol, phi_method,
-                                 p->sec_idx, p->sec_sym, p->t_final, p->nmse, p->psi, nullptr));
-    SG_HIP(hipMemcpyAsync(map_idx, p->sec_idx, sizeof(int32_t) * B * p->L, hipMemcpyDeviceToHost, s));
-    if (map_sym) SG_HIP(hipMemcpyAsync(map_sym, p->sec_sym, sizeof(int32_t) * B * p->L, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(t_final, p->t_final, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(nmse, p->nmse, sizeof(double) * B * t_max * p->Lc, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(psi, p->psi, sizeof(double) * B * p->Lc, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipStreamSynchronize(s));
+    SG_TRY(decode_host(p, y, B, K, constel, nullptr, nullptr, true_idx, true_sym, awgn_var, t_max, rtol, phi_method,
+                       map_idx, map_sym, t_final, nmse, psi));
+    if (p->soft) { p->last_B = B; p->last_K = K; }
     return SG_OK;
+}
+
+int sg_camp_decode_partial(sg_camp_plan *p, const double *y, int B, int K, const double *constel,
+                           const int32_t *known_idx, const int32_t *known_sym, const int32_t *true_idx,
+                           const int32_t *true_sym, double awgn_var, int t_max, double rtol, int phi_method,
+                           int32_t *map_idx, int32_t *map_sym, int32_t *t_final, double *nmse, double *psi) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    p->last_B = p->last_K = 0;
+    SG_TRY(partial_checks(B, K, constel, awgn_var, t_max, rtol, phi_method));
+    if (B <= 0) return SG_OK;
+    SG_CHECK_ARG(y && known_idx && map_idx && t_final && nmse && psi, "null host buffer");
+    SG_CHECK_ARG(K == 1 || (known_sym && map_sym), "K > 1 needs known_sym and map_sym");
+    SG_CHECK_ARG(K == 1 || !true_idx || true_sym, "K > 1 with true_idx needs true_sym");
+    for (size_t i = 0; i < (size_t)B * p->L; ++i) {
+        SG_CHECK_ARG(known_idx[i] >= -1 && known_idx[i] < p->M, "known_idx[%zu] = %d outside [-1, %d)", i,
+                     (int)known_idx[i], p->M);
+        SG_CHECK_ARG(K == 1 || known_idx[i] < 0 || (known_sym[i] >= 0 && known_sym[i] < K),
+                     "known_sym[%zu] = %d outside [0, %d)", i, K > 1 ? (int)known_sym[i] : 0, K);
+        if (true_idx) {
+            SG_CHECK_ARG(true_idx[i] >= 0 && true_idx[i] < p->M, "true_idx out of range");
+            SG_CHECK_ARG(K == 1 || (true_sym[i] >= 0 && true_sym[i] < K), "true_sym out of range");
+        }
+    }
+    return decode_host(p, y, B, K, constel, known_idx, known_sym, true_idx, true_sym, awgn_var, t_max, rtol,
+                       phi_method, map_idx, map_sym, t_final, nmse, psi);
 }
 
 int sg_bits_to_psk_sections_device(const uint8_t *d_bits, int B, int L, int logM, int logK, int32_t *d_idx,
@@ -422,8 +541,7 @@ int sg_camp_encode_device(sg_camp_plan *p, int K, const double *constel, const i
     SG_CHECK_ARG(p && d_idx && d_x, "null argument");
     SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B, "batch must be in [0, 65535]");
     if (B == 0) return SG_OK;
-    SG_CHECK_ARG(psk_order_ok(K), "K must be 1 or a power of two");
-    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    SG_TRY(psk_order_checks(K));
     SG_CHECK_ARG(K == 1 || (constel && d_sym), "K > 1 needs the constellation and d_sym");
     p->last_B = p->last_K = 0;  // overwrites beta
     SG_HIP(hipSetDevice(p->device));
@@ -454,19 +572,15 @@ int sg_camp_count_errors_device(const int32_t *d_map_idx, const int32_t *d_map_s
 int sg_section_mmse_psk(const double *x, int L, int M, int K, const double *constel, int x_is_complex, double *out) {
     SG_CHECK_ARG(x && out && L >= 0 && M > 0, "bad arguments");
     SG_CHECK_ARG(psk_order_ok(K) && (K == 1 || constel), "K must be 1 or a power of two with its constellation");
-    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    SG_TRY(psk_max_check(K));
     if (L == 0) return SG_OK;
     SG_TRY(ensure_device());
     hipStream_t s = lib_stream();
     const size_t N = (size_t)L * M;
-    std::vector<cxd> hx(N);
-    for (size_t i = 0; i < N; ++i) hx[i] = x_is_complex ? cxd{x[2 * i], x[2 * i + 1]} : cxd{x[i], 0.0};
-    DevMem mem;
-    SG_TRY(mem.ensure((2 * N + CAMP_MAX_K) * sizeof(cxd)));
-    cxd *d = mem.at<cxd>(), *dout = d + N, *dc = d + 2 * N;
-    SG_HIP(hipMemcpyAsync(d, hx.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
-    if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
-    SG_TRY(camp_launch_mmse(d, L, M, K, dc, dout, s));
+    SectionStage st;
+    SG_TRY(st.upload(x, N, x_is_complex, K, constel, N * sizeof(cxd), s));
+    cxd *dout = (cxd *)st.res;
+    SG_TRY(camp_launch_mmse(st.d, L, M, K, st.dc, dout, s));
     SG_HIP(hipMemcpyAsync(out, dout, N * sizeof(cxd), hipMemcpyDeviceToHost, s));
     SG_HIP(hipStreamSynchronize(s));
     return SG_OK;
@@ -478,21 +592,15 @@ int sg_section_map_psk(const double *sv, int L, int M, int K, const double *cons
                        int32_t *sym) {
     SG_CHECK_ARG(sv && idx && L >= 0 && M > 0, "bad arguments");
     SG_CHECK_ARG(psk_order_ok(K) && (K == 1 || (constel && sym)), "K must be 1 or a power of two with its constellation");
-    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    SG_TRY(psk_max_check(K));
     if (L == 0) return SG_OK;
     SG_TRY(ensure_device());
     hipStream_t s = lib_stream();
-    const size_t N = (size_t)L * M;
-    std::vector<cxd> hs(N);
-    for (size_t i = 0; i < N; ++i) hs[i] = s_is_complex ? cxd{sv[2 * i], sv[2 * i + 1]} : cxd{sv[i], 0.0};
     std::vector<int32_t> hsym(L);
-    DevMem mem;
-    SG_TRY(mem.ensure((N + CAMP_MAX_K) * sizeof(cxd) + 2 * (size_t)L * sizeof(int32_t)));
-    cxd *d = mem.at<cxd>(), *dc = d + N;
-    int32_t *di = (int32_t *)(dc + CAMP_MAX_K), *dsym = di + L;
-    SG_HIP(hipMemcpyAsync(d, hs.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
-    if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
-    SG_TRY(camp_launch_map(d, L, M, K, dc, di, dsym, s));
+    SectionStage st;
+    SG_TRY(st.upload(sv, (size_t)L * M, s_is_complex, K, constel, 2 * (size_t)L * sizeof(int32_t), s));
+    int32_t *di = (int32_t *)st.res, *dsym = di + L;
+    SG_TRY(camp_launch_map(st.d, L, M, K, st.dc, di, dsym, s));
     SG_HIP(hipMemcpyAsync(idx, di, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     SG_HIP(hipMemcpyAsync(hsym.data(), dsym, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     SG_HIP(hipStreamSynchronize(s));
@@ -523,9 +631,7 @@ static int camp_llr_checks(sg_camp_plan *p, int B, int K, const double *constel,
                  nl, p->L);
     SG_CHECK_ARG(p->M >= 2, "section size M = %d must be a power of two >= 2", p->M);
     if (p->M > 2048) return fail(SG_ERR_UNSUPPORTED, "bit LLRs of sections of M = %d > 2048 entries", p->M);
-    int per = 0;
-    while ((1 << per) < p->M) ++per;
-    for (int k = 1; k < K; k <<= 1) ++per;
+    const int per = bits_per_section(p->M, K);
     SG_CHECK_ARG(llr_ld >= (long long)nl * per, "llr_ld = %lld < nl (log2 M + log2 K) = %lld", llr_ld,
                  (long long)nl * per);
     *per_out = per;
@@ -573,24 +679,16 @@ int sg_section_llr_psk(const double *x, int L, int M, int K, const double *const
     SG_CHECK_ARG(x && out && L >= 0, "bad arguments");
     SG_CHECK_ARG(M >= 2 && (M & (M - 1)) == 0, "section size M = %d must be a power of two >= 2", M);
     SG_CHECK_ARG(psk_order_ok(K) && (K == 1 || constel), "K must be 1 or a power of two with its constellation");
-    if (K > CAMP_MAX_K) return fail(SG_ERR_UNSUPPORTED, "K=%d-PSK: at most %d symbols are supported", K, CAMP_MAX_K);
+    SG_TRY(psk_max_check(K));
     if (M > 2048) return fail(SG_ERR_UNSUPPORTED, "bit LLRs of sections of M = %d > 2048 entries", M);
     if (L == 0) return SG_OK;
     hipStream_t s = lib_stream();
-    int per = 0;
-    while ((1 << per) < M) ++per;
-    for (int k = 1; k < K; k <<= 1) ++per;
-    const size_t N = (size_t)L * M, nout = (size_t)L * per;
-    std::vector<cxd> hx(N);
-    for (size_t i = 0; i < N; ++i) hx[i] = x_is_complex ? cxd{x[2 * i], x[2 * i + 1]} : cxd{x[i], 0.0};
-    DevMem mem;
-    SG_TRY(mem.ensure((N + CAMP_MAX_K) * sizeof(cxd) + nout * sizeof(double)));
-    cxd *d = mem.at<cxd>(), *dc = d + N;
-    double *dout = (double *)(dc + CAMP_MAX_K);
-    SG_HIP(hipMemcpyAsync(d, hx.data(), N * sizeof(cxd), hipMemcpyHostToDevice, s));
-    if (K > 1) SG_HIP(hipMemcpyAsync(dc, constel, (size_t)K * sizeof(cxd), hipMemcpyHostToDevice, s));
+    const size_t nout = (size_t)L * bits_per_section(M, K);
+    SectionStage st;
+    SG_TRY(st.upload(x, (size_t)L * M, x_is_complex, K, constel, nout * sizeof(double), s));
+    double *dout = (double *)st.res;
     // one "codeword" of L sections, x given: no tau
-    SG_TRY(camp_launch_llr(d, nullptr, 1, L, 1, M, K, dc, 0, L, (int)nout, probs_only, dout, s));
+    SG_TRY(camp_launch_llr(st.d, nullptr, 1, L, 1, M, K, st.dc, 0, L, (int)nout, probs_only, dout, s));
     SG_HIP(hipMemcpyAsync(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost, s));
     SG_HIP(hipStreamSynchronize(s));
     return SG_OK;
@@ -617,112 +715,6 @@ int sg_psk_pack_sections_device(const int32_t *d_idx, const int32_t *d_sym, int 
     SG_CHECK_ARG(logK >= 0 && logK <= 30, "bad logK");
     SG_CHECK_ARG(logK == 0 || d_sym, "logK > 0 needs d_sym");
     return camp_launch_pack(d_idx, logK ? d_sym : nullptr, B, L, logK, d_word, pick_stream(stream));
-}
-
-// sg_camp_decode_device's loop with the known sections given (camp_partial.hip): iteration 0 runs the forward
-// transform of beta0 too, and has its own residual kernel.
-int sg_camp_decode_partial_device(sg_camp_plan *p, const void *d_y, int B, int K, const double *constel,
-                                  const int32_t *d_known_idx, const int32_t *d_known_sym, const int32_t *d_true_idx,
-                                  const int32_t *d_true_sym, double awgn_var, int t_max, double rtol, int phi_method,
-                                  int32_t *d_map_idx, int32_t *d_map_sym, int32_t *d_t_final, double *d_nmse,
-                                  double *d_psi, void *stream) {
-    SG_TRY(ensure_device());
-    SG_CHECK_ARG(p, "plan is NULL");
-    p->last_B = p->last_K = 0;  // the loop overwrites the state a decode left; s_keep is not refilled
-    SG_TRY(partial_checks(B, K, constel, awgn_var, t_max, rtol, phi_method));
-    if (B <= 0) return SG_OK;
-    SG_CHECK_ARG(d_y && d_known_idx, "d_y or d_known_idx is NULL");
-    SG_CHECK_ARG(K == 1 || d_known_sym, "K > 1 needs d_known_sym");
-    SG_CHECK_ARG(K == 1 || !d_true_idx || d_true_sym, "K > 1 with true_idx needs true_sym");
-    SG_HIP(hipSetDevice(p->device));
-    hipStream_t s = pick_stream(stream);
-    SG_TRY(ensure_ws(p, B, t_max));
-    SG_TRY(set_constel(p, K, constel, s));
-    const CampTables tb = tables(p);
-    CampBufs bf = bufs(p, B, K);
-    bf.y = (const cxd *)d_y;
-    bf.sec_idx = d_map_idx ? d_map_idx : p->sec_idx;
-    bf.sec_sym = d_map_sym ? d_map_sym : p->sec_sym;
-    bf.true_idx = d_true_idx;
-    bf.true_sym = (K > 1 && d_true_idx) ? d_true_sym : nullptr;
-    const int32_t *ksym = K > 1 ? d_known_sym : nullptr;
-    AmpScalars sc;
-    sc.psi = d_psi ? d_psi : p->psi; sc.psi_prev = p->psi_prev; sc.phi_prev = p->phi_prev; sc.gamma = p->gamma;
-    sc.bcoef = p->bco;
-    sc.nmse = d_nmse ? d_nmse : p->nmse; sc.t_final = d_t_final ? d_t_final : p->t_final;
-    AmpParams pr;
-    pr.W = p->dW; pr.awgn_var = awgn_var; pr.rtol = rtol;
-    pr.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
-    pr.phi_method = phi_method; pr.t_max = t_max;
-    SG_HIP(hipMemsetAsync(p->beta, 0, (size_t)B * p->LM * sizeof(cxd), s));
-    SG_HIP(hipMemsetAsync(bf.sec_idx, 0, sizeof(int32_t) * B * p->L, s));
-    SG_HIP(hipMemsetAsync(bf.sec_sym, 0, sizeof(int32_t) * B * p->L, s));
-    SG_TRY(camp_part_launch_init(tb, bf, sc, pr, d_known_idx, ksym, s));
-    std::vector<int32_t> act(B);
-    for (int t = 0; t < t_max - 1; ++t) {
-        SG_TRY(camp_launch_fft(tb, bf, false, s));
-        if (t == 0) SG_TRY(camp_part_launch_start(tb, bf, sc, pr, s));
-        else SG_TRY(camp_launch_control(tb, bf, sc, pr, 0, t, s));
-        SG_TRY(camp_launch_fft(tb, bf, true, s));
-        SG_TRY(camp_part_launch_eta(tb, bf, d_known_idx, ksym, s));
-        SG_TRY(camp_launch_control(tb, bf, sc, pr, 1, t, s));
-        if (t % 4 == 3 && t + 1 < t_max - 1) {  // skip the remaining launches once every codeword stopped
-            SG_HIP(hipMemcpyAsync(act.data(), p->active, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-            SG_HIP(hipStreamSynchronize(s));
-            int na = 0;
-            for (int b = 0; b < B; ++b) na += act[b] != 0;
-            if (na == 0) break;
-        }
-    }
-    return SG_OK;
-}
-
-// upload -> sg_camp_decode_partial_device on the plan's own buffers -> download
-int sg_camp_decode_partial(sg_camp_plan *p, const double *y, int B, int K, const double *constel,
-                           const int32_t *known_idx, const int32_t *known_sym, const int32_t *true_idx,
-                           const int32_t *true_sym, double awgn_var, int t_max, double rtol, int phi_method,
-                           int32_t *map_idx, int32_t *map_sym, int32_t *t_final, double *nmse, double *psi) {
-    SG_TRY(ensure_device());
-    SG_CHECK_ARG(p, "plan is NULL");
-    p->last_B = p->last_K = 0;
-    SG_TRY(partial_checks(B, K, constel, awgn_var, t_max, rtol, phi_method));
-    if (B <= 0) return SG_OK;
-    SG_CHECK_ARG(y && known_idx && map_idx && t_final && nmse && psi, "null host buffer");
-    SG_CHECK_ARG(K == 1 || (known_sym && map_sym), "K > 1 needs known_sym and map_sym");
-    SG_CHECK_ARG(K == 1 || !true_idx || true_sym, "K > 1 with true_idx needs true_sym");
-    const size_t nsec = (size_t)B * p->L;
-    for (size_t i = 0; i < nsec; ++i) {
-        SG_CHECK_ARG(known_idx[i] >= -1 && known_idx[i] < p->M, "known_idx[%zu] = %d outside [-1, %d)", i,
-                     (int)known_idx[i], p->M);
-        SG_CHECK_ARG(K == 1 || known_idx[i] < 0 || (known_sym[i] >= 0 && known_sym[i] < K),
-                     "known_sym[%zu] = %d outside [0, %d)", i, K > 1 ? (int)known_sym[i] : 0, K);
-        if (true_idx) {
-            SG_CHECK_ARG(true_idx[i] >= 0 && true_idx[i] < p->M, "true_idx out of range");
-            SG_CHECK_ARG(K == 1 || (true_sym[i] >= 0 && true_sym[i] < K), "true_sym out of range");
-        }
-    }
-    SG_HIP(hipSetDevice(p->device));
-    hipStream_t s = lib_stream();
-    SG_TRY(ensure_ws(p, B, t_max));
-    SG_TRY(ensure_known(p, B));
-    SG_HIP(hipMemcpyAsync(p->y, y, (size_t)B * p->n * sizeof(cxd), hipMemcpyHostToDevice, s));
-    SG_HIP(hipMemcpyAsync(p->known_idx, known_idx, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
-    if (K > 1) SG_HIP(hipMemcpyAsync(p->known_sym, known_sym, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
-    if (true_idx) {
-        SG_HIP(hipMemcpyAsync(p->true_idx, true_idx, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
-        if (K > 1) SG_HIP(hipMemcpyAsync(p->true_sym, true_sym, sizeof(int32_t) * nsec, hipMemcpyHostToDevice, s));
-    }
-    SG_TRY(sg_camp_decode_partial_device(p, p->y, B, K, constel, p->known_idx, p->known_sym,
-                                         true_idx ? p->true_idx : nullptr, (true_idx && K > 1) ? p->true_sym : nullptr,
-                                         awgn_var, t_max, rtol, phi_method, p->sec_idx, p->sec_sym, p->t_final, p->nmse,
-                                         p->psi, nullptr));
-    SG_HIP(hipMemcpyAsync(map_idx, p->sec_idx, sizeof(int32_t) * nsec, hipMemcpyDeviceToHost, s));
-    if (map_sym) SG_HIP(hipMemcpyAsync(map_sym, p->sec_sym, sizeof(int32_t) * nsec, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(t_final, p->t_final, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(nmse, p->nmse, sizeof(double) * B * t_max * p->Lc, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipMemcpyAsync(psi, p->psi, sizeof(double) * B * p->Lc, hipMemcpyDeviceToHost, s));
-    SG_HIP(hipStreamSynchronize(s));
-    return SG_OK;
 }
 
 int sg_psk_unpack_sections_device(const int32_t *d_word, int B, int L, int logK, int32_t *d_idx, int32_t *d_sym,

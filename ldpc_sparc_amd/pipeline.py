@@ -20,18 +20,25 @@ from .sparc_new import DenseDesign
 class ConcatPipeline:
     def __init__(self, L, M, n, P, L_unprotected, mults, ldpc=("802.11n", "1/2", 81), design_seed=0,
                  precision="f32", t_max=25, bp_dectype="sumprod2", bp_its=200, A=None):
-        self.L, self.M, self.n, self.P = int(L), int(M), int(n), float(P)
-        self.logM = int(np.log2(M))
-        self.L_unp, self.mults = int(L_unprotected), int(mults)
-        self.c = code(*ldpc)
-        assert (self.L - self.L_unp) * self.logM == self.mults * self.c.N, "protected sections must hold the blocks"
-        self.prec = {"f64": _native.SG_F64, "f32": _native.SG_F32}[precision]
-        self.dt = np.float64 if self.prec == _native.SG_F64 else np.float32
-        self.t_max, self.bp_dectype, self.bp_its = int(t_max), bp_dectype, int(bp_its)
+        self._init_common(L, M, n, P, int(np.log2(M)), 0, L_unprotected, mults, ldpc, precision, t_max, bp_dectype,
+                          bp_its)
         self.design = DenseDesign(A, P, L, M, n=n, seed=design_seed)
         self.plan = self.design.plan(self.prec)
         self.graph = self.c._device_graph()
         self.snp = float(np.sqrt(n * P / L))
+
+    def _init_common(self, L, M, n, P, logM, logK, L_unprotected, mults, ldpc, precision, t_max, bp_dectype, bp_its):
+        """What every pipeline holds whatever its design: the shape, the LDPC code, the precision and the
+        iteration counts.  A section carries bits_per_section = logM + logK bits."""
+        self.L, self.M, self.n, self.P = int(L), int(M), int(n), float(P)
+        self.logM, self.bits_per_section = logM, logM + logK
+        self.L_unp, self.mults = int(L_unprotected), int(mults)
+        self.c = code(*ldpc)
+        assert (self.L - self.L_unp) * self.bits_per_section == self.mults * self.c.N, \
+            "protected sections must hold the blocks"
+        self.prec = {"f64": _native.SG_F64, "f32": _native.SG_F32}[precision]
+        self.dt = np.float64 if self.prec == _native.SG_F64 else np.float32
+        self.t_max, self.bp_dectype, self.bp_its = int(t_max), bp_dectype, int(bp_its)
         self._cap = 0
 
     def _ensure(self, B):
@@ -105,21 +112,50 @@ class ConcatPipeline:
         self.B, self.awgn_var = B, float(awgn_var)
 
     def decode(self):
-        """One batch: returns nothing; counters accumulate in d_cnt."""
-        lib, c, B = _native.lib(), self.c, self.B
+        """One batch: returns nothing; counters accumulate in d_cnt.  The stages below, of which a subclass
+        overrides those that differ on its design or in its decoder."""
+        self._amp()
+        self._soft_output()
+        self._bp()
+        self._final_pass()
+        self._count()
+
+    def _amp(self):
+        """AMP on d_y; the section decisions into d_idx."""
+        lib, B = _native.lib(), self.B
         _native.check(lib.sg_dense_amp_device(self.plan, self.d_y.ptr, B, self.t_max, None, None, None))
-        d_beta, d_s = ct.c_void_p(), ct.c_void_p()
-        _native.check(lib.sg_dense_state_device(self.plan, ct.byref(d_beta), ct.byref(d_s)))
+        self._d_beta, d_s = ct.c_void_p(), ct.c_void_p()
+        _native.check(lib.sg_dense_state_device(self.plan, ct.byref(self._d_beta), ct.byref(d_s)))
         _native.check(lib.sg_dense_map_device(self.plan, d_s, B, self.d_idx.ptr, None))
-        ld = self.mults * c.N
-        _native.check(lib.sg_beta_to_llr_device(self.prec, d_beta, B, self.L, self.M, self.snp, self.L_unp,
-                                                self.L - self.L_unp, ld, 0, self.d_llr.ptr, None))
-        _native.check(lib.sg_ldpc_decode_device(self.graph, _native.DECTYPES[self.bp_dectype], self.prec,
-                                                self.d_llr.ptr, B * self.mults, self.bp_its, 0.7, self.d_app.ptr,
-                                                self.d_it.ptr, None))
-        _native.check(lib.sg_concat_count_errors_device(self.prec, self.d_idx.ptr, self.d_true.ptr, B, self.L,
-                                                        self.L_unp, self.logM, self.d_app.ptr, self.d_info.ptr,
-                                                        self.mults, c.N, c.K, self.d_cnt.ptr, None))
+
+    def _soft_output(self):
+        """The bit LLRs of the protected sections, from the state the AMP left, into d_llr."""
+        _native.check(_native.lib().sg_beta_to_llr_device(
+            self.prec, self._d_beta, self.B, self.L, self.M, self.snp, self.L_unp, self.L - self.L_unp,
+            self.mults * self.c.N, 0, self.d_llr.ptr, None))
+
+    def _bp(self):
+        """BP over every LDPC block of the batch: d_llr -> d_app, d_it."""
+        _native.check(_native.lib().sg_ldpc_decode_device(
+            self.graph, _native.DECTYPES[self.bp_dectype], self.prec, self.d_llr.ptr, self.B * self.mults, self.bp_its,
+            0.7, self.d_app.ptr, self.d_it.ptr, None))
+
+    def _final_pass(self):
+        """Nothing here; the three-stage decoders' AMP pass with the BP-decoded sections known."""
+
+    def _known_sections(self):
+        """d_known (a three-stage decoder's buffer): the hard decisions of every protected section whose LDPC
+        blocks stopped on their syndrome, -1 elsewhere."""
+        _native.check(_native.lib().sg_concat_known_sections_device(
+            self.prec, self.d_app.ptr, self.d_it.ptr, self.bp_its, self.B, self.mults, self.c.N, self.L, self.L_unp,
+            self.bits_per_section, self.d_known.ptr, None))
+
+    def _count(self, d_idx=None):
+        """d_cnt += the errors of the sections in d_idx (default: self.d_idx) and of the BP output in d_app."""
+        c = self.c
+        _native.check(_native.lib().sg_concat_count_errors_device(
+            self.prec, (self.d_idx if d_idx is None else d_idx).ptr, self.d_true.ptr, self.B, self.L, self.L_unp,
+            self.bits_per_section, self.d_app.ptr, self.d_info.ptr, self.mults, c.N, c.K, self.d_cnt.ptr, None))
 
     def reset_counts(self):
         self.d_cnt.zero()
@@ -157,14 +193,8 @@ class DctConcatPipeline(ConcatPipeline):
     def __init__(self, L, M, n, P, L_unprotected, mults, ldpc=("802.11n", "1/2", 81), design_seed=0,
                  precision="f32", t_max=25, rtol=1e-6, phi_method=1, bp_dectype="sumprod2", bp_its=200, op=None):
         from . import sparc
-        self.L, self.M, self.n, self.P = int(L), int(M), int(n), float(P)
-        self.logM = int(np.log2(M))
-        self.L_unp, self.mults = int(L_unprotected), int(mults)
-        self.c = code(*ldpc)
-        assert (self.L - self.L_unp) * self.logM == self.mults * self.c.N, "protected sections must hold the blocks"
-        self.prec = {"f64": _native.SG_F64, "f32": _native.SG_F32}[precision]
-        self.dt = np.float64 if self.prec == _native.SG_F64 else np.float32
-        self.t_max, self.bp_dectype, self.bp_its = int(t_max), bp_dectype, int(bp_its)
+        self._init_common(L, M, n, P, int(np.log2(M)), 0, L_unprotected, mults, ldpc, precision, t_max, bp_dectype,
+                          bp_its)
         self.rtol, self.phi_method = float(rtol), int(phi_method)
         if op is None:
             W = np.array(float(P))
@@ -175,25 +205,18 @@ class DctConcatPipeline(ConcatPipeline):
         self.op = op
         self.plan = op.plan(self.prec)
         self.graph = self.c._device_graph()
-        self._cap = 0
 
     def _encode(self, B):
         _native.check(_native.lib().sg_amp_encode_device(self.plan, self.d_true.ptr, B, self.d_x.ptr, None))
 
-    def decode(self):
-        """One batch: returns nothing; counters accumulate in d_cnt."""
-        lib, c, B = _native.lib(), self.c, self.B
-        _native.check(lib.sg_amp_decode_device(self.plan, self.d_y.ptr, B, None, self.awgn_var, self.t_max,
-                                               self.rtol, self.phi_method, self.d_idx.ptr, None, None, None, None))
-        ld = self.mults * c.N
-        _native.check(lib.sg_amp_llr_device(self.plan, B, self.L_unp, self.L - self.L_unp, ld, 0, self.d_llr.ptr,
-                                            None))
-        _native.check(lib.sg_ldpc_decode_device(self.graph, _native.DECTYPES[self.bp_dectype], self.prec,
-                                                self.d_llr.ptr, B * self.mults, self.bp_its, 0.7, self.d_app.ptr,
-                                                self.d_it.ptr, None))
-        _native.check(lib.sg_concat_count_errors_device(self.prec, self.d_idx.ptr, self.d_true.ptr, B, self.L,
-                                                        self.L_unp, self.logM, self.d_app.ptr, self.d_info.ptr,
-                                                        self.mults, c.N, c.K, self.d_cnt.ptr, None))
+    def _amp(self):
+        _native.check(_native.lib().sg_amp_decode_device(
+            self.plan, self.d_y.ptr, self.B, None, self.awgn_var, self.t_max, self.rtol, self.phi_method,
+            self.d_idx.ptr, None, None, None, None))
+
+    def _soft_output(self):
+        _native.check(_native.lib().sg_amp_llr_device(self.plan, self.B, self.L_unp, self.L - self.L_unp,
+                                                      self.mults * self.c.N, 0, self.d_llr.ptr, None))
 
 
 class DctConcat3Pipeline(DctConcatPipeline):
@@ -223,26 +246,11 @@ class DctConcat3Pipeline(DctConcatPipeline):
         super()._ensure(B)
         self.d_known = _native.DeviceBuffer(B * self.L * 4)
 
-    def decode(self):
-        """One batch: returns nothing; counters accumulate in d_cnt."""
-        lib, c, B = _native.lib(), self.c, self.B
-        _native.check(lib.sg_amp_decode_device(self.plan, self.d_y.ptr, B, None, self.awgn_var, self.t_max,
-                                               self.rtol, self.phi_method, self.d_idx.ptr, None, None, None, None))
-        ld = self.mults * c.N
-        _native.check(lib.sg_amp_llr_device(self.plan, B, self.L_unp, self.L - self.L_unp, ld, 0, self.d_llr.ptr,
-                                            None))
-        _native.check(lib.sg_ldpc_decode_device(self.graph, _native.DECTYPES[self.bp_dectype], self.prec,
-                                                self.d_llr.ptr, B * self.mults, self.bp_its, 0.7, self.d_app.ptr,
-                                                self.d_it.ptr, None))
-        _native.check(lib.sg_concat_known_sections_device(self.prec, self.d_app.ptr, self.d_it.ptr, self.bp_its, B,
-                                                          self.mults, c.N, self.L, self.L_unp, self.logM,
-                                                          self.d_known.ptr, None))
-        _native.check(lib.sg_amp_decode_partial_device(self.plan, self.d_y.ptr, B, self.d_known.ptr, None,
-                                                       self.awgn_var, self.final_t_max, self.rtol, self.phi_method,
-                                                       self.d_idx.ptr, None, None, None, None))
-        _native.check(lib.sg_concat_count_errors_device(self.prec, self.d_idx.ptr, self.d_true.ptr, B, self.L,
-                                                        self.L_unp, self.logM, self.d_app.ptr, self.d_info.ptr,
-                                                        self.mults, c.N, c.K, self.d_cnt.ptr, None))
+    def _final_pass(self):
+        self._known_sections()
+        _native.check(_native.lib().sg_amp_decode_partial_device(
+            self.plan, self.d_y.ptr, self.B, self.d_known.ptr, None, self.awgn_var, self.final_t_max, self.rtol,
+            self.phi_method, self.d_idx.ptr, None, None, None, None))
 
 
 class DctIntegratedPipeline(DctConcatPipeline):
@@ -280,9 +288,7 @@ class DctIntegratedPipeline(DctConcatPipeline):
             self.plan, self.graph, _native.INTEGRATED_MODES[self.mode], c.K, self.d_y.ptr, B, self.t_max,
             self.bp_its_inner, self.bp_its_final, self.d_bits.ptr, self.d_app.ptr, None, None))
         # no unprotected section: the section-index arguments carry no bits (valid buffers all the same)
-        _native.check(lib.sg_concat_count_errors_device(self.prec, self.d_true.ptr, self.d_true.ptr, B, self.L, 0,
-                                                        self.logM, self.d_app.ptr, self.d_info.ptr, self.mults, c.N,
-                                                        c.K, self.d_cnt.ptr, None))
+        self._count(self.d_true)
 
 
 class CsparcConcatPipeline(ConcatPipeline):
@@ -311,17 +317,11 @@ class CsparcConcatPipeline(ConcatPipeline):
         from . import sparc
         if precision != "f64":
             raise NotImplementedError("complex SPARCs run in double precision only (precision='f64')")
-        self.L, self.M, self.K, self.n, self.P = int(L), int(M), int(K), int(n), float(P)
+        self.K = int(K)
         sparc._check_psk(self.K)
-        self.logM = int(round(np.log2(self.M)))
         self.logK = int(round(np.log2(self.K)))
-        self.bits_per_section = self.logM + self.logK
-        self.L_unp, self.mults = int(L_unprotected), int(mults)
-        self.c = code(*ldpc)
-        assert (self.L - self.L_unp) * self.bits_per_section == self.mults * self.c.N, \
-            "protected sections must hold the blocks"
-        self.prec, self.dt = _native.SG_F64, np.float64
-        self.t_max, self.bp_dectype, self.bp_its = int(t_max), bp_dectype, int(bp_its)
+        self._init_common(L, M, n, P, int(round(np.log2(int(M)))), self.logK, L_unprotected, mults, ldpc, precision,
+                          t_max, bp_dectype, bp_its)
         self.rtol, self.phi_method = float(rtol), int(phi_method)
         if op is None:
             W = np.array(float(P))
@@ -334,7 +334,6 @@ class CsparcConcatPipeline(ConcatPipeline):
         self.plan = op.plan()
         op.soft_output(True)
         self.graph = self.c._device_graph()
-        self._cap = 0
 
     def _ensure(self, B):
         if B <= self._cap:
@@ -420,33 +419,21 @@ class CsparcConcatPipeline(ConcatPipeline):
                                          float(np.sqrt(awgn_var / 2)), self.d_y.ptr, None))
         self.B, self.awgn_var = B, float(awgn_var)
 
-    def _decode_to_bp(self):
-        """AMP, section words, soft output and BP of one batch: d_idx, d_app and d_it."""
-        lib, c, B = _native.lib(), self.c, self.B
-        cs = _native.ptr(self.constel)
-        _native.check(lib.sg_camp_decode_device(self.plan, self.d_y.ptr, B, self.K, cs, None, None, self.awgn_var,
-                                                self.t_max, self.rtol, self.phi_method, self.d_midx.ptr,
-                                                self.d_msym.ptr, None, None, None, None))
-        _native.check(lib.sg_psk_pack_sections_device(self.d_midx.ptr, self.d_msym.ptr, B, self.L, self.logK,
-                                                      self.d_idx.ptr, None))
-        ld = self.mults * c.N
-        _native.check(lib.sg_camp_llr_device(self.plan, B, self.K, cs, self.L_unp, self.L - self.L_unp, ld, 0,
-                                             self.d_llr.ptr, None))
-        _native.check(lib.sg_ldpc_decode_device(self.graph, _native.DECTYPES[self.bp_dectype], self.prec,
-                                                self.d_llr.ptr, B * self.mults, self.bp_its, 0.7, self.d_app.ptr,
-                                                self.d_it.ptr, None))
+    def _pack_map(self):
+        """d_idx: the section words of the MAP (location, symbol) pairs in d_midx / d_msym."""
+        _native.check(_native.lib().sg_psk_pack_sections_device(self.d_midx.ptr, self.d_msym.ptr, self.B, self.L,
+                                                                self.logK, self.d_idx.ptr, None))
 
-    def _count(self):
-        """d_cnt += the errors of the section words in d_idx and of the BP output in d_app."""
-        c = self.c
-        _native.check(_native.lib().sg_concat_count_errors_device(
-            self.prec, self.d_idx.ptr, self.d_true.ptr, self.B, self.L, self.L_unp, self.bits_per_section,
-            self.d_app.ptr, self.d_info.ptr, self.mults, c.N, c.K, self.d_cnt.ptr, None))
+    def _amp(self):
+        _native.check(_native.lib().sg_camp_decode_device(
+            self.plan, self.d_y.ptr, self.B, self.K, _native.ptr(self.constel), None, None, self.awgn_var, self.t_max,
+            self.rtol, self.phi_method, self.d_midx.ptr, self.d_msym.ptr, None, None, None, None))
+        self._pack_map()
 
-    def decode(self):
-        """One batch: returns nothing; counters accumulate in d_cnt."""
-        self._decode_to_bp()
-        self._count()
+    def _soft_output(self):
+        _native.check(_native.lib().sg_camp_llr_device(
+            self.plan, self.B, self.K, _native.ptr(self.constel), self.L_unp, self.L - self.L_unp,
+            self.mults * self.c.N, 0, self.d_llr.ptr, None))
 
 
 class CsparcConcat3Pipeline(CsparcConcatPipeline):
@@ -477,19 +464,13 @@ class CsparcConcat3Pipeline(CsparcConcatPipeline):
         self.d_kidx = _native.DeviceBuffer(B * self.L * 4)
         self.d_ksym = _native.DeviceBuffer(B * self.L * 4)
 
-    def decode(self):
-        """One batch: returns nothing; counters accumulate in d_cnt."""
-        lib, c, B = _native.lib(), self.c, self.B
-        self._decode_to_bp()
-        _native.check(lib.sg_concat_known_sections_device(self.prec, self.d_app.ptr, self.d_it.ptr, self.bp_its, B,
-                                                          self.mults, c.N, self.L, self.L_unp, self.bits_per_section,
-                                                          self.d_known.ptr, None))
+    def _final_pass(self):
+        lib, B = _native.lib(), self.B
+        self._known_sections()
         _native.check(lib.sg_psk_unpack_sections_device(self.d_known.ptr, B, self.L, self.logK, self.d_kidx.ptr,
                                                         self.d_ksym.ptr, None))
         _native.check(lib.sg_camp_decode_partial_device(self.plan, self.d_y.ptr, B, self.K, _native.ptr(self.constel),
                                                         self.d_kidx.ptr, self.d_ksym.ptr, None, None, self.awgn_var,
                                                         self.final_t_max, self.rtol, self.phi_method, self.d_midx.ptr,
                                                         self.d_msym.ptr, None, None, None, None))
-        _native.check(lib.sg_psk_pack_sections_device(self.d_midx.ptr, self.d_msym.ptr, B, self.L, self.logK,
-                                                      self.d_idx.ptr, None))
-        self._count()
+        self._pack_map()

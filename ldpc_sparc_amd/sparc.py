@@ -687,6 +687,31 @@ def operator_of(Ab, Az):
 # ------------------------------------------------------------------ AMP
 
 
+def _received_words(Y, op, dtype):
+    """Y as a contiguous [B, n] array of dtype; returns (Y, B)."""
+    Y = np.ascontiguousarray(Y, dtype=dtype)
+    if Y.ndim != 2 or Y.shape[1] != op.n:
+        raise ValueError(f"received words must have shape [B, {op.n}]")
+    return Y, Y.shape[0]
+
+
+def _known_sections(a, name, B, op):
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if a.shape != (B, op.L):
+        raise ValueError(f"{name} must have shape [{B}, {op.L}]")
+    return a
+
+
+def _true_sections(a, B, op):
+    return np.ascontiguousarray(a, dtype=np.int32).reshape(B, op.L)
+
+
+def _decode_outputs(B, op, t_max):
+    """(map_idx [B, L], t_final [B], nmse [B, t_max, Lc], psi [B, Lc]) for a decoder to fill."""
+    return (np.empty((B, op.L), dtype=np.int32), np.empty(B, dtype=np.int32), np.empty((B, t_max, op.Lc)),
+            np.empty((B, op.Lc)))
+
+
 def amp_decode_batch(Y, op, awgn_var, t_max, rtol=1e-6, phi_est_method=1, true_idx=None,
                      precision=_native.SG_F64):
     """Batched AMP on the GPU for codewords sharing one design.
@@ -694,17 +719,9 @@ def amp_decode_batch(Y, op, awgn_var, t_max, rtol=1e-6, phi_est_method=1, true_i
     Y [B, n] received words; true_idx [B, L] transmitted section indices (for
     NMSE) or None.  Returns (map_idx [B, L], t_final [B], nmse [B, t_max, Lc],
     psi [B, Lc])."""
-    Y = np.ascontiguousarray(Y, dtype=np.float64)
-    if Y.ndim != 2 or Y.shape[1] != op.n:
-        raise ValueError(f"received words must have shape [B, {op.n}]")
-    B = Y.shape[0]
-    ti = None
-    if true_idx is not None:
-        ti = np.ascontiguousarray(true_idx, dtype=np.int32).reshape(B, op.L)
-    map_idx = np.empty((B, op.L), dtype=np.int32)
-    t_final = np.empty(B, dtype=np.int32)
-    nmse = np.empty((B, t_max, op.Lc))
-    psi = np.empty((B, op.Lc))
+    Y, B = _received_words(Y, op, np.float64)
+    ti = None if true_idx is None else _true_sections(true_idx, B, op)
+    map_idx, t_final, nmse, psi = _decode_outputs(B, op, t_max)
     _native.check(_native.lib().sg_amp_decode(
         op.plan(precision), _native.ptr(Y), B, _native.ptr(ti), float(awgn_var), int(t_max),
         float(rtol), int(phi_est_method), _native.ptr(map_idx), _native.ptr(t_final),
@@ -724,20 +741,10 @@ def amp_decode_partial_batch(Y, op, known_idx, awgn_var, t_max, rtol=1e-6, phi_e
     [B, L], t_final [B], nmse [B, t_max, Lc], psi [B, Lc])."""
     if op.csparc:
         raise NotImplementedError("AMP with known sections is implemented for real (DCT design) SPARCs only")
-    Y = np.ascontiguousarray(Y, dtype=np.float64)
-    if Y.ndim != 2 or Y.shape[1] != op.n:
-        raise ValueError(f"received words must have shape [B, {op.n}]")
-    B = Y.shape[0]
-    known = np.ascontiguousarray(known_idx, dtype=np.int32)
-    if known.shape != (B, op.L):
-        raise ValueError(f"known_idx must have shape [{B}, {op.L}]")
-    ti = None
-    if true_idx is not None:
-        ti = np.ascontiguousarray(true_idx, dtype=np.int32).reshape(B, op.L)
-    map_idx = np.empty((B, op.L), dtype=np.int32)
-    t_final = np.empty(B, dtype=np.int32)
-    nmse = np.empty((B, t_max, op.Lc))
-    psi = np.empty((B, op.Lc))
+    Y, B = _received_words(Y, op, np.float64)
+    known = _known_sections(known_idx, "known_idx", B, op)
+    ti = None if true_idx is None else _true_sections(true_idx, B, op)
+    map_idx, t_final, nmse, psi = _decode_outputs(B, op, t_max)
     _native.check(_native.lib().sg_amp_decode_partial(
         op.plan(precision), _native.ptr(Y), B, _native.ptr(known), _native.ptr(ti), float(awgn_var), int(t_max),
         float(rtol), int(phi_est_method), _native.ptr(map_idx), _native.ptr(t_final), _native.ptr(nmse),
@@ -761,6 +768,28 @@ def amp_llr(op, B, l0, nl, probs_only=False, precision=_native.SG_F64):
     return out
 
 
+def _camp_decode(Y, op, known, awgn_var, t_max, rtol, phi_est_method, K, true_idx, true_sym):
+    """camp_decode_batch (known None) and camp_decode_partial_batch (known = (known_idx, known_sym)) after their
+    own refusals."""
+    Y, B = _received_words(Y, op, np.complex128)
+    if known is not None:
+        ki = _known_sections(known[0], "known_idx", B, op)
+        ks = _known_sections(known[1], "known_sym", B, op) if K != 1 else None
+    ti = None if true_idx is None else _true_sections(true_idx, B, op)
+    ts = _true_sections(true_sym, B, op) if ti is not None and K != 1 else None
+    map_idx, t_final, nmse, psi = _decode_outputs(B, op, t_max)
+    map_sym = np.zeros((B, op.L), dtype=np.int32)
+    c = _interleaved(psk_constel(K)) if K != 1 else None
+    head = (op.plan(), _native.ptr(Y), B, int(K), _native.ptr(c))
+    tail = (_native.ptr(ti), _native.ptr(ts), float(awgn_var), int(t_max), float(rtol), int(phi_est_method),
+            _native.ptr(map_idx), _native.ptr(map_sym), _native.ptr(t_final), _native.ptr(nmse), _native.ptr(psi))
+    if known is None:
+        _native.check(_native.lib().sg_camp_decode(*head, *tail))
+    else:
+        _native.check(_native.lib().sg_camp_decode_partial(*head, _native.ptr(ki), _native.ptr(ks), *tail))
+    return map_idx, map_sym, t_final, nmse, psi
+
+
 def camp_decode_batch(Y, op, awgn_var, t_max, rtol=1e-6, phi_est_method=1, K=1, true_idx=None, true_sym=None):
     """Batched AMP on the GPU for complex codewords sharing one complex design.
 
@@ -769,26 +798,7 @@ def camp_decode_batch(Y, op, awgn_var, t_max, rtol=1e-6, phi_est_method=1, K=1, 
     (for NMSE) or None.  Returns (map_idx [B, L], map_sym [B, L], t_final [B],
     nmse [B, t_max, Lc], psi [B, Lc])."""
     _check_psk(K)
-    Y = np.ascontiguousarray(Y, dtype=np.complex128)
-    if Y.ndim != 2 or Y.shape[1] != op.n:
-        raise ValueError(f"received words must have shape [B, {op.n}]")
-    B = Y.shape[0]
-    ti = ts = None
-    if true_idx is not None:
-        ti = np.ascontiguousarray(true_idx, dtype=np.int32).reshape(B, op.L)
-        if K != 1:
-            ts = np.ascontiguousarray(true_sym, dtype=np.int32).reshape(B, op.L)
-    map_idx = np.empty((B, op.L), dtype=np.int32)
-    map_sym = np.zeros((B, op.L), dtype=np.int32)
-    t_final = np.empty(B, dtype=np.int32)
-    nmse = np.empty((B, t_max, op.Lc))
-    psi = np.empty((B, op.Lc))
-    c = _interleaved(psk_constel(K)) if K != 1 else None
-    _native.check(_native.lib().sg_camp_decode(
-        op.plan(), _native.ptr(Y), B, int(K), _native.ptr(c), _native.ptr(ti), _native.ptr(ts), float(awgn_var),
-        int(t_max), float(rtol), int(phi_est_method), _native.ptr(map_idx), _native.ptr(map_sym),
-        _native.ptr(t_final), _native.ptr(nmse), _native.ptr(psi)))
-    return map_idx, map_sym, t_final, nmse, psi
+    return _camp_decode(Y, op, None, awgn_var, t_max, rtol, phi_est_method, K, true_idx, true_sym)
 
 
 def camp_decode_partial_batch(Y, op, known_idx, known_sym, awgn_var, t_max, rtol=1e-6, phi_est_method=1, K=1,
@@ -807,34 +817,7 @@ def camp_decode_partial_batch(Y, op, known_idx, known_sym, awgn_var, t_max, rtol
         raise ValueError("camp_decode_partial_batch needs a ComplexDesignOperator (real designs: "
                          "amp_decode_partial_batch)")
     _check_psk(K)
-    Y = np.ascontiguousarray(Y, dtype=np.complex128)
-    if Y.ndim != 2 or Y.shape[1] != op.n:
-        raise ValueError(f"received words must have shape [B, {op.n}]")
-    B = Y.shape[0]
-    ki = np.ascontiguousarray(known_idx, dtype=np.int32)
-    if ki.shape != (B, op.L):
-        raise ValueError(f"known_idx must have shape [{B}, {op.L}]")
-    ks = None
-    if K != 1:
-        ks = np.ascontiguousarray(known_sym, dtype=np.int32)
-        if ks.shape != (B, op.L):
-            raise ValueError(f"known_sym must have shape [{B}, {op.L}]")
-    ti = ts = None
-    if true_idx is not None:
-        ti = np.ascontiguousarray(true_idx, dtype=np.int32).reshape(B, op.L)
-        if K != 1:
-            ts = np.ascontiguousarray(true_sym, dtype=np.int32).reshape(B, op.L)
-    map_idx = np.empty((B, op.L), dtype=np.int32)
-    map_sym = np.zeros((B, op.L), dtype=np.int32)
-    t_final = np.empty(B, dtype=np.int32)
-    nmse = np.empty((B, t_max, op.Lc))
-    psi = np.empty((B, op.Lc))
-    c = _interleaved(psk_constel(K)) if K != 1 else None
-    _native.check(_native.lib().sg_camp_decode_partial(
-        op.plan(), _native.ptr(Y), B, int(K), _native.ptr(c), _native.ptr(ki), _native.ptr(ks), _native.ptr(ti),
-        _native.ptr(ts), float(awgn_var), int(t_max), float(rtol), int(phi_est_method), _native.ptr(map_idx),
-        _native.ptr(map_sym), _native.ptr(t_final), _native.ptr(nmse), _native.ptr(psi)))
-    return map_idx, map_sym, t_final, nmse, psi
+    return _camp_decode(Y, op, (known_idx, known_sym), awgn_var, t_max, rtol, phi_est_method, K, true_idx, true_sym)
 
 
 def camp_llr(op, B, K, l0, nl, probs_only=False):
