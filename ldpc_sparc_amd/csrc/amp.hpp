@@ -244,6 +244,7 @@ struct Cw2Tables {
     const uint32_t *cls_ls;   // [Mc] padded real LDS index | section << 16
     const uint32_t *cls2;     // [Q][9216] cls_ls of each class padded to 9216 entries with CW2_TRASH
     const uint32_t *clsp;     // [Q][4608] image positions of entries q and q + 4608 of cls2 (low, high half)
+    const uint32_t *clss;     // [Q][4608] sections of the same two entries (cw2_az recomputes beta_prev from s)
     const int32_t *qpos;      // [Mc]
     const uint16_t *seg;      // [Q][Lblk+1]
     float *xr;                // [B][2][OT][512] each half's part of Re(c1 H[a] + c2 conj H[b]) per output

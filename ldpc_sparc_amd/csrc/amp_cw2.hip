@@ -3,7 +3,7 @@
 // operators of sub_dct, sparc.py:648-701) per codeword as four launches:
 //
 //   cw2_ab    (2 B workgroups)  half h of the Q classes: beta of the class
-//             (from s and the section statistics) -> LDS scatter -> P-point
+//             (from s and the section statistics; s is only read) -> LDS scatter -> P-point
 //             FFT -> for every output i owned by the thread:
 //                 H[a]      += W Y_m2[r],
 //                 conj H[b] += W conj Y_m2[P - r],   W = w_N2^(m2 a), r = a mod P
@@ -14,7 +14,9 @@
 //   cw2_az    (2 B)  half h of the classes: rows r and P - r of each owned
 //             conjugate pair from the outputs' al z/phi conj(W) and be z/phi W
 //             -> inverse P-point FFT -> s = beta_prev + tau u (sparc.py:972) in
-//             class order -> per-section partial (max, sums without the max).
+//             class order, beta_prev recomputed from the old s, the section
+//             statistics and the previous tau exactly as cw2_ab computed it
+//             -> per-section partial (max, sums without the max).
 //   cw2_merge (B)  the two halves' section statistics -> max, 1/sum, psi,
 //             NMSE, early stop (sparc.py:973-988).
 //
@@ -89,6 +91,10 @@ __device__ __forceinline__ cx<float> c2_w(const Cw2Tables &tb, uint32_t j) {
 typedef float c2f __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) c2f c2lds;
 __device__ __forceinline__ c2lds *c2_at(int pos) { return (c2lds *)(size_t)(8u * (uint32_t)pos); }
+// beta = eta(s) of one entry (sparc.py:429-432) from its section's (max, 1 / sum) and log2 e / tau: a
+// subtraction, a multiply, v_exp_f32, a multiply, nothing here for the compiler to contract.  cw2_ab scatters
+// it and cw2_az recomputes it as beta_prev from the same operands, so the two are the same bits.
+__device__ __forceinline__ float c2_beta(float s, c2f mi, float inv_tp) { return c2_exp2((s - mi.x) * inv_tp) * mi.y; }
 // complex index of the first radix-16 stage's twiddle table (after the image,
 // the staged statistics and the trash slot): w_512^(r k) at (r - 1) 32 + k,
 // r = 1..15, k < 32, forward or (cw2_az) inverse
@@ -318,6 +324,12 @@ __device__ __forceinline__ const int *c2_stage_cp(unsigned char *smem, const Cw2
 }
 static_assert(C2_TW1 * 8 == C2_IMG_BYTES + 2 * 1024 * 4 + 16, "twiddle table after the trash slot");
 static_assert(CW2_TRASH == (C2_IMG_BYTES + 2 * 1024 * 4) / 4, "trash slot after the staged statistics");
+// cw2_az stages the same statistics one element further on: its rows write row P of the r = 0 pair at
+// c2pos(P), the first 8 bytes after the image.  The last section then lies on the first half of the trash
+// slot, which cw2_az only ever reads (the gathers of a slice's padding entries).
+constexpr uint32_t C2_AZ_MI_BYTES = (uint32_t)C2_IMG_BYTES + 8;
+static_assert(C2_AZ_MI_BYTES == 8u * (uint32_t)c2pos(C2_P) + 8, "behind row P of the r = 0 pair");
+static_assert(C2_AZ_MI_BYTES + 1024 * 8 <= C2_TW1 * 8, "the staged statistics end before the stage twiddles");
 
 // (the class slices go through raw buffer resources, device_util.hpp: their ragged ends need no clamps)
 constexpr int C2_SN = C2_NC * C2_SC;  // class entries per thread
@@ -336,7 +348,7 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
         sMI[l] = c2f{bf.stM[lb + l], bf.stI[lb + l]};
     }
     const float inv_tp = (float)(C2_LOG2E / bf.tau[cw]);  // log2 e / tau (c2_exp2)
-    float *s = bf.s + (size_t)cw * tb.LM;  // s in; beta out (read by cw2_az, which writes the new s)
+    const float *s = bf.s + (size_t)cw * tb.LM;  // read-only here (cw2_az reads it again, then writes the new s)
     cx<float> Ha[OT], Hb[OT];  // H[a], conj H[b] of the thread's outputs over this half's classes
 #pragma unroll
     for (int j = 0; j < OT; ++j) Ha[j] = Hb[j] = {0.f, 0.f};
@@ -404,18 +416,14 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_ab(Cw2Tables tb, RegBufs<float> b
             __syncthreads();  // the image is read before the scatter overwrites it
         }
         C2_TPC(8);
-        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(s + q0, 4 * (q1 - q0));
 #pragma unroll
-        for (int c = 0; c < C2_NC; ++c) {  // beta = eta(s), sparc.py:429-432, scattered into the image and
-                                           // stored over s for cw2_az (its beta_prev; past the end: dropped)
+        for (int c = 0; c < C2_NC; ++c) {  // beta = eta(s), sparc.py:429-432, scattered into the image (s stays:
+                                           // cw2_az recomputes this beta from it, c2_beta; no vector-memory
+                                           // store in the class loop)
 #pragma unroll
             for (int i = c * C2_SC; i < (c + 1) * C2_SC; ++i) {
                 const int sec = e[i] >> 16;
-                const c2f mi = sMI[sec];
-                v[i] = c2_exp2((v[i] - mi.x) * inv_tp) * mi.y;
-                dr[e[i] & 0xffffu] = v[i];
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v[i]), rs, 4 * tl + 4 * i * C2_T,
-                                                      0, 0);
+                dr[e[i] & 0xffffu] = c2_beta(v[i], sMI[sec], inv_tp);
             }
             C2_TPC(1 + c);
         }
@@ -597,6 +605,16 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
     const bool have_beta = t > 0;
     const double tv = bf.tau[cw];
     const float tau = (float)tv, inv_tau = (float)(C2_LOG2E / tv);  // log2 e / tau (c2_exp2)
+    // beta_prev = eta(s) is recomputed here as cw2_ab(t) computed it (c2_beta), from operands that are all
+    // still what cw2_ab read: s (cw2_ab only reads it), the section statistics (cw2_merge(t) replaces them
+    // after this kernel) and the tau that cw2_ctrl(t) saved before replacing it.  cw2_ab storing beta over s
+    // for this kernel to read back was 4 LM bytes written per codeword-iteration and 18 vector-memory stores
+    // per thread and class in cw2_ab's loop, which every wait for its next prefetched slice also waited for.
+    const float inv_tp = have_beta ? (float)(C2_LOG2E / bf.tau_prev[cw]) : 0.f;
+    const c2lds *sMI = (const c2lds *)(size_t)C2_AZ_MI_BYTES;  // (section max, 1 / sum), as cw2_ab stages them
+    if (have_beta)
+        for (int l = tid; l < tb.L; l += C2_T)
+            *(c2lds *)(size_t)(C2_AZ_MI_BYTES + 8u * (uint32_t)l) = c2f{bf.stM[lb + l], bf.stI[lb + l]};
     float *s = bf.s + (size_t)cw * tb.LM;
     constexpr int OTP = cw2_otp(OT);
     // z / phi [512][OTP] thread-major (scaled here by (|al|, |be|) from the plan's thread-major table, shared by
@@ -617,13 +635,16 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
     const int Qh = tb.Q / tb.np;
     c2_tw1_init<true>(tid);
     const int *cpl = c2_stage_cp(smem, tb, tid);
+    const uint32_t rmk0 = tb.cmask[tb.Q * C2_T + tid];  // the rows' first-stage mask: the same for every class
     __syncthreads();  // the staged statistics
     C2_TP(42);
     for (int m2 = h * Qh; m2 < (h + 1) * Qh; ++m2) {
         const int tl = opaque(tid);
         C2_TPC(32);
-        const uint32_t rmk = tb.cmask[tb.Q * C2_T + tl];
-        // the class slice (entries' image positions, beta_prev), requested before the transform and
+        // (opaque per class: otherwise the first stage's 32 bit extracts of it are hoisted with it and held
+        // in as many VGPRs across the loop)
+        const uint32_t rmk = (uint32_t)opaque((int)rmk0);
+        // the class slice (entries' image positions, the old s), requested before the transform and
         // consumed after it, so its HBM latency hides behind the transform
         const int q0 = uni(cpl[m2]), q1 = uni(cpl[m2 + 1]);
         const __amdgpu_buffer_rsrc_t rs = buf_rsrc(s + q0, 4 * (q1 - q0));  // past the class's end: reads 0,
@@ -633,7 +654,7 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
         constexpr bool EARLY = OT <= 12;
         float v[C2_SN];
         uint32_t e[C2_SN / 2];
-        auto load_slice = [&]() {  // the entries' positions and beta_prev
+        auto load_slice = [&]() {  // the entries' positions and the old s
             // the entries' image positions two per word (clsp: entries i and i + 9 of the thread), half the
             // table loads and bytes of the full words (the sections are not needed here)
             const __amdgpu_buffer_rsrc_t re = buf_rsrc(tb.clsp + (size_t)m2 * (CW2_SLICE / 2), 2 * CW2_SLICE);
@@ -642,8 +663,10 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
                 const uint32_t w = buf_ldu(re, 4 * tl, 4 * i * C2_T);
                 e[i] = w;  // (packed: entries i and i + 9, unpacked at the gather -- 9 VGPRs across the transform)
             }
+            if (have_beta) {  // (t = 0: s holds nothing yet and there is no beta_prev)
 #pragma unroll
-            for (int i = 0; i < C2_SN; ++i) v[i] = buf_ldf(rs, 4 * tl + 4 * i * C2_T, 0);  // (t = 0: unused)
+                for (int i = 0; i < C2_SN; ++i) v[i] = buf_ldf(rs, 4 * tl + 4 * i * C2_T, 0);
+            }
         };
         {  // rows r and P - r of each owned pair: sum of al v conj(W) / be v W over its outputs
             // (v = z / phi).  Polar form (build_cw2): al conj(W) = |al| (cos x, sin x) and be W = |be| (sin x,
@@ -748,12 +771,32 @@ __global__ __launch_bounds__(C2_T, 4) void cw2_az(Cw2Tables tb, RegBufs<float> b
         C2_TPC(35);
         float snv[C2_SN];
         if constexpr (!EARLY) load_slice();
-        {
+        // s = beta_prev + tau u (sparc.py:972), one FMA on beta_prev rounded as cw2_ab rounded it.  The
+        // entries' sections (clss, packed as the positions are) are requested here and not with the slice:
+        // nine more VGPRs across the transform do not fit under the 128 of two workgroups per CU.  u is
+        // gathered while they are in flight.
+        if (have_beta) {
+            uint32_t es[C2_SN / 2];
+            const __amdgpu_buffer_rsrc_t rc = buf_rsrc(tb.clss + (size_t)m2 * (CW2_SLICE / 2), 2 * CW2_SLICE);
 #pragma unroll
-            for (int i = 0; i < C2_SN; ++i) {  // s = beta_prev + tau u (sparc.py:972); beta_prev stored by cw2_ab
-                const float b = have_beta ? v[i] : 0.f;
+            for (int i = 0; i < C2_SN / 2; ++i) es[i] = buf_ldu(rc, 4 * tl, 4 * i * C2_T);
+#pragma unroll
+            for (int c = 0; c < C2_NC; ++c) {  // (a chunk's gathers and statistics in registers at a time)
+                float u[C2_SC];
+#pragma unroll
+                for (int i = 0; i < C2_SC; ++i) u[i] = dr[c ? e[i] >> 16 : e[i] & 0xffffu];
+#pragma unroll
+                for (int i = 0; i < C2_SC; ++i) {
+                    const uint32_t sec = c ? es[i] >> 16 : es[i] & 0xffffu;
+                    snv[c * C2_SC + i] = __builtin_fmaf(u[i], tau, c2_beta(v[c * C2_SC + i], sMI[sec], inv_tp));
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < C2_SN; ++i) {
                 const uint32_t pos = i < C2_SN / 2 ? e[i] & 0xffffu : e[i - C2_SN / 2] >> 16;
-                snv[i] = b + tau * dr[pos];
+                snv[i] = __builtin_fmaf(dr[pos], tau, 0.f);
             }
         }
         C2_TPC(36);

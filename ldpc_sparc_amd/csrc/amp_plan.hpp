@@ -90,7 +90,8 @@ struct sg_amp_plan {
     // split per-codeword engine (amp_cw2.hip; build_cw2): outputs per thread (0 = not built) and its tables
     int cw2OT = 0;
     int c2_np = 2;                // f32 split engine: workgroups per codeword for the next launches (decode_regular)
-    uint32_t *c2_ka = nullptr, *c2_kat = nullptr, *c2_cmask = nullptr, *c2_cls = nullptr, *c2_clsp = nullptr;
+    uint32_t *c2_ka = nullptr, *c2_kat = nullptr, *c2_cmask = nullptr, *c2_cls = nullptr, *c2_clsp = nullptr,
+             *c2_clss = nullptr;
     int32_t *c2_oi = nullptr;
     void *c2_cf = nullptr;
     float *c2_gm = nullptr;  // [OT][512][2] (|al|, |be|) of the polar row form (build_cw2)

@@ -377,15 +377,18 @@ int build_cw2(sg_amp_plan *p, const uint32_t *o0, double sc, const std::vector<i
             cls2[(size_t)m2 * CW2_SLICE + (q - cls_ptr[m2])] = (cls_ls[q] & ~0xffffu) | pl;
         }
     SG_TRY(p->tables.upload(&p->c2_cls, cls2));
-    {  // image positions alone, two per word (cw2_az's gathers: entries tl + 512 i and tl + 512 (i + 9))
+    {  // image positions alone, two per word (cw2_az's gathers: entries tl + 512 i and tl + 512 (i + 9)), and
+       // the same entries' sections in a table of their own (cw2_az's beta_prev, requested after its transform)
         constexpr int H = CW2_SLICE / 2;
-        std::vector<uint32_t> clsp((size_t)Q * H);
+        std::vector<uint32_t> clsp((size_t)Q * H), clss((size_t)Q * H);
         for (int m2 = 0; m2 < Q; ++m2)
             for (int q = 0; q < H; ++q) {
                 const uint32_t *c = &cls2[(size_t)m2 * CW2_SLICE];
                 clsp[(size_t)m2 * H + q] = (c[q] & 0xffffu) | (c[q + H] << 16);
+                clss[(size_t)m2 * H + q] = (c[q] >> 16) | (c[q + H] & ~0xffffu);
             }
         SG_TRY(p->tables.upload(&p->c2_clsp, clsp));
+        if (!f64) SG_TRY(p->tables.upload(&p->c2_clss, clss));
     }
     SG_TRY(p->tables.upload(&p->c2_cmask, cmask));
     SG_TRY(p->tables.upload(&p->c2_ka, ka));
@@ -451,7 +454,8 @@ Cw2Tables c2tables(const sg_amp_plan *p, int B) {
     tb.cf = (const float4 *)p->c2_cf; tb.gm = (const float2 *)p->c2_gm;
     tb.gmt = (const float4 *)p->c2_gmt;
     tb.sh_off = p->c2_shoff; tb.m4n = (uint32_t)(4 * p->w - 1); tb.inv_4n = (float)(1.0 / (4.0 * (double)p->w));
-    tb.cls_ptr = p->r_cls_ptr; tb.cls_ls = p->r_cls_ls; tb.cls2 = p->c2_cls; tb.clsp = p->c2_clsp; tb.qpos = p->r_qpos; tb.seg = p->r_seg;
+    tb.cls_ptr = p->r_cls_ptr; tb.cls_ls = p->r_cls_ls; tb.cls2 = p->c2_cls; tb.clsp = p->c2_clsp; tb.clss = p->c2_clss;
+    tb.qpos = p->r_qpos; tb.seg = p->r_seg;
     tb.xr = (float *)p->ws_c2xp; tb.vz = (float *)p->ws_c2vz; tb.ys = (float *)p->ws_c2ys; tb.zs = (float *)p->ws_c2zs; tb.part = (float4 *)p->ws_c2part;
     // [np B][64] stamps (workgroup blockIdx.x < np B writes 64 blockIdx.x + k), only when the diagnostics
     // buffer holds them (build_cw2 accepts any even Q, and its B * Q * 20 entries are fewer for small Q)
