@@ -425,6 +425,32 @@ int sg_amp_decode_partial_device(sg_amp_plan *p, const void *d_y, int B, const i
 int sg_amp_decode_partial(sg_amp_plan *p, const double *y, int B, const int32_t *known_idx,
                           const int32_t *true_idx, double awgn_var, int t_max, double rtol, int phi_method,
                           int32_t *map_idx, int32_t *t_final, double *nmse, double *psi);
+/* Real K = 2 (BPSK) modulated SPARCs (amp_bpsk.hip): sg_amp_decode_device's loop (sparc.py:883-999) with the
+ * non-zero entry of a section +1 or -1.  A section is one word = (location << 1) | symbol in [0, 2M), symbol 0 for
+ * +1 and 1 for -1: its binary digits, MSB first, are the section's log2 M location bits and its one symbol bit in
+ * the reference's order (sparc.py:330-364), so sg_bits_to_sections_device and sg_amp_count_errors_device serve K = 2
+ * with logM + 1 in the place of logM.  d_true_word [B][L] (optional) gives the transmitted words, for the NMSE
+ * against the +-1 one-hots.  The denoiser is beta_j = (e^{x_j} - e^{-x_j}) / sum_k (e^{x_k} + e^{-x_k}), x = s / tau
+ * (sparc.py:433-441), evaluated with the section's own maximum of |x| and expm1; everything else -- gamma, the
+ * Onsager term, phi by either phi_method, tau, psi = 1 - |beta|^2 / L per column block, the psi stopping rule --
+ * is the unmodulated loop.  d_map_word [B][L] is the final decision on s (sparc.py:488-492): the first location
+ * of the largest |s| and the sign of s there (+1 for s >= 0).  Other outputs as sg_amp_decode_device (any may be
+ * NULL).  Serves every plan sg_amp_apply serves -- flat, power-allocated and spatially coupled W, both precisions
+ * -- on the plan's own operators (never the companion plan, no throughput engine).  Every check precedes any
+ * launch or allocation: SG_ERR_UNSUPPORTED for M not a power of two in [2, 2048] (one wavefront per section, up to
+ * 32 entries per lane); SG_ERR_INVALID for bad t_max, rtol, phi_method, awgn_var as sg_amp_decode_device; B <= 0
+ * returns SG_OK with nothing done.  Works in the workspace and the partial buffers of sg_amp_decode_partial_device:
+ * clears the last-decode state (no soft output for K = 2) and leaves the plan fit for sg_amp_decode*.  A
+ * codeword's results do not depend on the batch it is decoded in. */
+int sg_amp_decode_bpsk_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_true_word, double awgn_var,
+                              int t_max, double rtol, int phi_method, int32_t *d_map_word, int32_t *d_t_final,
+                              double *d_nmse, double *d_psi, void *stream);
+/* Host variant: arrays as sg_amp_decode with words in the place of indices; blocking. */
+int sg_amp_decode_bpsk(sg_amp_plan *p, const double *y, int B, const int32_t *true_word, double awgn_var, int t_max,
+                       double rtol, int phi_method, int32_t *map_word, int32_t *t_final, double *nmse, double *psi);
+/* x = A beta0 [B][n] on the device for section words d_word [B][L] of a real K = 2 SPARC: beta0 holds +1
+ * (symbol 0) or -1 at the word's location; a word outside [0, 2M) leaves its section zero. */
+int sg_amp_encode_bpsk_device(sg_amp_plan *p, const int32_t *d_word, int B, void *d_x, void *stream);
 /* Soft output of the last decode through this plan (sg_amp_decode_device or
  * sg_amp_decode), in the plan precision: for sections [l0, l0 + nl) of each of
  * the B codewords, P(bit = 0) of the log2 M section bits, MSB first, from the

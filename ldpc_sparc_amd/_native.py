@@ -97,6 +97,12 @@ SIGNATURES = [
                                                 ct.c_int, vp, vp, vp, vp, vp]),
     ("sg_concat_known_sections_device", ct.c_int, [ct.c_int, vp, vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
                                                    ct.c_int, ct.c_int, vp, vp]),
+    # real K = 2 (BPSK) modulated AMP: sections as words (location << 1) | symbol
+    ("sg_amp_decode_bpsk", ct.c_int, [vp, vp, ct.c_int, vp, ct.c_double, ct.c_int, ct.c_double, ct.c_int,
+                                      vp, vp, vp, vp]),
+    ("sg_amp_decode_bpsk_device", ct.c_int, [vp, vp, ct.c_int, vp, ct.c_double, ct.c_int, ct.c_double,
+                                             ct.c_int, vp, vp, vp, vp, vp]),
+    ("sg_amp_encode_bpsk_device", ct.c_int, [vp, vp, ct.c_int, vp, vp]),
     ("sg_amp_llr_device", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp, vp]),
     ("sg_amp_llr", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp]),
     ("sg_amp_apply", ct.c_int, [vp, ct.c_int, vp, ct.c_int, vp]),

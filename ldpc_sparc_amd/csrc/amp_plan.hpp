@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "amp.hpp"
+#include "amp_bpsk.hpp"
 #include "amp_partial.hpp"
 #include "device_mem.hpp"
 
@@ -126,7 +127,8 @@ struct sg_amp_plan {
     // (partial_ensure_ws): u = Az(z / phi) [B][LM]; r = Ab(beta) and z [B][n]; partial sums of z^2 [B][PART_MAX];
     // per-section sum beta^2 and squared error [B][L]; phi [B], tau [B][Lc]; the loop's own active flags [B] (the
     // general engine's operators want ws_active all ones) and the known indices of the host variant [B][L].
-    // beta, z / phi and the per-codeword scalars live in the batch workspace.
+    // beta, z / phi and the per-codeword scalars live in the batch workspace.  The real K = 2 loop (amp_bpsk.hip)
+    // runs in the same buffers, with the sums of z^2 per row block [B][Lr][part_count(Mr)] and phi in ws_phi_prev.
     sg::DevPool wp;
     int cap_Bp = 0;
     void *wp_u = nullptr, *wp_r = nullptr, *wp_z = nullptr;

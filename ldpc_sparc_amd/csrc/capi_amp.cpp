@@ -511,6 +511,48 @@ static int partial_impl(sg_amp_plan *p, const DecodeArgs &a, const int32_t *d_kn
     return copy_results(p, a, s);
 }
 
+// Real K = 2 modulated AMP (amp_bpsk.hip): partial_impl's launch sequence with the K = 2 kernels between the
+// operators, in the same buffers.  W of ndim 2 included: phi, gamma and b per row block (phi in ws_phi_prev; the
+// general engine's Az divides by ws_phi, which stays 1), the sums of z^2 per row block in wp_zz.
+template <typename T>
+static int bpsk_impl(sg_amp_plan *p, const DecodeArgs &a, hipStream_t s) {
+    const int B = a.B, t_max = a.t_max;
+    SG_TRY(ensure_ws(p, B, t_max));
+    SG_TRY(partial_ensure_ws(p, B));
+    BpskBufs<T> bb{};
+    bb.B = B; bb.L = p->L; bb.M = p->M; bb.LM = p->LM; bb.n = p->n; bb.Lr = p->Lr; bb.Lc = p->Lc; bb.Mr = p->Mr;
+    bb.ndim = p->ndim; bb.t_max = t_max; bb.np = part_count(p->Mr);
+    bb.y = (const T *)a.d_y;
+    bb.beta = p->regular ? (T *)p->ws_s : (T *)p->ws_beta;
+    bb.u = (T *)p->wp_u; bb.r = (T *)p->wp_r; bb.z = (T *)p->wp_z; bb.zs = (T *)p->ws_z;
+    bb.true_word = a.d_true;
+    bb.zz = p->wp_zz; bb.bsq = p->wp_bsq; bb.err = p->wp_err; bb.map = p->ws_argmax;
+    bb.psi = p->ws_psi; bb.psi_prev = p->ws_psi_prev; bb.gamma = p->ws_gamma; bb.bco = p->ws_bco;
+    bb.phi = p->ws_phi_prev; bb.tau = p->wp_tau; bb.nmse = p->ws_nmse;
+    bb.active = p->wp_active; bb.t_final = p->ws_tfinal;
+    bb.W = p->dW; bb.awgn_var = a.awgn_var; bb.rtol = a.rtol;
+    bb.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
+    bb.phi_method = a.phi_method;
+    SG_HIP(hipMemsetAsync(bb.beta, 0, (size_t)B * p->LM * sizeof(T), s));
+    if (!p->regular) SG_TRY(idct_launch_ones(p->ws_active, B, p->ws_phi, B * p->Lr, s));
+    SG_TRY(bpsk_launch_init<T>(bb, s));
+    ActivePoll poll{p, B, s, false, p->wp_active};
+    for (int t = 0; t < t_max - 1; ++t) {
+        SG_TRY(apply_enqueue<T>(p, 0, bb.beta, B, bb.r, s));  // r = Ab(beta) (t = 0: of zero)
+        SG_TRY(bpsk_launch_residual<T>(bb, t, s));
+        SG_TRY(bpsk_launch_control<T>(bb, 0, t, s));
+        SG_TRY(apply_enqueue<T>(p, 1, bb.zs, B, bb.u, s));  // u = Az(z / phi)
+        SG_TRY(bpsk_launch_section<T>(bb, s));
+        SG_TRY(bpsk_launch_control<T>(bb, 1, t, s));
+        // skip the remaining launches once every codeword stopped (ActivePoll: the flags after iterations 3, 7,
+        // 11, ..., read one iteration later)
+        bool stopped = false;
+        SG_TRY(poll.step(t % 4 == 3 && t + 2 < t_max - 1, &stopped));
+        if (stopped) break;
+    }
+    return copy_results(p, a, s);
+}
+
 // The refusals of a decode's scalar parameters
 static int param_checks(double awgn_var, int t_max, double rtol, int phi_method) {
     SG_CHECK_ARG(t_max > 1, "t_max must be > 1 (sparc.py:168)");
@@ -531,16 +573,25 @@ static int partial_checks(const sg_amp_plan *p, double awgn_var, int t_max, doub
     return param_checks(awgn_var, t_max, rtol, phi_method);
 }
 
+// Every refusal of the K = 2 decode that needs no device (header, sg_amp_decode_bpsk_device)
+static int bpsk_checks(const sg_amp_plan *p, double awgn_var, int t_max, double rtol, int phi_method) {
+    if (p->M < 2 || (p->M & (p->M - 1)) != 0 || p->M > 2048)
+        return fail(SG_ERR_UNSUPPORTED, "section size M = %d: the K = 2 section kernel takes a power of two in "
+                    "[2, 2048]", p->M);
+    return param_checks(awgn_var, t_max, rtol, phi_method);
+}
+
 // The host side of a decode, after the entry point's refusals: y (and the known and true sections) into the plan's
-// buffers, the decode there, the results back.  known_idx null: decode_impl; given: partial_impl.
+// buffers, the decode there, the results back.  known_idx null: decode_impl; given: partial_impl; bpsk: bpsk_impl
+// (true_idx, map_idx then hold section words).
 static int decode_host(sg_amp_plan *p, const double *y, int B, const int32_t *known_idx, const int32_t *true_idx,
                        double awgn_var, int t_max, double rtol, int phi_method, int32_t *map_idx, int32_t *t_final,
-                       double *nmse, double *psi) {
+                       double *nmse, double *psi, bool bpsk = false) {
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = lib_stream();
     // (the workspace before the staging buffer: growing the workspace frees io too)
     SG_TRY(ensure_ws(p, B, t_max));
-    if (known_idx) SG_TRY(partial_ensure_ws(p, B));
+    if (known_idx || bpsk) SG_TRY(partial_ensure_ws(p, B));
     const size_t ny = (size_t)B * p->n, nsec = (size_t)B * p->L;
     SG_TRY(ensure_io(p, ny * sizeof(double)));
     SG_HIP(hipMemcpyAsync(p->io.at(), y, ny * sizeof(double), hipMemcpyHostToDevice, s));
@@ -551,6 +602,7 @@ static int decode_host(sg_amp_plan *p, const double *y, int B, const int32_t *kn
         SG_TRY(amp_launch_cast<T>(p->io.at(), 1, (T *)p->ws_y, ny, s));
         const DecodeArgs a{p->ws_y, B, true_idx ? p->ws_true : nullptr, awgn_var, t_max, rtol, phi_method,
                            nullptr, nullptr, nullptr, nullptr};
+        if (bpsk) return bpsk_impl<T>(p, a, s);
         return known_idx ? partial_impl<T>(p, a, p->wp_known, s) : decode_impl<T>(p, a, s);
     }));
     SG_HIP(hipMemcpyAsync(map_idx, p->ws_argmax, sizeof(int32_t) * nsec, hipMemcpyDeviceToHost, s));
@@ -574,12 +626,25 @@ __global__ void onehot_one_kernel(const int32_t *idx, int L, int M, T *beta) {
         beta[(size_t)b * L * M + (size_t)l * M + idx[(size_t)b * L + l]] = T(1);
 }
 
+// K = 2: section words (location << 1) | symbol -> beta0 with +1 (symbol 0) or -1 at the location; a word outside
+// [0, 2M) leaves its section zero.
 template <typename T>
-static int encode_impl(sg_amp_plan *p, const int32_t *d_idx, int B, T *d_x, hipStream_t s) {
+__global__ void onehot_bpsk_kernel(const int32_t *word, int L, int M, T *beta) {
+    const int b = blockIdx.y;
+    for (int l = blockIdx.x * blockDim.x + threadIdx.x; l < L; l += gridDim.x * blockDim.x) {
+        const int w = word[(size_t)b * L + l];
+        if (w >= 0 && w < 2 * M) beta[(size_t)b * L * M + (size_t)l * M + (w >> 1)] = (w & 1) ? T(-1) : T(1);
+    }
+}
+
+template <typename T>
+static int encode_impl(sg_amp_plan *p, const int32_t *d_idx, int B, T *d_x, hipStream_t s, bool bpsk = false) {
     SG_TRY(ensure_ws(p, B, 2));
     T *beta0 = p->regular ? (T *)p->ws_s : (T *)p->ws_beta;  // (where apply_enqueue reads it without a copy)
     SG_HIP(hipMemsetAsync(beta0, 0, (size_t)B * p->LM * sizeof(T), s));
-    hipLaunchKernelGGL(onehot_one_kernel<T>, dim3((p->L + 255) / 256, B), dim3(256), 0, s, d_idx, p->L, p->M, beta0);
+    const dim3 grid((p->L + 255) / 256, B);
+    if (bpsk) hipLaunchKernelGGL(onehot_bpsk_kernel<T>, grid, dim3(256), 0, s, d_idx, p->L, p->M, beta0);
+    else hipLaunchKernelGGL(onehot_one_kernel<T>, grid, dim3(256), 0, s, d_idx, p->L, p->M, beta0);
     std::vector<int32_t> ones;
     if (!p->regular) {  // the general engine: all codewords active
         ones.assign(B, 1);
@@ -702,6 +767,33 @@ int sg_amp_decode_partial(sg_amp_plan *p, const double *y, int B, const int32_t 
                            psi);
 }
 
+int sg_amp_decode_bpsk_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_true_word, double awgn_var,
+                              int t_max, double rtol, int phi_method, int32_t *d_map_word, int32_t *d_t_final,
+                              double *d_nmse, double *d_psi, void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    reset_last(p);  // (the loop runs in the workspace that holds a decode's final state)
+    SG_TRY(sg::bpsk_checks(p, awgn_var, t_max, rtol, phi_method));
+    if (B <= 0) return SG_OK;
+    SG_CHECK_ARG(d_y, "d_y is NULL");
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = pick_stream(stream);
+    const DecodeArgs a{d_y, B, d_true_word, awgn_var, t_max, rtol, phi_method, d_map_word, d_t_final, d_nmse, d_psi};
+    return by_precision(p->precision, [&](auto t) { return bpsk_impl<decltype(t)>(p, a, s); });
+}
+
+int sg_amp_decode_bpsk(sg_amp_plan *p, const double *y, int B, const int32_t *true_word, double awgn_var, int t_max,
+                       double rtol, int phi_method, int32_t *map_word, int32_t *t_final, double *nmse, double *psi) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    reset_last(p);
+    SG_TRY(sg::bpsk_checks(p, awgn_var, t_max, rtol, phi_method));
+    if (B <= 0) return SG_OK;
+    SG_CHECK_ARG(y && map_word && t_final && nmse && psi, "null host buffer");
+    return sg::decode_host(p, y, B, nullptr, true_word, awgn_var, t_max, rtol, phi_method, map_word, t_final, nmse, psi,
+                           true);
+}
+
 int sg_concat_known_sections_device(int precision, const void *d_app, const int32_t *d_it, int max_it, int B, int mults,
                                     int N, int L, int L_unprotected, int logM, int32_t *d_known_idx, void *stream) {
     SG_TRY(ensure_device());
@@ -745,6 +837,15 @@ int sg_amp_encode_device(sg_amp_plan *p, const int32_t *d_idx, int B, void *d_x,
     SG_TRY(ensure_device());
     hipStream_t s = pick_stream(stream);
     return by_precision(p->precision, [&](auto t) { return encode_impl(p, d_idx, B, (decltype(t) *)d_x, s); });
+}
+
+int sg_amp_encode_bpsk_device(sg_amp_plan *p, const int32_t *d_word, int B, void *d_x, void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p && d_word && d_x, "null argument");
+    if (B <= 0) return SG_OK;
+    p->last_B = 0;
+    hipStream_t s = pick_stream(stream);
+    return by_precision(p->precision, [&](auto t) { return encode_impl(p, d_word, B, (decltype(t) *)d_x, s, true); });
 }
 
 // Diagnostics: mean shader-clock cycles between the phase timestamps of the

@@ -262,18 +262,28 @@ class SparcTrial:
     (sparc_sim.py:179-204) -> AMP (sparc.py:883-999) -> errors.  Counters
     [codewords, bit errors, codeword errors, AMP iterations, section errors];
     the Philox stream of block b at point p is (p, b), so results do not
-    depend on the rank count.  op: sparc.DesignOperator (shared design)."""
+    depend on the rank count.  op: sparc.DesignOperator (shared design).
 
-    def __init__(self, op, awgn_vars, t_max=25, rtol=1e-6, phi_method=1, precision="f32", seed=0):
+    K = 2: the real BPSK-modulated SPARC on the same design (csrc/amp_bpsk.hip,
+    the staged path): log2 M + 1 bits per section, the section word
+    (location << 1) | symbol in the place of the index, so a section error is
+    a wrong location or a wrong sign."""
+
+    def __init__(self, op, awgn_vars, t_max=25, rtol=1e-6, phi_method=1, precision="f32", seed=0, K=1):
+        if K not in (1, 2):
+            raise ValueError("SparcTrial: K must be 1 (unmodulated) or 2 (BPSK modulated)")
+        self.K = int(K)
         self.op, self.vars = op, list(awgn_vars)
         self.t_max, self.rtol, self.phi = int(t_max), float(rtol), int(phi_method)
         self.prec = {"f64": _native.SG_F64, "f32": _native.SG_F32}[precision]
         self.seed = int(seed)
-        self.logM = int(np.log2(op.M))
+        self.logM = int(np.log2(op.M)) + (1 if self.K == 2 else 0)  # bits per section
 
     def __call__(self, point, first_block, n_blocks, block):
         op, lib, off = self.op, _native.lib(), _native.offset
         L, n, logM = op.L, op.n, self.logM
+        encode, decode = ((lib.sg_amp_encode_device, lib.sg_amp_decode_device) if self.K == 1 else
+                          (lib.sg_amp_encode_bpsk_device, lib.sg_amp_decode_bpsk_device))
         es = 8 if self.prec == _native.SG_F64 else 4
         B = n_blocks * block
         plan = op.plan(self.prec)
@@ -287,7 +297,7 @@ class SparcTrial:
             o = i * block
             _native.check(lib.sg_rng_bits_device(self.seed, sid, block, L * logM, off(d_bits.ptr, o * L * logM), None))
         _native.check(lib.sg_bits_to_sections_device(d_bits.ptr, B, L, logM, d_true.ptr, None))
-        _native.check(lib.sg_amp_encode_device(plan, d_true.ptr, B, d_x.ptr, None))
+        _native.check(encode(plan, d_true.ptr, B, d_x.ptr, None))
         for i, blk in enumerate(range(first_block, first_block + n_blocks)):
             sid = (int(point) << 32) | int(blk)
             o = i * block
@@ -297,8 +307,8 @@ class SparcTrial:
         d_tf = _native.DeviceBuffer(B * 4)
         d_cnt = _native.DeviceBuffer(4 * 8)
         d_cnt.zero()
-        _native.check(lib.sg_amp_decode_device(plan, d_y.ptr, B, d_true.ptr, float(self.vars[point]), self.t_max,
-                                               self.rtol, self.phi, d_map.ptr, d_tf.ptr, None, None, None))
+        _native.check(decode(plan, d_y.ptr, B, d_true.ptr, float(self.vars[point]), self.t_max, self.rtol, self.phi,
+                             d_map.ptr, d_tf.ptr, None, None, None))
         _native.check(lib.sg_amp_count_errors_device(d_map.ptr, d_true.ptr, d_tf.ptr, B, L, logM, d_cnt.ptr, None))
         cnt = d_cnt.download(np.zeros(4, np.int64))
         return np.array([B, cnt[1], cnt[2], cnt[3], cnt[0]], dtype=np.int64)

@@ -16,7 +16,15 @@ Complex SPARCs (the sub-sampled FFT design, sub_fft sparc.py:593-646) and
 K-PSK modulated complex SPARCs (K up to 64) run on the complex engine
 (csrc/amp_cfft.hip) in double precision only: 'precision': 'f32' with a
 complex design raises NotImplementedError.  Also out of scope, raising
-NotImplementedError: real K=2 modulated SPARCs on the DCT engines, and K > 64.
+NotImplementedError: K > 64.
+
+Real K=2 (BPSK) modulated SPARCs -- the DCT design with section entries +1 or
+-1 -- decode on the GPU in either precision (csrc/amp_bpsk.hip, flat,
+power-allocated and spatially coupled designs): amp_decode_bpsk_batch, and
+montecarlo.SparcTrial(..., K=2) for campaigns.  Through the drop-in functions
+(sparc_encode, sparc_amp, sparc_decode, sparc_sim.sparc_sim) the family is
+opt-in: they refuse it with NotImplementedError until enable_real_psk() has
+been called once, the one line a reference script needs added.
 Soft output of the complex engine: ComplexDesignOperator.soft_output() then
 camp_llr (bit LLRs of location and K-PSK symbol bits); section_llr_psk is the
 stand-alone function.  Monte-Carlo campaigns of complex SPARCs that stay on the GPU are
@@ -338,12 +346,30 @@ def _check_psk(K):
             raise NotImplementedError("K-PSK with K > {} is not part of the GPU engine".format(MAX_PSK))
 
 
+_real_psk = False  # enable_real_psk
+
+
+def enable_real_psk(on=True):
+    """Switch the drop-in functions' real K=2 modulated path (sparc_encode,
+    sparc_amp, sparc_decode, sparc_sim.sparc_sim) on or off; off is the
+    default.  Returns the previous setting; calling it again with the same
+    value changes nothing.  amp_decode_bpsk_batch and
+    montecarlo.SparcTrial(K=2) need no switch."""
+    global _real_psk
+    prev, _real_psk = _real_psk, bool(on)
+    return prev
+
+
 def _check_family(K, csparc):
-    """Complex designs carry any K up to MAX_PSK; real designs only K=1."""
+    """Complex designs carry any K up to MAX_PSK; real designs K=1, and K=2
+    after enable_real_psk()."""
     _check_psk(K)
     if K != 1 and not csparc:
-        raise NotImplementedError("real K=2 modulated SPARCs are not part of the GPU engine "
-                                  "(the DCT engines are unmodulated)")
+        assert K == 2, 'Real-modulated SPARCs requires K=2'
+        if not _real_psk:
+            raise NotImplementedError("real K=2 modulated SPARCs are opt-in for the drop-in functions: call "
+                                      "ldpc_sparc_amd.sparc.enable_real_psk() once before (amp_decode_bpsk_batch and "
+                                      "montecarlo.SparcTrial(K=2) need no switch)")
 
 
 def _interleaved(a):
@@ -752,6 +778,34 @@ def amp_decode_partial_batch(Y, op, known_idx, awgn_var, t_max, rtol=1e-6, phi_e
     return map_idx, t_final, nmse, psi
 
 
+def bpsk_words(loc, sym):
+    """Section words (location << 1) | symbol of a real K=2 SPARC, int32: the
+    MSB-first digits of a word are the section's log2 M location bits and its
+    symbol bit (0: +1, 1: -1) in the order of bin_arr_2_msg_vector."""
+    return ((np.asarray(loc, dtype=np.int64) << 1) | np.asarray(sym, dtype=np.int64)).astype(np.int32)
+
+
+def amp_decode_bpsk_batch(Y, op, awgn_var, t_max, rtol=1e-6, phi_est_method=1, true_word=None,
+                          precision=_native.SG_F64):
+    """amp_decode_batch for real K=2 (BPSK) modulated SPARCs: the section's
+    non-zero entry is +1 or -1.  A section is reported and supplied as one
+    word (bpsk_words): true_word [B, L] the transmitted words (for NMSE) or
+    None.  Flat, power-allocated and spatially coupled DCT designs, M a power
+    of two in [2, 2048], either precision.  Returns (map_word [B, L], t_final
+    [B], nmse [B, t_max, Lc], psi [B, Lc])."""
+    if op.csparc:
+        raise ValueError("amp_decode_bpsk_batch needs a real DesignOperator (complex designs: camp_decode_batch "
+                         "with K=2)")
+    Y, B = _received_words(Y, op, np.float64)
+    tw = None if true_word is None else _true_sections(true_word, B, op)
+    map_word, t_final, nmse, psi = _decode_outputs(B, op, t_max)
+    _native.check(_native.lib().sg_amp_decode_bpsk(
+        op.plan(precision), _native.ptr(Y), B, _native.ptr(tw), float(awgn_var), int(t_max),
+        float(rtol), int(phi_est_method), _native.ptr(map_word), _native.ptr(t_final),
+        _native.ptr(nmse), _native.ptr(psi)))
+    return map_word, t_final, nmse, psi
+
+
 def amp_llr(op, B, l0, nl, probs_only=False, precision=_native.SG_F64):
     """Soft output of the last amp_decode_batch of B codewords through `op` at
     this precision: for sections [l0, l0 + nl), the LLRs log p - log(1 - p) of
@@ -861,7 +915,8 @@ def sparc_amp(y, code_params, decode_params, awgn_var, rand_seed, beta0, Ab=None
     nmse, psi) with the reference's shapes: nmse (t_max,) for a regular
     design, (t_max, Lc) otherwise; psi a scalar or (Lc,).  Complex designs
     (code_params['complex'], optionally K-PSK modulated) run on the complex
-    engine in double precision."""
+    engine in double precision; real K=2 modulated codes (after
+    enable_real_psk()) return beta with entries +1 / -1."""
     P, R, L, M, n = map(code_params.get, ['P', 'R', 'L', 'M', 'n'])
     K = code_params['K'] if code_params['modulated'] else 1
     _check_family(K, code_params.get('complex', False))
@@ -882,6 +937,16 @@ def sparc_amp(y, code_params, decode_params, awgn_var, rand_seed, beta0, Ab=None
         raise ValueError("Ab/Az do not match code_params['complex']")
     if op.csparc:
         return _sparc_amp_complex(y, op, W, L, M, K, decode_params, awgn_var, beta0)
+    if K == 2:
+        true_word = None
+        if beta0 is not None:
+            true_word = bpsk_words(*_msg_vector_indices(np.asarray(beta0), M, K))[None, :]
+        map_word, t_final, nmse, psi = amp_decode_bpsk_batch(np.asarray(y)[None, :], op, awgn_var, t_max, rtol,
+                                                             phi_est_method, true_word, _precision(decode_params))
+        beta = _msg_vector_from_indices(map_word[0] >> 1, map_word[0] & 1, M, K)
+        if W.ndim == 0:
+            return beta, int(t_final[0]), nmse[0, :, 0].copy(), np.float64(psi[0, 0])
+        return beta, int(t_final[0]), nmse[0].copy(), psi[0].copy()
     true_idx = None
     if beta0 is not None:
         b0 = np.asarray(beta0).reshape(L, M)

@@ -4,9 +4,11 @@ sparc_sim(code_params, decode_params, awgn_var, rand_seed) returns the
 reference's result dict (sparc_sim.py:8-58); the decoder runs on the GPU.
 Complex SPARCs, unmodulated or K-PSK modulated (K up to 64), run on the
 complex engine in double precision; modulated codes add the location / value
-error statistics of calc_ler_ver.  Out of scope (NotImplementedError): real
-K=2 modulated SPARCs on the DCT engines, single precision for complex SPARCs,
-and K > 64.  An error-rate curve of a complex SPARC is
+error statistics of calc_ler_ver.  Real K=2 (BPSK) modulated SPARCs run on
+the DCT design after sparc.enable_real_psk() (opt-in: refused with
+NotImplementedError before), in either precision.  Out of scope
+(NotImplementedError): single precision for complex SPARCs, and K > 64.  An
+error-rate curve of a complex SPARC is
 montecarlo.csparc_ser_sweep (one shared design, generated, decoded and counted
 on the GPU); its state-evolution prediction is sparc_se.sparc_se.
 """
