@@ -399,7 +399,7 @@ int sg_amp_decode_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *
                          double awgn_var, int t_max, double rtol, int phi_method,
                          int32_t *d_map_idx, int32_t *d_t_final, double *d_nmse, double *d_psi,
                          void *stream);
-/* AMP with known sections (amp_partial.hip): sg_amp_decode_device's loop (sparc.py:883-999) in which some
+/* AMP with known sections (amp_oploop.hip): sg_amp_decode_device's loop (sparc.py:883-999) in which some
  * sections of a codeword are given.  d_known_idx [B][L] holds a section's index in [0, M), or -1 for a section
  * to decode; the known set is per codeword.  The denoiser of a known section returns the one-hot of its index (it
  * adds 1 to sum beta^2, 0 to psi, and 0 to the NMSE where it agrees with d_true_idx); the start is beta0 = the
@@ -425,7 +425,7 @@ int sg_amp_decode_partial_device(sg_amp_plan *p, const void *d_y, int B, const i
 int sg_amp_decode_partial(sg_amp_plan *p, const double *y, int B, const int32_t *known_idx,
                           const int32_t *true_idx, double awgn_var, int t_max, double rtol, int phi_method,
                           int32_t *map_idx, int32_t *t_final, double *nmse, double *psi);
-/* Real K = 2 (BPSK) modulated SPARCs (amp_bpsk.hip): sg_amp_decode_device's loop (sparc.py:883-999) with the
+/* Real K = 2 (BPSK) modulated SPARCs (amp_oploop.hip): sg_amp_decode_device's loop (sparc.py:883-999) with the
  * non-zero entry of a section +1 or -1.  A section is one word = (location << 1) | symbol in [0, 2M), symbol 0 for
  * +1 and 1 for -1: its binary digits, MSB first, are the section's log2 M location bits and its one symbol bit in
  * the reference's order (sparc.py:330-364), so sg_bits_to_sections_device and sg_amp_count_errors_device serve K = 2

@@ -129,11 +129,9 @@ int partial_ensure_ws(sg_amp_plan *p, int B) {
     SG_TRY(p->wp.alloc(&p->wp_u, Bz * p->LM * rs));
     SG_TRY(p->wp.alloc(&p->wp_r, Bz * p->n * rs));
     SG_TRY(p->wp.alloc(&p->wp_z, Bz * p->n * rs));
-    // (PART_MAX per codeword for one row block; the K = 2 loop keeps sums per row block of a spatially coupled W)
-    SG_TRY(p->wp.alloc(&p->wp_zz, Bz * bpsk_zz_count(p->Lr, p->Mr) * sizeof(double)));
+    SG_TRY(p->wp.alloc(&p->wp_zz, Bz * oploop_zz_count(p->Lr, p->Mr) * sizeof(double)));
     SG_TRY(p->wp.alloc(&p->wp_bsq, Bz * p->L * sizeof(double)));
     SG_TRY(p->wp.alloc(&p->wp_err, Bz * p->L * sizeof(double)));
-    SG_TRY(p->wp.alloc(&p->wp_phi, Bz * sizeof(double)));
     SG_TRY(p->wp.alloc(&p->wp_tau, Bz * p->Lc * sizeof(double)));
     SG_TRY(p->wp.alloc(&p->wp_active, Bz * sizeof(int32_t)));
     SG_TRY(p->wp.alloc(&p->wp_known, Bz * p->L * sizeof(int32_t)));

@@ -10,8 +10,7 @@
 #include <vector>
 
 #include "amp.hpp"
-#include "amp_bpsk.hpp"
-#include "amp_partial.hpp"
+#include "amp_oploop.hpp"
 #include "device_mem.hpp"
 
 using cd = std::complex<double>;
@@ -123,16 +122,16 @@ struct sg_amp_plan {
          *wi_llr = nullptr, *wi_app = nullptr;
     int32_t *wi_it = nullptr;
     double *wi_part = nullptr, *wi_ons = nullptr;
-    // AMP with known sections (amp_partial.hip), grow-only per (plan, B) like the integrated buffers
-    // (partial_ensure_ws): u = Az(z / phi) [B][LM]; r = Ab(beta) and z [B][n]; partial sums of z^2 [B][PART_MAX];
-    // per-section sum beta^2 and squared error [B][L]; phi [B], tau [B][Lc]; the loop's own active flags [B] (the
-    // general engine's operators want ws_active all ones) and the known indices of the host variant [B][L].
-    // beta, z / phi and the per-codeword scalars live in the batch workspace.  The real K = 2 loop (amp_bpsk.hip)
-    // runs in the same buffers, with the sums of z^2 per row block [B][Lr][part_count(Mr)] and phi in ws_phi_prev.
+    // The operator-loop decoder (amp_oploop.hip: AMP with known sections and real K = 2 modulated AMP), grow-only
+    // per (plan, B) like the integrated buffers (partial_ensure_ws): u = Az(z / phi) [B][LM]; r = Ab(beta) and z
+    // [B][n]; partial sums of z^2 per row block [B][oploop_zz_count(Lr, Mr)]; per-section sum beta^2 and squared
+    // error [B][L]; tau [B][Lc]; the loop's own active flags [B] (the general engine's operators want ws_active all
+    // ones) and the known indices of the host variant [B][L].  beta, z / phi and the per-codeword scalars (phi in
+    // ws_phi_prev) live in the batch workspace.
     sg::DevPool wp;
     int cap_Bp = 0;
     void *wp_u = nullptr, *wp_r = nullptr, *wp_z = nullptr;
-    double *wp_zz = nullptr, *wp_bsq = nullptr, *wp_err = nullptr, *wp_phi = nullptr, *wp_tau = nullptr;
+    double *wp_zz = nullptr, *wp_bsq = nullptr, *wp_err = nullptr, *wp_tau = nullptr;
     int32_t *wp_active = nullptr, *wp_known = nullptr;
 };
 

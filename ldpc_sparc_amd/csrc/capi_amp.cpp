@@ -1,5 +1,6 @@
 // C ABI of the AMP decoder on a design plan (amp_plan.hpp): engine choice, batched decode, the design
 // operators Ab / Az, the encoder, soft output, the integrated AMP <-> BP loop, error counting.
+#include <optional>
 #include <type_traits>
 
 #include "amp_plan.hpp"
@@ -466,84 +467,44 @@ static int integ_dct_impl(sg_amp_plan *p, sg_graph *g, int mode, int N, int K, c
     return SG_OK;
 }
 
-// AMP with known sections (amp_partial.hip): sparc_amp with the plan's operators on natural-order vectors, as
-// integ_dct_impl runs them.  beta lives in the plan's [B][LM] workspace (ws_s of a regular plan, ws_beta of a
-// general one) and z / phi in ws_z, where apply_enqueue reads them without a copy; z, r = Ab(beta), u = Az(z / phi)
-// and the section sums in the partial buffers; the per-codeword scalars and results in the batch workspace's slots,
-// so copy_results ends the call.  Nothing but launches inside the loop; the loop's own active flags are polled
-// like a decode's.
+// The operator-loop decoder (amp_oploop.hip), for AMP with known sections (rule Known, d_known given) and real
+// K = 2 modulated AMP (rule Bpsk, d_known null; a.d_true then holds words): sparc_amp with the plan's operators on
+// natural-order vectors, as integ_dct_impl runs them.  beta lives in the plan's [B][LM] workspace (ws_s of a
+// regular plan, ws_beta of a general one) and z / phi in ws_z, where apply_enqueue reads them without a copy; z,
+// r = Ab(beta), u = Az(z / phi), the sums of z^2 per row block and the section sums in the loop's own buffers
+// (wp); the per-codeword scalars and results in the batch workspace's slots, so copy_results ends the call.  phi,
+// gamma and b are per row block (W of ndim 2; phi in ws_phi_prev: the general engine's Az divides by ws_phi, which
+// stays 1).  Nothing but launches inside the loop; the loop's own active flags are polled like a decode's.
 template <typename T>
-static int partial_impl(sg_amp_plan *p, const DecodeArgs &a, const int32_t *d_known, hipStream_t s) {
+static int oploop_impl(sg_amp_plan *p, const DecodeArgs &a, SectionRule rule, const int32_t *d_known, hipStream_t s) {
     const int B = a.B, t_max = a.t_max;
     SG_TRY(ensure_ws(p, B, t_max));
     SG_TRY(partial_ensure_ws(p, B));
-    PartBufs<T> pb{};
-    pb.B = B; pb.L = p->L; pb.M = p->M; pb.LM = p->LM; pb.n = p->n; pb.Lc = p->Lc; pb.ndim = p->ndim;
-    pb.t_max = t_max; pb.np = part_count(p->n);
-    pb.y = (const T *)a.d_y;
-    pb.beta = p->regular ? (T *)p->ws_s : (T *)p->ws_beta;
-    pb.u = (T *)p->wp_u; pb.r = (T *)p->wp_r; pb.z = (T *)p->wp_z; pb.zs = (T *)p->ws_z;
-    pb.known = d_known; pb.true_idx = a.d_true;
-    pb.zz = p->wp_zz; pb.bsq = p->wp_bsq; pb.err = p->wp_err; pb.map = p->ws_argmax;
-    pb.psi = p->ws_psi; pb.psi_prev = p->ws_psi_prev; pb.gamma = p->ws_gamma; pb.bco = p->ws_bco;
-    pb.phi = p->wp_phi; pb.tau = p->wp_tau; pb.nmse = p->ws_nmse;
-    pb.active = p->wp_active; pb.t_final = p->ws_tfinal;
-    pb.W = p->dW; pb.awgn_var = a.awgn_var; pb.rtol = a.rtol;
-    pb.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
-    pb.phi_method = a.phi_method;
-    SG_HIP(hipMemsetAsync(pb.beta, 0, (size_t)B * p->LM * sizeof(T), s));
+    OpLoopBufs<T> ob{};
+    ob.B = B; ob.L = p->L; ob.M = p->M; ob.LM = p->LM; ob.n = p->n; ob.Lr = p->Lr; ob.Lc = p->Lc; ob.Mr = p->Mr;
+    ob.ndim = p->ndim; ob.t_max = t_max; ob.np = part_count(p->Mr);
+    ob.y = (const T *)a.d_y;
+    ob.beta = p->regular ? (T *)p->ws_s : (T *)p->ws_beta;
+    ob.u = (T *)p->wp_u; ob.r = (T *)p->wp_r; ob.z = (T *)p->wp_z; ob.zs = (T *)p->ws_z;
+    ob.known = d_known; ob.truth = a.d_true;
+    ob.zz = p->wp_zz; ob.bsq = p->wp_bsq; ob.err = p->wp_err; ob.map = p->ws_argmax;
+    ob.psi = p->ws_psi; ob.psi_prev = p->ws_psi_prev; ob.gamma = p->ws_gamma; ob.bco = p->ws_bco;
+    ob.phi = p->ws_phi_prev; ob.tau = p->wp_tau; ob.nmse = p->ws_nmse;
+    ob.active = p->wp_active; ob.t_final = p->ws_tfinal;
+    ob.W = p->dW; ob.awgn_var = a.awgn_var; ob.rtol = a.rtol;
+    ob.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
+    ob.phi_method = a.phi_method;
+    SG_HIP(hipMemsetAsync(ob.beta, 0, (size_t)B * p->LM * sizeof(T), s));
     if (!p->regular) SG_TRY(idct_launch_ones(p->ws_active, B, p->ws_phi, B * p->Lr, s));
-    SG_TRY(part_launch_init<T>(pb, s));
+    SG_TRY(oploop_launch_init<T>(ob, s));
     ActivePoll poll{p, B, s, false, p->wp_active};
     for (int t = 0; t < t_max - 1; ++t) {
-        SG_TRY(apply_enqueue<T>(p, 0, pb.beta, B, pb.r, s));  // r = Ab(beta) (t = 0: of the known one-hots)
-        SG_TRY(part_launch_residual<T>(pb, t, s));
-        SG_TRY(part_launch_control<T>(pb, 0, t, s));
-        SG_TRY(apply_enqueue<T>(p, 1, pb.zs, B, pb.u, s));  // u = Az(z / phi)
-        SG_TRY(part_launch_section<T>(pb, s));
-        SG_TRY(part_launch_control<T>(pb, 1, t, s));
-        // skip the remaining launches once every codeword stopped (ActivePoll: the flags after iterations 3, 7,
-        // 11, ..., read one iteration later)
-        bool stopped = false;
-        SG_TRY(poll.step(t % 4 == 3 && t + 2 < t_max - 1, &stopped));
-        if (stopped) break;
-    }
-    return copy_results(p, a, s);
-}
-
-// Real K = 2 modulated AMP (amp_bpsk.hip): partial_impl's launch sequence with the K = 2 kernels between the
-// operators, in the same buffers.  W of ndim 2 included: phi, gamma and b per row block (phi in ws_phi_prev; the
-// general engine's Az divides by ws_phi, which stays 1), the sums of z^2 per row block in wp_zz.
-template <typename T>
-static int bpsk_impl(sg_amp_plan *p, const DecodeArgs &a, hipStream_t s) {
-    const int B = a.B, t_max = a.t_max;
-    SG_TRY(ensure_ws(p, B, t_max));
-    SG_TRY(partial_ensure_ws(p, B));
-    BpskBufs<T> bb{};
-    bb.B = B; bb.L = p->L; bb.M = p->M; bb.LM = p->LM; bb.n = p->n; bb.Lr = p->Lr; bb.Lc = p->Lc; bb.Mr = p->Mr;
-    bb.ndim = p->ndim; bb.t_max = t_max; bb.np = part_count(p->Mr);
-    bb.y = (const T *)a.d_y;
-    bb.beta = p->regular ? (T *)p->ws_s : (T *)p->ws_beta;
-    bb.u = (T *)p->wp_u; bb.r = (T *)p->wp_r; bb.z = (T *)p->wp_z; bb.zs = (T *)p->ws_z;
-    bb.true_word = a.d_true;
-    bb.zz = p->wp_zz; bb.bsq = p->wp_bsq; bb.err = p->wp_err; bb.map = p->ws_argmax;
-    bb.psi = p->ws_psi; bb.psi_prev = p->ws_psi_prev; bb.gamma = p->ws_gamma; bb.bco = p->ws_bco;
-    bb.phi = p->ws_phi_prev; bb.tau = p->wp_tau; bb.nmse = p->ws_nmse;
-    bb.active = p->wp_active; bb.t_final = p->ws_tfinal;
-    bb.W = p->dW; bb.awgn_var = a.awgn_var; bb.rtol = a.rtol;
-    bb.atol = 2e-15;  // 2*np.finfo(float).resolution, sparc.py:916
-    bb.phi_method = a.phi_method;
-    SG_HIP(hipMemsetAsync(bb.beta, 0, (size_t)B * p->LM * sizeof(T), s));
-    if (!p->regular) SG_TRY(idct_launch_ones(p->ws_active, B, p->ws_phi, B * p->Lr, s));
-    SG_TRY(bpsk_launch_init<T>(bb, s));
-    ActivePoll poll{p, B, s, false, p->wp_active};
-    for (int t = 0; t < t_max - 1; ++t) {
-        SG_TRY(apply_enqueue<T>(p, 0, bb.beta, B, bb.r, s));  // r = Ab(beta) (t = 0: of zero)
-        SG_TRY(bpsk_launch_residual<T>(bb, t, s));
-        SG_TRY(bpsk_launch_control<T>(bb, 0, t, s));
-        SG_TRY(apply_enqueue<T>(p, 1, bb.zs, B, bb.u, s));  // u = Az(z / phi)
-        SG_TRY(bpsk_launch_section<T>(bb, s));
-        SG_TRY(bpsk_launch_control<T>(bb, 1, t, s));
+        SG_TRY(apply_enqueue<T>(p, 0, ob.beta, B, ob.r, s));  // r = Ab(beta) (t = 0: of the known one-hots, or of zero)
+        SG_TRY(oploop_launch_residual<T>(ob, t, s));
+        SG_TRY(oploop_launch_control<T>(ob, 0, t, s));
+        SG_TRY(apply_enqueue<T>(p, 1, ob.zs, B, ob.u, s));  // u = Az(z / phi)
+        SG_TRY(oploop_launch_section<T>(ob, rule, s));
+        SG_TRY(oploop_launch_control<T>(ob, 1, t, s));
         // skip the remaining launches once every codeword stopped (ActivePoll: the flags after iterations 3, 7,
         // 11, ..., read one iteration later)
         bool stopped = false;
@@ -562,36 +523,31 @@ static int param_checks(double awgn_var, int t_max, double rtol, int phi_method)
     return SG_OK;
 }
 
-// Every refusal of the partial decode that needs no device (header, sg_amp_decode_partial_device)
-static int partial_checks(const sg_amp_plan *p, double awgn_var, int t_max, double rtol, int phi_method) {
-    if (p->ndim == 2)
+// Every refusal of an operator-loop decode that needs no device (header, sg_amp_decode_partial_device and
+// sg_amp_decode_bpsk_device).  The merged kernels would serve a spatially coupled W with known sections; nothing
+// holds that against a reference yet, so it stays refused.
+static int oploop_checks(const sg_amp_plan *p, SectionRule rule, double awgn_var, int t_max, double rtol,
+                         int phi_method) {
+    if (rule == SectionRule::Known && p->ndim == 2)
         return fail(SG_ERR_UNSUPPORTED, "AMP with known sections takes a flat or power-allocated design (W of ndim 0 "
                     "or 1), not a spatially coupled one");
     if (p->M < 2 || (p->M & (p->M - 1)) != 0 || p->M > 2048)
-        return fail(SG_ERR_UNSUPPORTED, "section size M = %d: the partial section kernel takes a power of two in "
-                    "[2, 2048]", p->M);
-    return param_checks(awgn_var, t_max, rtol, phi_method);
-}
-
-// Every refusal of the K = 2 decode that needs no device (header, sg_amp_decode_bpsk_device)
-static int bpsk_checks(const sg_amp_plan *p, double awgn_var, int t_max, double rtol, int phi_method) {
-    if (p->M < 2 || (p->M & (p->M - 1)) != 0 || p->M > 2048)
-        return fail(SG_ERR_UNSUPPORTED, "section size M = %d: the K = 2 section kernel takes a power of two in "
-                    "[2, 2048]", p->M);
+        return fail(SG_ERR_UNSUPPORTED, "section size M = %d: the %s section kernel takes a power of two in "
+                    "[2, 2048]", p->M, rule_name(rule));
     return param_checks(awgn_var, t_max, rtol, phi_method);
 }
 
 // The host side of a decode, after the entry point's refusals: y (and the known and true sections) into the plan's
-// buffers, the decode there, the results back.  known_idx null: decode_impl; given: partial_impl; bpsk: bpsk_impl
-// (true_idx, map_idx then hold section words).
-static int decode_host(sg_amp_plan *p, const double *y, int B, const int32_t *known_idx, const int32_t *true_idx,
-                       double awgn_var, int t_max, double rtol, int phi_method, int32_t *map_idx, int32_t *t_final,
-                       double *nmse, double *psi, bool bpsk = false) {
+// buffers, the decode there, the results back.  No rule: decode_impl; a rule: oploop_impl with it (known_idx for
+// Known; for Bpsk true_idx and map_idx hold section words).
+static int decode_host(sg_amp_plan *p, const double *y, int B, std::optional<SectionRule> rule,
+                       const int32_t *known_idx, const int32_t *true_idx, double awgn_var, int t_max, double rtol,
+                       int phi_method, int32_t *map_idx, int32_t *t_final, double *nmse, double *psi) {
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = lib_stream();
     // (the workspace before the staging buffer: growing the workspace frees io too)
     SG_TRY(ensure_ws(p, B, t_max));
-    if (known_idx || bpsk) SG_TRY(partial_ensure_ws(p, B));
+    if (rule) SG_TRY(partial_ensure_ws(p, B));
     const size_t ny = (size_t)B * p->n, nsec = (size_t)B * p->L;
     SG_TRY(ensure_io(p, ny * sizeof(double)));
     SG_HIP(hipMemcpyAsync(p->io.at(), y, ny * sizeof(double), hipMemcpyHostToDevice, s));
@@ -602,8 +558,8 @@ static int decode_host(sg_amp_plan *p, const double *y, int B, const int32_t *kn
         SG_TRY(amp_launch_cast<T>(p->io.at(), 1, (T *)p->ws_y, ny, s));
         const DecodeArgs a{p->ws_y, B, true_idx ? p->ws_true : nullptr, awgn_var, t_max, rtol, phi_method,
                            nullptr, nullptr, nullptr, nullptr};
-        if (bpsk) return bpsk_impl<T>(p, a, s);
-        return known_idx ? partial_impl<T>(p, a, p->wp_known, s) : decode_impl<T>(p, a, s);
+        if (!rule) return decode_impl<T>(p, a, s);
+        return oploop_impl<T>(p, a, *rule, known_idx ? p->wp_known : nullptr, s);
     }));
     SG_HIP(hipMemcpyAsync(map_idx, p->ws_argmax, sizeof(int32_t) * nsec, hipMemcpyDeviceToHost, s));
     SG_HIP(hipMemcpyAsync(t_final, p->ws_tfinal, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
@@ -669,6 +625,21 @@ static void reset_last(sg_amp_plan *p) {
     }
 }
 
+// What the four entry points of the operator-loop decoder share: every refusal that needs no buffer, then `body`
+// on the call's stream (the host variants go on through decode_host, on the library's).  The call clears the
+// last-decode state: the loop runs in the workspace that holds a decode's final state.
+template <typename Body>
+static int oploop_entry(sg_amp_plan *p, SectionRule rule, int B, double awgn_var, int t_max, double rtol,
+                        int phi_method, void *stream, Body &&body) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    reset_last(p);
+    SG_TRY(oploop_checks(p, rule, awgn_var, t_max, rtol, phi_method));
+    if (B <= 0) return SG_OK;
+    SG_HIP(hipSetDevice(p->device));
+    return body(pick_stream(stream));
+}
+
 extern "C" {
 
 int sg_amp_plan_engine(const sg_amp_plan *p, int B) {
@@ -731,7 +702,8 @@ int sg_amp_decode(sg_amp_plan *p, const double *y, int B, const int32_t *true_id
     sg_amp_plan *const handle = p;
     p = p->last_ran = sg::decode_plan(p, B);
     SG_TRY(ensure_device());
-    SG_TRY(sg::decode_host(p, y, B, nullptr, true_idx, awgn_var, t_max, rtol, phi_method, map_idx, t_final, nmse, psi));
+    SG_TRY(sg::decode_host(p, y, B, std::nullopt, nullptr, true_idx, awgn_var, t_max, rtol, phi_method, map_idx,
+                           t_final, nmse, psi));
     handle->last_B = B;
     return SG_OK;
 }
@@ -739,59 +711,48 @@ int sg_amp_decode(sg_amp_plan *p, const double *y, int B, const int32_t *true_id
 int sg_amp_decode_partial_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_known_idx,
                                  const int32_t *d_true_idx, double awgn_var, int t_max, double rtol, int phi_method,
                                  int32_t *d_map_idx, int32_t *d_t_final, double *d_nmse, double *d_psi, void *stream) {
-    SG_TRY(ensure_device());
-    SG_CHECK_ARG(p, "plan is NULL");
-    reset_last(p);  // (the loop runs in the workspace that holds a decode's final state)
-    SG_TRY(sg::partial_checks(p, awgn_var, t_max, rtol, phi_method));
-    if (B <= 0) return SG_OK;
-    SG_CHECK_ARG(d_y && d_known_idx, "d_y or d_known_idx is NULL");
-    SG_HIP(hipSetDevice(p->device));
-    hipStream_t s = pick_stream(stream);
-    const DecodeArgs a{d_y, B, d_true_idx, awgn_var, t_max, rtol, phi_method, d_map_idx, d_t_final, d_nmse, d_psi};
-    return by_precision(p->precision, [&](auto t) { return partial_impl<decltype(t)>(p, a, d_known_idx, s); });
+    return oploop_entry(p, SectionRule::Known, B, awgn_var, t_max, rtol, phi_method, stream, [&](hipStream_t s) {
+        SG_CHECK_ARG(d_y && d_known_idx, "d_y or d_known_idx is NULL");
+        const DecodeArgs a{d_y, B, d_true_idx, awgn_var, t_max, rtol, phi_method, d_map_idx, d_t_final, d_nmse, d_psi};
+        return by_precision(p->precision, [&](auto t) {
+            return oploop_impl<decltype(t)>(p, a, SectionRule::Known, d_known_idx, s);
+        });
+    });
 }
 
 int sg_amp_decode_partial(sg_amp_plan *p, const double *y, int B, const int32_t *known_idx, const int32_t *true_idx,
                           double awgn_var, int t_max, double rtol, int phi_method, int32_t *map_idx, int32_t *t_final,
                           double *nmse, double *psi) {
-    SG_TRY(ensure_device());
-    SG_CHECK_ARG(p, "plan is NULL");
-    reset_last(p);
-    SG_TRY(sg::partial_checks(p, awgn_var, t_max, rtol, phi_method));
-    if (B <= 0) return SG_OK;
-    SG_CHECK_ARG(y && known_idx && map_idx && t_final && nmse && psi, "null host buffer");
-    for (size_t i = 0; i < (size_t)B * p->L; ++i)
-        SG_CHECK_ARG(known_idx[i] >= -1 && known_idx[i] < p->M, "known_idx[%zu] = %d outside [-1, %d)", i,
-                     (int)known_idx[i], p->M);
-    return sg::decode_host(p, y, B, known_idx, true_idx, awgn_var, t_max, rtol, phi_method, map_idx, t_final, nmse,
-                           psi);
+    return oploop_entry(p, SectionRule::Known, B, awgn_var, t_max, rtol, phi_method, nullptr, [&](hipStream_t) {
+        SG_CHECK_ARG(y && known_idx && map_idx && t_final && nmse && psi, "null host buffer");
+        for (size_t i = 0; i < (size_t)B * p->L; ++i)
+            SG_CHECK_ARG(known_idx[i] >= -1 && known_idx[i] < p->M, "known_idx[%zu] = %d outside [-1, %d)", i,
+                         (int)known_idx[i], p->M);
+        return sg::decode_host(p, y, B, SectionRule::Known, known_idx, true_idx, awgn_var, t_max, rtol, phi_method,
+                               map_idx, t_final, nmse, psi);
+    });
 }
 
 int sg_amp_decode_bpsk_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_true_word, double awgn_var,
                               int t_max, double rtol, int phi_method, int32_t *d_map_word, int32_t *d_t_final,
                               double *d_nmse, double *d_psi, void *stream) {
-    SG_TRY(ensure_device());
-    SG_CHECK_ARG(p, "plan is NULL");
-    reset_last(p);  // (the loop runs in the workspace that holds a decode's final state)
-    SG_TRY(sg::bpsk_checks(p, awgn_var, t_max, rtol, phi_method));
-    if (B <= 0) return SG_OK;
-    SG_CHECK_ARG(d_y, "d_y is NULL");
-    SG_HIP(hipSetDevice(p->device));
-    hipStream_t s = pick_stream(stream);
-    const DecodeArgs a{d_y, B, d_true_word, awgn_var, t_max, rtol, phi_method, d_map_word, d_t_final, d_nmse, d_psi};
-    return by_precision(p->precision, [&](auto t) { return bpsk_impl<decltype(t)>(p, a, s); });
+    return oploop_entry(p, SectionRule::Bpsk, B, awgn_var, t_max, rtol, phi_method, stream, [&](hipStream_t s) {
+        SG_CHECK_ARG(d_y, "d_y is NULL");
+        const DecodeArgs a{d_y, B, d_true_word, awgn_var, t_max, rtol, phi_method, d_map_word, d_t_final, d_nmse,
+                           d_psi};
+        return by_precision(p->precision, [&](auto t) {
+            return oploop_impl<decltype(t)>(p, a, SectionRule::Bpsk, nullptr, s);
+        });
+    });
 }
 
 int sg_amp_decode_bpsk(sg_amp_plan *p, const double *y, int B, const int32_t *true_word, double awgn_var, int t_max,
                        double rtol, int phi_method, int32_t *map_word, int32_t *t_final, double *nmse, double *psi) {
-    SG_TRY(ensure_device());
-    SG_CHECK_ARG(p, "plan is NULL");
-    reset_last(p);
-    SG_TRY(sg::bpsk_checks(p, awgn_var, t_max, rtol, phi_method));
-    if (B <= 0) return SG_OK;
-    SG_CHECK_ARG(y && map_word && t_final && nmse && psi, "null host buffer");
-    return sg::decode_host(p, y, B, nullptr, true_word, awgn_var, t_max, rtol, phi_method, map_word, t_final, nmse, psi,
-                           true);
+    return oploop_entry(p, SectionRule::Bpsk, B, awgn_var, t_max, rtol, phi_method, nullptr, [&](hipStream_t) {
+        SG_CHECK_ARG(y && map_word && t_final && nmse && psi, "null host buffer");
+        return sg::decode_host(p, y, B, SectionRule::Bpsk, nullptr, true_word, awgn_var, t_max, rtol, phi_method,
+                               map_word, t_final, nmse, psi);
+    });
 }
 
 int sg_concat_known_sections_device(int precision, const void *d_app, const int32_t *d_it, int max_it, int B, int mults,

@@ -264,7 +264,7 @@ class SparcTrial:
     the Philox stream of block b at point p is (p, b), so results do not
     depend on the rank count.  op: sparc.DesignOperator (shared design).
 
-    K = 2: the real BPSK-modulated SPARC on the same design (csrc/amp_bpsk.hip,
+    K = 2: the real BPSK-modulated SPARC on the same design (csrc/amp_oploop.hip,
     the staged path): log2 M + 1 bits per section, the section word
     (location << 1) | symbol in the place of the index, so a section error is
     a wrong location or a wrong sign."""

@@ -19,7 +19,7 @@ complex design raises NotImplementedError.  Also out of scope, raising
 NotImplementedError: K > 64.
 
 Real K=2 (BPSK) modulated SPARCs -- the DCT design with section entries +1 or
--1 -- decode on the GPU in either precision (csrc/amp_bpsk.hip, flat,
+-1 -- decode on the GPU in either precision (csrc/amp_oploop.hip, flat,
 power-allocated and spatially coupled designs): amp_decode_bpsk_batch, and
 montecarlo.SparcTrial(..., K=2) for campaigns.  Through the drop-in functions
 (sparc_encode, sparc_amp, sparc_decode, sparc_sim.sparc_sim) the family is

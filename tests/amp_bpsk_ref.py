@@ -1,5 +1,5 @@
 """The yardstick of the real K = 2 (BPSK) modulated AMP decode
-(sg_amp_decode_bpsk*, amp_bpsk.hip): a NumPy restatement per codeword on
+(sg_amp_decode_bpsk*, amp_oploop.hip): a NumPy restatement per codeword on
 oracle.sparc_ref's DCT operators.
 
 amp_bpsk is oracle.sparc_ref.amp (sparc.py:883-999) operation for operation,

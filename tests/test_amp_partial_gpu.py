@@ -1,5 +1,5 @@
 """GPU tests of the AMP decode with known sections (sg_amp_decode_partial*,
-amp_partial.hip), the BP -> known-sections glue
+amp_oploop.hip), the BP -> known-sections glue
 (sg_concat_known_sections_device) and the three-stage concatenated decoder
 built on them (pipeline.DctConcat3Pipeline).
 

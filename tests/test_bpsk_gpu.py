@@ -1,5 +1,5 @@
 """GPU tests of the real K = 2 (BPSK) modulated AMP decode (sg_amp_decode_bpsk*,
-sg_amp_encode_bpsk_device, amp_bpsk.hip), of the drop-in surface behind
+sg_amp_encode_bpsk_device, amp_oploop.hip), of the drop-in surface behind
 sparc.enable_real_psk() and of montecarlo.SparcTrial(K=2).
 
 The yardsticks are the reference's fixture tests/golden/bpsk_golden.npz (every

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Time per AMP iteration of the real K = 2 (BPSK) modulated decode
-(sg_amp_decode_bpsk_device, csrc/amp_bpsk.hip) against
+(sg_amp_decode_bpsk_device, csrc/amp_oploop.hip) against
 sg_amp_decode_partial_device with no section known on the same plan and
 batch: L = 1024, M = 512, n = 6144 (R = 1.5 in unmodulated terms), flat design,
 B = 256, both precisions.
