@@ -30,6 +30,15 @@
 //           the section statistics
 //   control (one workgroup per codeword): Onsager residual, phi, tau, psi,
 //           NMSE, early stop (sparc.py:931-988) with complex quantities.
+// With known sections (CampBufs::known_idx, sg_camp_decode_partial*) the loop
+// is the same with the denoiser of a known section replaced by its
+// constellation one-hot, started from beta0 = the known one-hots and
+// z0 = y - A beta0: control's initialisation writes beta0, psi0 and gamma0, its
+// phase 0 of iteration 0 takes A beta0 off y, and eta reports a known section's
+// sums and decision without touching its beta.
+// A codeword that stopped is skipped by every kernel, so it keeps its state.
+// Fixed-order reductions, no atomics: a codeword's result does not depend on
+// the batch it is decoded in.
 #include "camp_section.hpp"
 
 namespace sg {
@@ -101,13 +110,35 @@ __global__ __launch_bounds__(512) void cfft_passB_long(CampTables tb, CampBufs b
 // ------------------------------------------------------------------ eta
 // One wavefront per section, lane owns entries lane, lane + 64, ...  The
 // section's x and then its numerators are staged in the lane's own beta
-// entries, so any M runs without per-lane register arrays.
+// entries, so any M runs without per-lane register arrays.  A known section
+// keeps the one-hot the initialisation wrote: sum |beta|^2 = 1, its squared
+// error against the truth, and the known (idx, sym) as the MAP decision.
 __global__ __launch_bounds__(256) void camp_eta(CampTables tb, CampBufs bf) {
     const int cw = blockIdx.y;
     if (!bf.active[cw]) return;
     const int lane = threadIdx.x & 63;
     const int l = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (l >= tb.L) return;
+    int k, ks;
+    if (known_of(bf, (size_t)cw * tb.L + l, tb.M, &k, &ks)) {
+        if (lane != 0) return;
+        const size_t o = (size_t)cw * tb.L + l;
+        const int truth = bf.true_idx ? bf.true_idx[o] : -1;
+        // another entry than the transmitted one: 2; no truth: sum |beta|^2, as below
+        double se = truth >= 0 && truth < tb.M ? 2.0 : 1.0;
+        if (k == truth) {
+            se = 0.0;
+            if (bf.K > 1 && bf.true_sym) {
+                const cxd a = bf.constel[ks], b = bf.constel[bf.true_sym[o]];
+                se = (a.x - b.x) * (a.x - b.x) + (a.y - b.y) * (a.y - b.y);
+            }
+        }
+        bf.sec_sumsq[o] = 1.0;
+        bf.sec_err[o] = se;
+        bf.sec_idx[o] = k;
+        bf.sec_sym[o] = ks;
+        return;
+    }
     const int c = l / (tb.L / tb.Lc);
     const double tau = bf.tau[(size_t)cw * tb.Lc + c];
     const double th = tau / 2;  // s is complex: sparc.py:417-418
@@ -164,24 +195,60 @@ __global__ __launch_bounds__(256) void camp_eta(CampTables tb, CampBufs bf) {
 }
 
 // ------------------------------------------------------------------ control
+// gamma_r of psi (sparc.py:936-939): W psi for a flat design, else dot(W_r, psi) / Lc
+__device__ __forceinline__ double gamma_of_psi(const CampTables &tb, const AmpParams &pr, const double *psi, int r) {
+    if (tb.ndim == 0) return pr.W[0] * psi[0];
+    double acc = 0.0;
+    for (int c = 0; c < tb.Lc; ++c) acc += pr.W[r * tb.Lc + c] * psi[c];
+    return acc / tb.Lc;
+}
+
+// The initialisation of codeword cw by its workgroup: beta = 0 (memset on host), nmse = 1.  With known sections
+// also beta0 = c[sym] at entry idx of each, psi0_c = the share of unknown sections of column block c, and gamma0
+// from psi0 as phase 0 forms every later gamma.
+__device__ __forceinline__ void camp_init(const CampTables &tb, const CampBufs &bf, const AmpScalars &sc,
+                                          const AmpParams &pr, int cw, int tid) {
+    const int Lr = tb.Lr, Lc = tb.Lc;
+    double *psi = sc.psi + (size_t)cw * Lc, *gamma = sc.gamma + (size_t)cw * Lr;
+    double *nmse = sc.nmse + (size_t)cw * pr.t_max * Lc;
+    for (int i = tid; i < pr.t_max * Lc; i += blockDim.x) nmse[i] = 1.0;
+    if (tid == 0) { bf.active[cw] = 1; sc.t_final[cw] = 0; }
+    if (!bf.known_idx) return;
+    const int lane = tid & 63, spc = tb.L / Lc;
+    for (int l = tid; l < tb.L; l += blockDim.x) {
+        int k, ks;
+        if (known_of(bf, (size_t)cw * tb.L + l, tb.M, &k, &ks))
+            bf.beta[(size_t)cw * tb.LM + (size_t)l * tb.M + k] = bf.K > 1 ? bf.constel[ks] : cxd{1.0, 0.0};
+    }
+    for (int c = tid >> 6; c < Lc; c += blockDim.x >> 6) {  // one wavefront per column block
+        double unk = 0.0;
+        for (int l = c * spc + lane; l < (c + 1) * spc; l += 64) {
+            int k, ks;
+            unk += known_of(bf, (size_t)cw * tb.L + l, tb.M, &k, &ks) ? 0.0 : 1.0;
+        }
+        unk = wave_sum(unk);
+        if (lane == 0) psi[c] = unk / spc;
+    }
+    __syncthreads();
+    for (int r = tid; r < Lr; r += blockDim.x) gamma[r] = gamma_of_psi(tb, pr, psi, r);
+}
+
 // phase 0 (before Az, iteration t): Onsager residual and phi / tau
 // (sparc.py:932-969); phase 1 (after eta): psi, NMSE, stopping
-// (sparc.py:976-988); phase 2: initialisation.
+// (sparc.py:976-988); phase 2: initialisation (camp_init; taken before the
+// other phases form their pointers, which keeps the kernel within 100 SGPRs
+// and eight waves per SIMD).
 __global__ __launch_bounds__(1024) void camp_control(CampTables tb, CampBufs bf, AmpScalars sc, AmpParams pr, int phase,
                                                      int t) {
     __shared__ double red[16];
     const int cw = blockIdx.x, tid = threadIdx.x;
+    if (phase == 2) return camp_init(tb, bf, sc, pr, cw, tid);
     const int Lr = tb.Lr, Lc = tb.Lc;
     double *psi = sc.psi + (size_t)cw * Lc, *psi_prev = sc.psi_prev + (size_t)cw * Lc;
     double *phi = bf.phi + (size_t)cw * Lr, *phi_prev = sc.phi_prev + (size_t)cw * Lr;
     double *gamma = sc.gamma + (size_t)cw * Lr, *bco = sc.bcoef + (size_t)cw * Lr;
     double *tau = bf.tau + (size_t)cw * Lc;
     double *nmse = sc.nmse + (size_t)cw * pr.t_max * Lc;
-    if (phase == 2) {  // init: beta = 0 (memset on host), nmse = 1
-        for (int i = tid; i < pr.t_max * Lc; i += blockDim.x) nmse[i] = 1.0;
-        if (tid == 0) { bf.active[cw] = 1; sc.t_final[cw] = 0; }
-        return;
-    }
     if (!bf.active[cw]) return;
     if (phase == 0) {
         cxd *z = bf.z + (size_t)cw * tb.n;
@@ -189,13 +256,7 @@ __global__ __launch_bounds__(1024) void camp_control(CampTables tb, CampBufs bf,
         if (t > 0) {
             for (int r = tid; r < Lr; r += blockDim.x) {
                 phi_prev[r] = phi[r];
-                double g;
-                if (tb.ndim == 0) g = pr.W[0] * psi[0];
-                else {
-                    double acc = 0.0;
-                    for (int c = 0; c < Lc; ++c) acc += pr.W[r * Lc + c] * psi[c];
-                    g = acc / Lc;
-                }
+                const double g = gamma_of_psi(tb, pr, psi, r);
                 gamma[r] = g;
                 bco[r] = g / phi[r];
             }
@@ -207,6 +268,13 @@ __global__ __launch_bounds__(1024) void camp_control(CampTables tb, CampBufs bf,
                 const double b = bco[r];
                 const cxd yv = y[i], zv = z[i];
                 z[i] = cxd{(yv.x - ab.x) + b * zv.x, (yv.y - ab.y) + b * zv.y};
+            }
+        } else if (bf.known_idx) {  // z0 = y - A beta0, no Onsager term; gamma0 is the initialisation's
+            for (int i = tid; i < tb.n; i += blockDim.x) {
+                const int r = i / tb.Mr;
+                const cxd ab = gather_ab(tb, bf, cw, r, i - r * tb.Mr);
+                const cxd yv = y[i];
+                z[i] = cxd{yv.x - ab.x, yv.y - ab.y};
             }
         } else {
             for (int i = tid; i < tb.n; i += blockDim.x) z[i] = y[i];

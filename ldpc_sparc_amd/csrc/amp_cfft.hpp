@@ -59,6 +59,11 @@ struct CampBufs {
     int32_t *sec_sym;    // [B][L] MAP constellation index of s per section
     const int32_t *true_idx, *true_sym;  // [B][L] or null
     cxd *s_keep;         // [B][LM] natural order: eta also stores s = beta + tau u here (soft output), or null
+    // Known sections (sg_camp_decode_partial*), or null: nothing given.  known_idx [B][L]: a location in [0, M),
+    // anything else: a section to decode; known_sym [B][L]: its constellation index, taken modulo K (null for K = 1).
+    // Given, the control kernel's initialisation writes their one-hots as beta0 with psi0 and gamma0, its phase 0 of
+    // iteration 0 starts from z0 = y - A beta0 (buf1: the forward transforms of beta0), and eta keeps them as they are.
+    const int32_t *known_idx, *known_sym;
 };
 
 int camp_prepare_fft(const CampTables &tb);  // once per plan: geometry check, LDS limit of the long-row pass B
@@ -88,18 +93,6 @@ int camp_launch_llr(const cxd *s, const double *tau, int B, int L, int Lc, int M
 int camp_launch_bits_to_psk_strided(const uint8_t *bits, size_t bit_stride, int B, int L, int logM, int logK,
                                     int32_t *idx, int32_t *sym, size_t idx_stride, hipStream_t s);
 int camp_launch_pack(const int32_t *idx, const int32_t *sym, int B, int L, int logK, int32_t *word, hipStream_t s);
-// AMP with known sections (camp_partial.hip).  known_idx [B][L]: a location in [0, M), anything else: a section to
-// decode; known_sym [B][L]: its constellation index, taken modulo K (null for K = 1).
-//   init   beta0 = the known one-hots into bf.beta (zeroed by the caller), psi0, gamma0, nmse = 1, active = 1
-//   start  iteration 0 after camp_launch_fft(.., false): z0 = y - Ab(beta0), phi, tau
-//   eta    camp_launch_eta with the known sections kept as they are
-// Iterations t >= 1 run camp_launch_control's phase 0, every iteration its phase 1.
-int camp_part_launch_init(const CampTables &tb, const CampBufs &bf, const AmpScalars &sc, const AmpParams &pr,
-                          const int32_t *known_idx, const int32_t *known_sym, hipStream_t s);
-int camp_part_launch_start(const CampTables &tb, const CampBufs &bf, const AmpScalars &sc, const AmpParams &pr,
-                           hipStream_t s);
-int camp_part_launch_eta(const CampTables &tb, const CampBufs &bf, const int32_t *known_idx, const int32_t *known_sym,
-                         hipStream_t s);
 // the inverse of camp_launch_pack: word < 0 -> idx = -1, sym = 0; else idx = word >> logK, sym = gray2bin of the low
 // logK bits (sym may be null)
 int camp_launch_unpack(const int32_t *word, int B, int L, int logK, int32_t *idx, int32_t *sym, hipStream_t s);

@@ -1,6 +1,6 @@
 // Soft output of the complex AMP engine (DESIGN.md "Soft output of the complex
-// engine") and the two small kernels a concatenated K-PSK SPARC + LDPC
-// campaign needs around it, double precision.
+// engine") and the small kernels a concatenated K-PSK SPARC + LDPC campaign
+// needs around it (section bits, section words and back), double precision.
 //
 // For K >= 2 the engine's final beta is the conditional mean sum_k p(j,k) c_k,
 // not a posterior, so the bit marginals come from the joint posterior over
@@ -122,6 +122,17 @@ __global__ __launch_bounds__(256) void psk_pack_kernel(const int32_t *__restrict
     }
 }
 
+// word -> (idx, sym), the inverse of psk_pack_kernel; a negative word is "unknown": idx = -1, sym = 0
+__global__ __launch_bounds__(256) void psk_unpack_kernel(const int32_t *__restrict__ word, size_t total, int logK,
+                                                         int32_t *__restrict__ idx, int32_t *__restrict__ sym) {
+    const int mK = (1 << logK) - 1;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int w = word[i];
+        idx[i] = w < 0 ? -1 : w >> logK;
+        if (sym) sym[i] = w < 0 ? 0 : gray_to_bin(w & mK);
+    }
+}
+
 unsigned grid_of(size_t items) { return (unsigned)std::max<size_t>(1, std::min<size_t>(1024, (items + 255) / 256)); }
 
 }  // namespace
@@ -154,6 +165,14 @@ int camp_launch_pack(const int32_t *idx, const int32_t *sym, int B, int L, int l
     const size_t total = (size_t)B * L;
     if (total == 0) return SG_OK;
     hipLaunchKernelGGL(psk_pack_kernel, dim3(grid_of(total)), dim3(256), 0, s, idx, sym, total, logK, word);
+    SG_HIP(hipGetLastError());
+    return SG_OK;
+}
+
+int camp_launch_unpack(const int32_t *word, int B, int L, int logK, int32_t *idx, int32_t *sym, hipStream_t s) {
+    const size_t total = (size_t)B * L;
+    if (total == 0) return SG_OK;
+    hipLaunchKernelGGL(psk_unpack_kernel, dim3(grid_of(total)), dim3(256), 0, s, word, total, logK, idx, sym);
     SG_HIP(hipGetLastError());
     return SG_OK;
 }

@@ -1,10 +1,20 @@
-// Device code shared by the complex AMP engine's kernels (amp_cfft.hip) and its loop with known sections
-// (camp_partial.hip): the operator's single-bin gathers, the K-PSK section estimators, the Gray code of the symbol
-// bits.  All __forceinline__: the kernels compile to the same code as with a private copy.
+// Device code shared by the complex AMP engine's kernels (amp_cfft.hip), its soft output (camp_llr.hip) and its
+// campaign kernels (camp_campaign.hip): the operator's single-bin gathers, the known sections of a decode, the K-PSK
+// section estimators, the Gray code of the symbol bits.  All __forceinline__: the kernels compile to the same code
+// as with a private copy.
 #pragma once
 #include "amp_cfft.hpp"
 
 namespace sg {
+
+// known (location, constellation index) of section o = cw L + l, or false: nothing is known without
+// CampBufs::known_idx, a location outside [0, M) is unknown, the constellation index is taken modulo K
+__device__ __forceinline__ bool known_of(const CampBufs &bf, size_t o, int M, int *k, int *ks) {
+    if (!bf.known_idx) return false;
+    *k = bf.known_idx[o];
+    *ks = bf.K > 1 ? bf.known_sym[o] & (bf.K - 1) : 0;
+    return *k >= 0 && *k < M;
+}
 
 // (A beta)_i of row block r summed over the row's transforms in table order
 __device__ __forceinline__ cxd gather_ab(const CampTables &tb, const CampBufs &bf, int cw, int r, int il) {

@@ -131,6 +131,7 @@ CampBufs bufs(const sg_camp_plan *p, int B, int K) {
     bf.sec_sumsq = p->sec_sumsq; bf.sec_err = p->sec_err; bf.sec_idx = p->sec_idx; bf.sec_sym = p->sec_sym;
     bf.true_idx = nullptr; bf.true_sym = nullptr;
     bf.s_keep = nullptr;  // only a decode with soft output on sets it
+    bf.known_idx = bf.known_sym = nullptr;  // only a decode with known sections sets them
     return bf;
 }
 
@@ -196,12 +197,29 @@ int set_constel(sg_camp_plan *p, int K, const double *constel, hipStream_t s) {
     return SG_OK;
 }
 
-// Every refusal of the partial decode that its two variants share: sg_camp_decode_device's, before any launch
-int partial_checks(int B, int K, const double *constel, double awgn_var, int t_max, double rtol, int phi_method) {
-    SG_CHECK_ARG(B <= CAMP_MAX_B, "batch must be at most 65535");
-    SG_TRY(decode_param_checks(K, awgn_var, t_max, rtol, phi_method));
-    SG_CHECK_ARG(K == 1 || constel, "K > 1 needs the constellation");
-    return SG_OK;
+// What the four decode entry points share, then body(): the device, the plan, the reset of the soft-output state
+// (every decode call makes it; a completed plain decode sets the state again), the refusals of the batch and the
+// scalars, hipSetDevice.  The plain entries refuse a negative batch and return on an empty one before they look at
+// anything else; those with known sections (part) refuse the scalars first and return on any B <= 0.  Either then
+// wants the arrays that every K needs (have, or the refusal `missing`); the checks that depend on K are body()'s.
+template <class Body>
+int decode_entry(sg_camp_plan *p, bool part, int B, int K, const double *constel, double awgn_var, int t_max,
+                 double rtol, int phi_method, bool have, const char *missing, Body &&body) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    p->last_B = p->last_K = 0;
+    if (part) {
+        SG_CHECK_ARG(B <= CAMP_MAX_B, "batch must be at most 65535");
+        SG_TRY(decode_param_checks(K, awgn_var, t_max, rtol, phi_method));
+        SG_CHECK_ARG(K == 1 || constel, "K > 1 needs the constellation");
+    } else {
+        SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B, "batch must be in [0, 65535]");
+    }
+    if (B <= 0) return SG_OK;
+    SG_CHECK_ARG(have, "%s", missing);
+    if (!part) SG_TRY(decode_param_checks(K, awgn_var, t_max, rtol, phi_method));
+    SG_HIP(hipSetDevice(p->device));
+    return body();
 }
 
 // What a decode is asked for, in the order of sg_camp_decode_partial_device's arguments (results: null if not
@@ -213,13 +231,12 @@ struct CampArgs {
     int32_t *d_map_idx, *d_map_sym, *d_t_final; double *d_nmse, *d_psi;
 };
 
-// The AMP decode on device arrays, after the entry point's refusals.  With known sections (camp_partial.hip) the
-// initialisation builds beta0 from them, iteration 0 runs the forward transform of beta0 too and has its own
-// residual kernel, and the eta kernel keeps them fixed; s_keep is then not refilled.
+// The AMP decode on device arrays, after the entry point's refusals.  The known sections reach the kernels through
+// CampBufs (amp_cfft.hpp); the driver's part is the forward transform of beta0 at iteration 0, which the plain decode
+// (beta0 = 0) skips, and s_keep, which a decode with known sections does not refill.
 int decode_impl(sg_camp_plan *p, const CampArgs &a, hipStream_t s) {
     const int B = a.B, K = a.K, t_max = a.t_max;
     const bool part = a.d_known_idx != nullptr;
-    const int32_t *ksym = K > 1 ? a.d_known_sym : nullptr;
     SG_TRY(ensure_ws(p, B, t_max));
     SG_TRY(set_constel(p, K, a.constel, s));
     const CampTables tb = tables(p);
@@ -231,6 +248,8 @@ int decode_impl(sg_camp_plan *p, const CampArgs &a, hipStream_t s) {
     bf.true_idx = a.d_true_idx;
     bf.true_sym = (K > 1 && a.d_true_idx) ? a.d_true_sym : nullptr;
     bf.s_keep = (p->soft && !part) ? p->s_keep : nullptr;
+    bf.known_idx = a.d_known_idx;
+    bf.known_sym = K > 1 ? a.d_known_sym : nullptr;
     AmpScalars sc;
     sc.psi = a.d_psi ? a.d_psi : p->psi; sc.psi_prev = p->psi_prev; sc.phi_prev = p->phi_prev; sc.gamma = p->gamma;
     sc.bcoef = p->bco;
@@ -242,16 +261,13 @@ int decode_impl(sg_camp_plan *p, const CampArgs &a, hipStream_t s) {
     SG_HIP(hipMemsetAsync(p->beta, 0, (size_t)B * p->LM * sizeof(cxd), s));
     SG_HIP(hipMemsetAsync(bf.sec_idx, 0, sizeof(int32_t) * B * p->L, s));
     SG_HIP(hipMemsetAsync(bf.sec_sym, 0, sizeof(int32_t) * B * p->L, s));
-    if (part) SG_TRY(camp_part_launch_init(tb, bf, sc, pr, a.d_known_idx, ksym, s));
-    else SG_TRY(camp_launch_control(tb, bf, sc, pr, 2, 0, s));
+    SG_TRY(camp_launch_control(tb, bf, sc, pr, 2, 0, s));
     std::vector<int32_t> act(B);
     for (int t = 0; t < t_max - 1; ++t) {
         if (t > 0 || part) SG_TRY(camp_launch_fft(tb, bf, false, s));
-        if (t == 0 && part) SG_TRY(camp_part_launch_start(tb, bf, sc, pr, s));
-        else SG_TRY(camp_launch_control(tb, bf, sc, pr, 0, t, s));
+        SG_TRY(camp_launch_control(tb, bf, sc, pr, 0, t, s));
         SG_TRY(camp_launch_fft(tb, bf, true, s));
-        if (part) SG_TRY(camp_part_launch_eta(tb, bf, a.d_known_idx, ksym, s));
-        else SG_TRY(camp_launch_eta(tb, bf, s));
+        SG_TRY(camp_launch_eta(tb, bf, s));
         SG_TRY(camp_launch_control(tb, bf, sc, pr, 1, t, s));
         if (t % 4 == 3 && t + 1 < t_max - 1) {  // skip the remaining launches once every codeword stopped
             SG_HIP(hipMemcpyAsync(act.data(), p->active, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
@@ -271,7 +287,6 @@ int decode_host(sg_camp_plan *p, const double *y, int B, int K, const double *co
                 double rtol, int phi_method, int32_t *map_idx, int32_t *map_sym, int32_t *t_final, double *nmse,
                 double *psi) {
     const size_t nsec = (size_t)B * p->L;
-    SG_HIP(hipSetDevice(p->device));
     hipStream_t s = lib_stream();
     SG_TRY(ensure_ws(p, B, t_max));
     if (known_idx) SG_TRY(ensure_known(p, B));
@@ -437,21 +452,16 @@ int sg_camp_decode_device(sg_camp_plan *p, const void *d_y, int B, int K, const 
                           const int32_t *d_true_idx, const int32_t *d_true_sym, double awgn_var, int t_max, double rtol,
                           int phi_method, int32_t *d_map_idx, int32_t *d_map_sym, int32_t *d_t_final, double *d_nmse,
                           double *d_psi, void *stream) {
-    SG_TRY(ensure_device());
-    SG_CHECK_ARG(p, "plan is NULL");
-    p->last_B = p->last_K = 0;  // every decode call resets the soft-output state; a completed one sets it below
-    SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B, "batch must be in [0, 65535]");
-    if (B == 0) return SG_OK;
-    SG_CHECK_ARG(d_y, "null received words");
-    SG_TRY(decode_param_checks(K, awgn_var, t_max, rtol, phi_method));
-    SG_CHECK_ARG(K == 1 || constel, "K > 1 needs the constellation");
-    SG_CHECK_ARG(K == 1 || !d_true_idx || d_true_sym, "K > 1 with true_idx needs true_sym");
-    SG_HIP(hipSetDevice(p->device));
-    const CampArgs a{d_y, B, K, constel, nullptr, nullptr, d_true_idx, d_true_sym, awgn_var, t_max, rtol, phi_method,
-                     d_map_idx, d_map_sym, d_t_final, d_nmse, d_psi};
-    SG_TRY(decode_impl(p, a, pick_stream(stream)));
-    if (p->soft) { p->last_B = B; p->last_K = K; }
-    return SG_OK;
+    return decode_entry(p, false, B, K, constel, awgn_var, t_max, rtol, phi_method, d_y != nullptr,
+                        "null received words", [&]() -> int {
+        SG_CHECK_ARG(K == 1 || constel, "K > 1 needs the constellation");
+        SG_CHECK_ARG(K == 1 || !d_true_idx || d_true_sym, "K > 1 with true_idx needs true_sym");
+        const CampArgs a{d_y, B, K, constel, nullptr, nullptr, d_true_idx, d_true_sym, awgn_var, t_max, rtol,
+                         phi_method, d_map_idx, d_map_sym, d_t_final, d_nmse, d_psi};
+        SG_TRY(decode_impl(p, a, pick_stream(stream)));
+        if (p->soft) { p->last_B = B; p->last_K = K; }
+        return SG_OK;
+    });
 }
 
 // The decode with the known sections given: sg_camp_decode_device's driver; the soft-output state stays cleared
@@ -461,67 +471,56 @@ int sg_camp_decode_partial_device(sg_camp_plan *p, const void *d_y, int B, int K
                                   const int32_t *d_true_sym, double awgn_var, int t_max, double rtol, int phi_method,
                                   int32_t *d_map_idx, int32_t *d_map_sym, int32_t *d_t_final, double *d_nmse,
                                   double *d_psi, void *stream) {
-    SG_TRY(ensure_device());
-    SG_CHECK_ARG(p, "plan is NULL");
-    p->last_B = p->last_K = 0;
-    SG_TRY(partial_checks(B, K, constel, awgn_var, t_max, rtol, phi_method));
-    if (B <= 0) return SG_OK;
-    SG_CHECK_ARG(d_y && d_known_idx, "d_y or d_known_idx is NULL");
-    SG_CHECK_ARG(K == 1 || d_known_sym, "K > 1 needs d_known_sym");
-    SG_CHECK_ARG(K == 1 || !d_true_idx || d_true_sym, "K > 1 with true_idx needs true_sym");
-    SG_HIP(hipSetDevice(p->device));
-    const CampArgs a{d_y, B, K, constel, d_known_idx, d_known_sym, d_true_idx, d_true_sym, awgn_var, t_max, rtol,
-                     phi_method, d_map_idx, d_map_sym, d_t_final, d_nmse, d_psi};
-    return decode_impl(p, a, pick_stream(stream));
+    return decode_entry(p, true, B, K, constel, awgn_var, t_max, rtol, phi_method, d_y && d_known_idx,
+                        "d_y or d_known_idx is NULL", [&]() -> int {
+        SG_CHECK_ARG(K == 1 || d_known_sym, "K > 1 needs d_known_sym");
+        SG_CHECK_ARG(K == 1 || !d_true_idx || d_true_sym, "K > 1 with true_idx needs true_sym");
+        const CampArgs a{d_y, B, K, constel, d_known_idx, d_known_sym, d_true_idx, d_true_sym, awgn_var, t_max, rtol,
+                         phi_method, d_map_idx, d_map_sym, d_t_final, d_nmse, d_psi};
+        return decode_impl(p, a, pick_stream(stream));
+    });
 }
 
 int sg_camp_decode(sg_camp_plan *p, const double *y, int B, int K, const double *constel, const int32_t *true_idx,
                    const int32_t *true_sym, double awgn_var, int t_max, double rtol, int phi_method, int32_t *map_idx,
                    int32_t *map_sym, int32_t *t_final, double *nmse, double *psi) {
-    SG_TRY(ensure_device());
-    SG_CHECK_ARG(p, "plan is NULL");
-    p->last_B = p->last_K = 0;
-    SG_CHECK_ARG(B >= 0 && B <= CAMP_MAX_B, "batch must be in [0, 65535]");
-    if (B == 0) return SG_OK;
-    SG_CHECK_ARG(y && map_idx && t_final && nmse && psi, "null host buffer");
-    SG_TRY(decode_param_checks(K, awgn_var, t_max, rtol, phi_method));
-    SG_CHECK_ARG(K == 1 || (constel && map_sym), "K > 1 needs the constellation and map_sym");
-    SG_CHECK_ARG(K == 1 || !true_idx || true_sym, "K > 1 with true_idx needs true_sym");
-    if (true_idx)
-        for (size_t i = 0; i < (size_t)B * p->L; ++i) {
-            SG_CHECK_ARG(true_idx[i] >= 0 && true_idx[i] < p->M, "true_idx out of range");
-            SG_CHECK_ARG(K == 1 || (true_sym[i] >= 0 && true_sym[i] < K), "true_sym out of range");
-        }
-    SG_TRY(decode_host(p, y, B, K, constel, nullptr, nullptr, true_idx, true_sym, awgn_var, t_max, rtol, phi_method,
-                       map_idx, map_sym, t_final, nmse, psi));
-    if (p->soft) { p->last_B = B; p->last_K = K; }
-    return SG_OK;
+    return decode_entry(p, false, B, K, constel, awgn_var, t_max, rtol, phi_method,
+                        y && map_idx && t_final && nmse && psi, "null host buffer", [&]() -> int {
+        SG_CHECK_ARG(K == 1 || (constel && map_sym), "K > 1 needs the constellation and map_sym");
+        SG_CHECK_ARG(K == 1 || !true_idx || true_sym, "K > 1 with true_idx needs true_sym");
+        if (true_idx)
+            for (size_t i = 0; i < (size_t)B * p->L; ++i) {
+                SG_CHECK_ARG(true_idx[i] >= 0 && true_idx[i] < p->M, "true_idx out of range");
+                SG_CHECK_ARG(K == 1 || (true_sym[i] >= 0 && true_sym[i] < K), "true_sym out of range");
+            }
+        SG_TRY(decode_host(p, y, B, K, constel, nullptr, nullptr, true_idx, true_sym, awgn_var, t_max, rtol,
+                           phi_method, map_idx, map_sym, t_final, nmse, psi));
+        if (p->soft) { p->last_B = B; p->last_K = K; }
+        return SG_OK;
+    });
 }
 
 int sg_camp_decode_partial(sg_camp_plan *p, const double *y, int B, int K, const double *constel,
                            const int32_t *known_idx, const int32_t *known_sym, const int32_t *true_idx,
                            const int32_t *true_sym, double awgn_var, int t_max, double rtol, int phi_method,
                            int32_t *map_idx, int32_t *map_sym, int32_t *t_final, double *nmse, double *psi) {
-    SG_TRY(ensure_device());
-    SG_CHECK_ARG(p, "plan is NULL");
-    p->last_B = p->last_K = 0;
-    SG_TRY(partial_checks(B, K, constel, awgn_var, t_max, rtol, phi_method));
-    if (B <= 0) return SG_OK;
-    SG_CHECK_ARG(y && known_idx && map_idx && t_final && nmse && psi, "null host buffer");
-    SG_CHECK_ARG(K == 1 || (known_sym && map_sym), "K > 1 needs known_sym and map_sym");
-    SG_CHECK_ARG(K == 1 || !true_idx || true_sym, "K > 1 with true_idx needs true_sym");
-    for (size_t i = 0; i < (size_t)B * p->L; ++i) {
-        SG_CHECK_ARG(known_idx[i] >= -1 && known_idx[i] < p->M, "known_idx[%zu] = %d outside [-1, %d)", i,
-                     (int)known_idx[i], p->M);
-        SG_CHECK_ARG(K == 1 || known_idx[i] < 0 || (known_sym[i] >= 0 && known_sym[i] < K),
-                     "known_sym[%zu] = %d outside [0, %d)", i, K > 1 ? (int)known_sym[i] : 0, K);
-        if (true_idx) {
-            SG_CHECK_ARG(true_idx[i] >= 0 && true_idx[i] < p->M, "true_idx out of range");
-            SG_CHECK_ARG(K == 1 || (true_sym[i] >= 0 && true_sym[i] < K), "true_sym out of range");
+    return decode_entry(p, true, B, K, constel, awgn_var, t_max, rtol, phi_method,
+                        y && known_idx && map_idx && t_final && nmse && psi, "null host buffer", [&]() -> int {
+        SG_CHECK_ARG(K == 1 || (known_sym && map_sym), "K > 1 needs known_sym and map_sym");
+        SG_CHECK_ARG(K == 1 || !true_idx || true_sym, "K > 1 with true_idx needs true_sym");
+        for (size_t i = 0; i < (size_t)B * p->L; ++i) {
+            SG_CHECK_ARG(known_idx[i] >= -1 && known_idx[i] < p->M, "known_idx[%zu] = %d outside [-1, %d)", i,
+                         (int)known_idx[i], p->M);
+            SG_CHECK_ARG(K == 1 || known_idx[i] < 0 || (known_sym[i] >= 0 && known_sym[i] < K),
+                         "known_sym[%zu] = %d outside [0, %d)", i, K > 1 ? (int)known_sym[i] : 0, K);
+            if (true_idx) {
+                SG_CHECK_ARG(true_idx[i] >= 0 && true_idx[i] < p->M, "true_idx out of range");
+                SG_CHECK_ARG(K == 1 || (true_sym[i] >= 0 && true_sym[i] < K), "true_sym out of range");
+            }
         }
-    }
-    return decode_host(p, y, B, K, constel, known_idx, known_sym, true_idx, true_sym, awgn_var, t_max, rtol,
-                       phi_method, map_idx, map_sym, t_final, nmse, psi);
+        return decode_host(p, y, B, K, constel, known_idx, known_sym, true_idx, true_sym, awgn_var, t_max, rtol,
+                           phi_method, map_idx, map_sym, t_final, nmse, psi);
+    });
 }
 
 int sg_bits_to_psk_sections_device(const uint8_t *d_bits, int B, int L, int logM, int logK, int32_t *d_idx,
