@@ -89,8 +89,7 @@ template <typename T>
 int reg_launch_llr(const RegTables<T> &tb, const T *s, const double *tau, int B, int l0, int nl, int llr_ld,
                    int probs_only, T *llr, hipStream_t st) {
     if (B <= 0 || nl <= 0) return SG_OK;
-    int logM = 0;
-    while ((1 << logM) < tb.M) ++logM;
+    const int logM = ilog2(tb.M);
     const dim3 grid((nl + 3) / 4, B), block(256);
     if (tb.M <= 64)
         hipLaunchKernelGGL((reg_llr_kernel<T, 1>), grid, block, 0, st, tb, s, tau, l0, nl, logM, llr_ld, probs_only, llr);

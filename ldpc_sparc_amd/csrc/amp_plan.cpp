@@ -6,12 +6,6 @@
 
 namespace sg {
 
-int ilog2(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
 template <typename R>
 static int upload_cx_as(sg_amp_plan *p, void **dst, const std::vector<cd> &src) {
     std::vector<R> v(2 * src.size());
@@ -20,7 +14,7 @@ static int upload_cx_as(sg_amp_plan *p, void **dst, const std::vector<cd> &src) 
 }
 
 int upload_cx(sg_amp_plan *p, void **dst, const std::vector<cd> &src) {
-    return p->precision == SG_F64 ? upload_cx_as<double>(p, dst, src) : upload_cx_as<float>(p, dst, src);
+    return by_precision(p->precision, [&](auto t) { return upload_cx_as<decltype(t)>(p, dst, src); });
 }
 
 cd expi(double a) { return cd(std::cos(a), std::sin(a)); }
@@ -102,25 +96,6 @@ int diag_skip() {
 }
 
 // ---- workspace: every buffer is a slot of one of the plan's pools (device_mem.hpp), released together
-int integ_ensure_ws(sg_amp_plan *p, int B, int nbits) {
-    if (B <= p->cap_Bi) return SG_OK;
-    p->wi.release();
-    p->cap_Bi = 0;
-    const size_t rs = p->precision == SG_F64 ? 8 : 4, Bz = (size_t)B;
-    SG_TRY(p->wi.alloc(&p->wi_alpha, Bz * p->LM * rs));
-    SG_TRY(p->wi.alloc(&p->wi_gamma, Bz * p->LM * rs));
-    SG_TRY(p->wi.alloc(&p->wi_x, Bz * p->n * rs));
-    SG_TRY(p->wi.alloc(&p->wi_vk0, Bz * nbits * rs));
-    SG_TRY(p->wi.alloc(&p->wi_vk, Bz * nbits * rs));
-    SG_TRY(p->wi.alloc(&p->wi_llr, Bz * nbits * rs));
-    SG_TRY(p->wi.alloc(&p->wi_app, Bz * nbits * rs));
-    SG_TRY(p->wi.alloc(&p->wi_it, Bz * nbits * sizeof(int32_t)));
-    SG_TRY(p->wi.alloc(&p->wi_part, Bz * p->L * sizeof(double)));
-    SG_TRY(p->wi.alloc(&p->wi_ons, Bz * sizeof(double)));
-    p->cap_Bi = B;
-    return SG_OK;
-}
-
 int partial_ensure_ws(sg_amp_plan *p, int B) {
     if (B <= p->cap_Bp) return SG_OK;
     p->wp.release();

@@ -12,6 +12,7 @@
 #include "amp.hpp"
 #include "amp_oploop.hpp"
 #include "device_mem.hpp"
+#include "integ_ws.hpp"
 
 using cd = std::complex<double>;
 
@@ -112,16 +113,8 @@ struct sg_amp_plan {
     int b_ngs = 0;
     void *ws_gbuf = nullptr;  // [B][b_ngs] G slots (block engine)
     void *b_oc = nullptr, *b_gc = nullptr, *b_stw = nullptr;
-    // integrated AMP <-> BP decoders (integrated_dct.hip), grow-only per (plan, B), slots recorded like the
-    // batch workspace's (integ_ensure_ws): u = Az(z) / weighted alpha and gamma [B][LM]; xhat = Ab(beta) [B][n];
-    // vk0, vk, LLRs, app [B][L log M]; BP iteration counts; per-section sums (differentiated eta, or beta^2 of
-    // the naive decoders) and their per-codeword sum
-    sg::DevPool wi;
-    int cap_Bi = 0;
-    void *wi_alpha = nullptr, *wi_gamma = nullptr, *wi_x = nullptr, *wi_vk0 = nullptr, *wi_vk = nullptr,
-         *wi_llr = nullptr, *wi_app = nullptr;
-    int32_t *wi_it = nullptr;
-    double *wi_part = nullptr, *wi_ons = nullptr;
+    // integrated AMP <-> BP decoders (integ_loop.hpp, integrated_dct.hip): their workspace, with the xhat slot
+    sg::IntegWs wi;
     // The operator-loop decoder (amp_oploop.hip: AMP with known sections and real K = 2 modulated AMP), grow-only
     // per (plan, B) like the integrated buffers (partial_ensure_ws): u = Az(z / phi) [B][LM]; r = Ab(beta) and z
     // [B][n]; partial sums of z^2 per row block [B][oploop_zz_count(Lr, Mr)]; per-section sum beta^2 and squared
@@ -138,7 +131,6 @@ struct sg_amp_plan {
 #pragma GCC visibility push(hidden)  // shared between the library's objects, not exported from it
 namespace sg {
 // ---- coefficient math and uploads (amp_plan.cpp)
-int ilog2(int v);
 cd expi(double a);
 cd tw(long long k, long long m);  // exp(-2 pi i k / m) with exact integer reduction of k mod m
 void fwd_coef(long long k, long long N, long long N2, double sc, long long *a, long long *b, cd *c1, cd *c2);
@@ -195,7 +187,6 @@ int build_block2(sg_amp_plan *p, const uint32_t *order0, const uint32_t *order1,
 // ---- workspace, grow-only (amp_plan.cpp)
 int ensure_ws(sg_amp_plan *p, int B, int t_max);
 int ensure_io(sg_amp_plan *p, size_t bytes);
-int integ_ensure_ws(sg_amp_plan *p, int B, int nbits);
 int partial_ensure_ws(sg_amp_plan *p, int B);
 
 // ---- kernel-facing views of a plan and its workspace (T: float, double), each beside its engine's builder

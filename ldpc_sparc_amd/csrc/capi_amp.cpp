@@ -4,13 +4,9 @@
 #include <type_traits>
 
 #include "amp_plan.hpp"
-#include "dense.hpp"
+#include "integ_loop.hpp"
 
 namespace sg {
-
-// f(T{}) with T the real type of a plan's precision
-template <typename F>
-static int by_precision(int precision, F &&f) { return precision == SG_F64 ? f(double{}) : f(float{}); }
 
 // The split engine (amp_cw2.hip) runs the per-codeword engine's iterations
 // when its tables were built; SG_AMP_CW2=0 keeps the one-workgroup form
@@ -409,62 +405,49 @@ static int apply_impl(sg_amp_plan *p, int transpose, const void *d_in, int in_is
     return SG_OK;
 }
 
-// The AMP <-> BP integrated decoders on a flat plan: integ_impl of capi_dense.cpp with the two GEMMs replaced by
-// the plan's operators on natural-order vectors and the three passes eta / bit probabilities / LLRs by one
-// section kernel (integrated_dct.hip).  beta lives in the plan's [B][LM] workspace (ws_s of a regular plan, ws_beta
-// of a general one), z in ws_z; u = Az(z) is written into the alpha buffer, where the section kernel turns it into
-// the weighted alpha.  Nothing but launches and device-to-device copies inside the loop.
+// The front end of integ_loop (integ_loop.hpp) on a flat plan: the plan's operators on natural-order vectors, and
+// one section kernel (integrated_dct.hip) for the dense front end's three passes eta / bit probabilities / LLRs.
+// beta lives in the plan's [B][LM] workspace (ws_s of a regular plan, ws_beta of a general one), z in ws_z, tau^2
+// in the plan's tau slot ([B], Lc = 1); u = Az(z) is written into the alpha buffer, where the section kernel turns
+// it into the weighted alpha.
+template <typename T>
+struct DctFront {
+    sg_amp_plan *p;
+    int B, t_max;
+    const T *y;
+    double *tau_hist;  // [B][t_max] or null
+    double P, snp;
+    DenseBufs<T> db;  // dense_launch_bsq reads beta, the shape and sec_bsq only
+    T *beta() const { return db.beta; }
+    const double *tau() const { return p->ws_tau; }
+    const DenseBufs<T> &bsq_view() const { return db; }
+    int forward(hipStream_t s) { return apply_enqueue<T>(p, 0, db.beta, B, (T *)p->wi.x, s); }  // Ab(beta) = snp A beta
+    int residual(int t, int ons_mode, hipStream_t s) {  // (the kernel writes the history itself)
+        return idct_launch_residual<T>(y, (const T *)p->wi.x, (T *)p->ws_z, B, p->n, p->L, snp, P, ons_mode, p->wi.ons,
+                                       p->wi.part, t, p->ws_tau, tau_hist, t_max, s);
+    }
+    int sections(int, hipStream_t s) {
+        SG_TRY(apply_enqueue<T>(p, 1, (const T *)p->ws_z, B, (T *)p->wi.alpha, s));  // u = Az(z) = snp A^T z
+        return idct_launch_section<T>((T *)p->wi.alpha, db.beta, p->ws_tau, B, p->L, p->M, snp, (T *)p->wi.vk0,
+                                      (T *)p->wi.llr, s);
+    }
+    // 1 / (1 + e^-app), finite for every app: this loop's single-precision LLRs pass the e^app overflow
+    int probs(const T *app, size_t nn, T *vk, hipStream_t s) { return idct_launch_probs<T>(app, nn, vk, s); }
+};
+
 template <typename T>
 static int integ_dct_impl(sg_amp_plan *p, sg_graph *g, int mode, int N, int K, const void *d_y, int B, int t_max,
                           int its, int its_final, uint8_t *d_bits, void *d_app, double *d_tau_hist, hipStream_t s) {
-    const int logM = ilog2(p->M);
-    const int nbits = p->L * logM, nblk = nbits / N;
     SG_TRY(ensure_ws(p, B, 2));
-    SG_TRY(integ_ensure_ws(p, B, nbits));
-    const double P = p->W[0], snp = std::sqrt((double)p->n * (P / p->L));
-    const bool naive = mode == SG_INT_NAIVE || mode == SG_INT_NAIVE_POST;
-    const bool post = mode == SG_INT_NAIVE_POST || mode == SG_INT_DIFF_POST;
-    const int ons_mode = naive ? 0 : (mode == SG_INT_DIFF ? 1 : 2);
-    T *beta = p->regular ? (T *)p->ws_s : (T *)p->ws_beta, *z = (T *)p->ws_z, *xhat = (T *)p->wi_x;
-    T *alpha_w = (T *)p->wi_alpha, *gamma = (T *)p->wi_gamma, *vk0 = (T *)p->wi_vk0, *vk = (T *)p->wi_vk;
-    T *llr = (T *)p->wi_llr, *app = (T *)p->wi_app;
-    const T *y = (const T *)d_y;
-    double *tau = p->ws_tau;  // [B] (Lc = 1): the plan's tau^2 slot
-    const size_t nb = (size_t)B * nbits;
-    const int prec = sizeof(T) == 8 ? SG_F64 : SG_F32;
-    DenseBufs<T> db{};  // dense_launch_bsq reads beta, the shape and sec_bsq only
-    db.L = p->L; db.M = p->M; db.LM = p->LM; db.B = B; db.beta = beta; db.sec_bsq = p->wi_part;
-    SG_HIP(hipMemsetAsync(beta, 0, (size_t)B * p->LM * sizeof(T), s));
+    SG_TRY(p->wi.ensure(B, p->L, p->LM, p->n, p->L * ilog2(p->M), sizeof(T), true));
+    const double P = p->W[0];
+    DctFront<T> front{p, B, t_max, (const T *)d_y, d_tau_hist, P, std::sqrt((double)p->n * (P / p->L)), {}};
+    DenseBufs<T> &db = front.db;
+    db.L = p->L; db.M = p->M; db.LM = p->LM; db.B = B; db.sec_bsq = p->wi.part;
+    db.beta = p->regular ? (T *)p->ws_s : (T *)p->ws_beta;
+    SG_HIP(hipMemsetAsync(front.beta(), 0, (size_t)B * p->LM * sizeof(T), s));
     if (!p->regular) SG_TRY(idct_launch_ones(p->ws_active, B, p->ws_phi, B * p->Lr, s));
-    for (int t = 0; t < t_max; ++t) {
-        if (!naive && t > 0) {  // sum of the differentiated eta with the previous tau^2
-            ProfScope ps(SG_PH_INT_DETA, s);
-            SG_TRY(integ_launch_deta<T>(post ? 1 : 0, beta, gamma, alpha_w, snp, vk, vk0, tau, B, p->L, p->M, snp,
-                                        p->wi_part, p->wi_ons, (T *)nullptr, s));
-        }
-        if (t > 0) SG_TRY(apply_enqueue<T>(p, 0, beta, B, xhat, s));  // xhat = Ab(beta) = snp A beta
-        SG_TRY(idct_launch_residual<T>(y, xhat, z, B, p->n, p->L, snp, P, ons_mode, p->wi_ons, p->wi_part, t, tau,
-                                       d_tau_hist, t_max, s));
-        SG_TRY(apply_enqueue<T>(p, 1, z, B, alpha_w, s));  // u = Az(z) = snp A^T z
-        SG_TRY(idct_launch_section<T>(alpha_w, beta, tau, B, p->L, p->M, snp, vk0, llr, s));
-        if (t == t_max - 1) {
-            T *app_out = d_app ? (T *)d_app : app;
-            SG_TRY(sg_ldpc_decode_device(g, SG_SUMPROD2, prec, llr, B * nblk, its_final, 0.7, app_out, p->wi_it, s));
-            SG_TRY(integ_launch_hard_bits<T>(app_out, B * nblk, N, K, d_bits, s));
-            break;
-        }
-        SG_TRY(sg_ldpc_decode_device(g, SG_SUMPROD2, prec, llr, B * nblk, its, 0.7, app, p->wi_it, s));
-        ProfScope ps(SG_PH_INT_GLUE, s);
-        SG_TRY(idct_launch_probs<T>(app, nb, vk, s));
-        if (!post) {
-            SG_TRY(integ_launch_bp_to_beta<T>(vk, B, p->L, p->M, snp, 0, beta, s));
-        } else {
-            SG_TRY(integ_launch_bp_to_beta<T>(vk, B, p->L, p->M, snp, 1, gamma, s));
-            SG_TRY(integ_launch_update<T>(gamma, alpha_w, snp, B, p->L, p->M, snp, beta, s));
-        }
-        if (naive) SG_TRY(dense_launch_bsq<T>(db, s));  // ||beta||^2 of the BP-derived beta for the Onsager term
-    }
-    return SG_OK;
+    return integ_loop<T>(front, p->wi, g, mode, N, K, B, p->L, p->M, t_max, its, its_final, d_bits, d_app, s);
 }
 
 // The operator-loop decoder (amp_oploop.hip), for AMP with known sections (rule Known, d_known given) and real
@@ -765,10 +748,10 @@ int sg_concat_known_sections_device(int precision, const void *d_app, const int3
                  "%d protected sections of %d bits do not fit %d blocks of %d bits", L - L_unprotected, logM, mults, N);
     if (B <= 0) return SG_OK;
     hipStream_t s = pick_stream(stream);
-    return precision == SG_F64 ? part_launch_known<double>((const double *)d_app, d_it, max_it, B, mults, N, L,
-                                                           L_unprotected, logM, d_known_idx, s)
-                               : part_launch_known<float>((const float *)d_app, d_it, max_it, B, mults, N, L,
-                                                          L_unprotected, logM, d_known_idx, s);
+    return by_precision(precision, [&](auto t) {
+        return part_launch_known((const decltype(t) *)d_app, d_it, max_it, B, mults, N, L, L_unprotected, logM,
+                                 d_known_idx, s);
+    });
 }
 
 int sg_amp_apply(sg_amp_plan *p, int transpose, const double *in, int B, double *out) {

@@ -157,8 +157,7 @@ int decode_param_checks(int K, double awgn_var, int t_max, double rtol, int phi_
 }
 
 int bits_per_section(int M, int K) {  // log2 M + log2 K
-    int per = 0;
-    while ((1 << per) < M) ++per;
+    int per = ilog2(M);
     for (int k = 1; k < K; k <<= 1) ++per;
     return per;
 }

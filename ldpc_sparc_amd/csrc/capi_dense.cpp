@@ -6,8 +6,7 @@
 #include <utility>
 #include <vector>
 
-#include "dense.hpp"
-#include "device_mem.hpp"
+#include "integ_loop.hpp"
 
 struct sg_dense_plan {
     int precision = SG_F32;
@@ -23,15 +22,8 @@ struct sg_dense_plan {
     double *ws_tau2 = nullptr, *ws_sec_bsq = nullptr;
     int32_t *ws_idx = nullptr;
     sg::DevMem io;
-    // integrated decoders (integrated.hip): weighted alpha, gamma [B][LM];
-    // bit probabilities vk0, vk, LLRs and app [B][L log M]; BP iteration counts;
-    // per-section / per-codeword sums of the differentiated eta
-    sg::DevPool wi;
-    int cap_Bi = 0;
-    void *wi_alpha = nullptr, *wi_gamma = nullptr, *wi_vk0 = nullptr, *wi_vk = nullptr, *wi_llr = nullptr,
-         *wi_app = nullptr;
-    int32_t *wi_it = nullptr;
-    double *wi_part = nullptr, *wi_ons = nullptr;
+    // integrated decoders (integ_loop.hpp, integrated.hip): their workspace, without the xhat slot
+    sg::IntegWs wi;
 };
 
 namespace sg {
@@ -58,28 +50,6 @@ static int dense_ensure_ws(sg_dense_plan *p, int B) {
     SG_TRY(p->ws.alloc(&p->ws_sec_bsq, Bz * p->L * sizeof(double)));
     SG_TRY(p->ws.alloc(&p->ws_idx, Bz * p->L * sizeof(int32_t)));
     p->cap_B = B;
-    return SG_OK;
-}
-
-static void integ_free_ws(sg_dense_plan *p) {
-    p->wi.release();
-    p->cap_Bi = 0;
-}
-
-static int integ_ensure_ws(sg_dense_plan *p, int B, int nbits) {
-    if (B <= p->cap_Bi) return SG_OK;
-    integ_free_ws(p);
-    const size_t rs = rsize(p), Bz = (size_t)B;
-    SG_TRY(p->wi.alloc(&p->wi_alpha, Bz * p->LM * rs));
-    SG_TRY(p->wi.alloc(&p->wi_gamma, Bz * p->LM * rs));
-    SG_TRY(p->wi.alloc(&p->wi_vk0, Bz * nbits * rs));
-    SG_TRY(p->wi.alloc(&p->wi_vk, Bz * nbits * rs));
-    SG_TRY(p->wi.alloc(&p->wi_llr, Bz * nbits * rs));
-    SG_TRY(p->wi.alloc(&p->wi_app, Bz * nbits * rs));
-    SG_TRY(p->wi.alloc(&p->wi_it, Bz * nbits * sizeof(int32_t)));
-    SG_TRY(p->wi.alloc(&p->wi_part, Bz * p->L * sizeof(double)));
-    SG_TRY(p->wi.alloc(&p->wi_ons, Bz * sizeof(double)));
-    p->cap_Bi = B;
     return SG_OK;
 }
 
@@ -201,63 +171,49 @@ static int iteration_impl(sg_dense_plan *p, const double *y, const double *beta,
     return SG_OK;
 }
 
+// The front end of integ_loop (integ_loop.hpp) on the dense design: the two GEMMs, and the three passes eta / bit
+// probabilities / LLRs of the AMP -> BP glue.  beta, z, s and tau^2 live in the batch workspace.
+template <typename T>
+struct DenseFront {
+    const IntegWs &w;
+    DenseBufs<T> d;
+    int nbits, t_max;
+    double *tau_hist;  // [B][t_max] or null
+    double snp;
+    T *beta() const { return d.beta; }
+    const double *tau() const { return d.tau2; }
+    const DenseBufs<T> &bsq_view() const { return d; }
+    int forward(hipStream_t s) { return dense_launch_ab<T>(d, s); }
+    int residual(int t, int ons_mode, hipStream_t s) {  // z; tau^2 = ||z||^2 / n
+        DenseBufs<T> dr = d;
+        dr.ons_mode = ons_mode;
+        dr.ons = ons_mode ? w.ons : nullptr;
+        return dense_launch_residual<T>(dr, t, s);
+    }
+    int sections(int t, hipStream_t s) {
+        SG_TRY(dense_launch_az<T>(d, s));  // s = beta + A^T z
+        if (tau_hist)
+            SG_HIP(hipMemcpy2DAsync(tau_hist + t, (size_t)t_max * 8, d.tau2, 8, 8, d.B, hipMemcpyDeviceToDevice, s));
+        DenseBufs<T> da = d;  // eta writes the weighted alpha (the MMSE estimate) here
+        da.beta = (T *)w.alpha;
+        SG_TRY(dense_launch_eta<T>(da, s));
+        SG_TRY(glue_launch_llr<T>(da.beta, d.B, d.L, d.M, 0, d.L, 1.0 / snp, nbits, (T *)w.vk0, 1, 0, s));  // P(bit = 0)
+        return integ_launch_llr<T>((const T *)w.vk0, (size_t)d.B * nbits, (T *)w.llr, s);
+    }
+    // e^app / (1 + e^app) as the reference forms it (inf / inf in single precision from app = 88.8 on)
+    int probs(const T *app, size_t nn, T *vk, hipStream_t s) { return integ_launch_probs<T>(app, nn, vk, s); }
+};
 
-// The AMP <-> BP integrated decoders (sparc_new.py:257-282 naive, :411-439
-// naive posteriors, :472-502 integrated, :675-705 integrated posteriors) for a
-// batch sharing the design: every LDPC block of every codeword goes through
-// one batched BP launch per iteration.  bits [B][nblk K] = app[:K] < 0 of the
-// final 200-iteration (bp_its_final) decode; tau_hist [B][t_max] optional.
 template <typename T>
 static int integ_impl(sg_dense_plan *p, sg_graph *g, int mode, int N, int K, const void *d_y, int B, int t_max,
                       int its, int its_final, uint8_t *d_bits, double *d_tau_hist, hipStream_t s) {
-    const int logM = [&] { int k = 0; while ((1 << k) < p->M) ++k; return k; }();
-    const int nbits = p->L * logM, nblk = nbits / N;
+    const int nbits = p->L * ilog2(p->M);
     SG_TRY(dense_ensure_ws(p, B));
-    SG_TRY(integ_ensure_ws(p, B, nbits));
-    DenseBufs<T> d = dbufs<T>(p, B, d_y);
-    const double snp = std::sqrt((double)p->n * (p->P / p->L));
-    const bool naive = mode == SG_INT_NAIVE || mode == SG_INT_NAIVE_POST;
-    const bool post = mode == SG_INT_NAIVE_POST || mode == SG_INT_DIFF_POST;
-    T *alpha_w = (T *)p->wi_alpha, *gamma = (T *)p->wi_gamma, *vk0 = (T *)p->wi_vk0, *vk = (T *)p->wi_vk;
-    T *llr = (T *)p->wi_llr, *app = (T *)p->wi_app;
-    const size_t nb = (size_t)B * nbits;
-    const int prec = sizeof(T) == 8 ? SG_F64 : SG_F32;
+    SG_TRY(p->wi.ensure(B, p->L, p->LM, p->n, nbits, sizeof(T), false));
+    DenseFront<T> front{p->wi, dbufs<T>(p, B, d_y), nbits, t_max, d_tau_hist, std::sqrt((double)p->n * (p->P / p->L))};
     SG_HIP(hipMemsetAsync(p->ws_beta, 0, (size_t)B * p->LM * sizeof(T), s));
     SG_HIP(hipMemsetAsync(p->ws_sec_bsq, 0, (size_t)B * p->L * sizeof(double), s));
-    DenseBufs<T> da = d;  // eta writes the weighted alpha (the MMSE estimate) here
-    da.beta = alpha_w;
-    if (!naive) {
-        d.ons_mode = mode == SG_INT_DIFF ? 1 : 2;
-        d.ons = p->wi_ons;
-    }
-    for (int t = 0; t < t_max; ++t) {
-        if (!naive && t > 0)  // sum of the differentiated eta with the previous tau^2
-            SG_TRY(integ_launch_deta<T>(post ? 1 : 0, d.beta, gamma, alpha_w, snp, vk, vk0, p->ws_tau2, B, p->L, p->M,
-                                        snp, p->wi_part, p->wi_ons, (T *)nullptr, s));
-        if (t > 0) SG_TRY(dense_launch_ab<T>(d, s));
-        SG_TRY(dense_launch_residual<T>(d, t, s));  // z; tau^2 = ||z||^2 / n
-        SG_TRY(dense_launch_az<T>(d, s));            // s = beta + A^T z
-        if (d_tau_hist)
-            SG_HIP(hipMemcpy2DAsync(d_tau_hist + t, (size_t)t_max * 8, p->ws_tau2, 8, 8, B, hipMemcpyDeviceToDevice, s));
-        SG_TRY(dense_launch_eta<T>(da, s));
-        SG_TRY(glue_launch_llr<T>(alpha_w, B, p->L, p->M, 0, p->L, 1.0 / snp, nbits, vk0, 1, 0, s));  // P(bit = 0)
-        SG_TRY(integ_launch_llr<T>(vk0, nb, llr, s));
-        if (t == t_max - 1) {
-            SG_TRY(sg_ldpc_decode_device(g, SG_SUMPROD2, prec, llr, B * nblk, its_final, 0.7, app, p->wi_it, s));
-            SG_TRY(integ_launch_hard_bits<T>(app, B * nblk, N, K, d_bits, s));
-            break;
-        }
-        SG_TRY(sg_ldpc_decode_device(g, SG_SUMPROD2, prec, llr, B * nblk, its, 0.7, app, p->wi_it, s));
-        SG_TRY(integ_launch_probs<T>(app, nb, vk, s));
-        if (!post) {
-            SG_TRY(integ_launch_bp_to_beta<T>(vk, B, p->L, p->M, snp, 0, d.beta, s));
-        } else {
-            SG_TRY(integ_launch_bp_to_beta<T>(vk, B, p->L, p->M, snp, 1, gamma, s));
-            SG_TRY(integ_launch_update<T>(gamma, alpha_w, snp, B, p->L, p->M, snp, d.beta, s));
-        }
-        if (naive) SG_TRY(dense_launch_bsq<T>(d, s));  // ||beta||^2 of the BP-derived beta for the Onsager term
-    }
-    return SG_OK;
+    return integ_loop<T>(front, p->wi, g, mode, N, K, B, p->L, p->M, t_max, its, its_final, d_bits, nullptr, s);
 }
 
 // The soft-glue pieces on host arrays (the reference's functions, batched over B).
@@ -355,8 +311,9 @@ int sg_dense_plan_create_random(int n, int L, int M, double P, uint64_t seed, in
     sg_dense_plan *p = nullptr;
     SG_TRY(plan_common(n, L, M, P, precision, out, &p));
     hipStream_t s = lib_stream();
-    int rc = precision == SG_F64 ? dense_launch_gen_A<double>(p->A.at<double>(), n, p->LM, seed, s)
-                                 : dense_launch_gen_A<float>(p->A.at<float>(), n, p->LM, seed, s);
+    int rc = by_precision(precision, [&](auto t) {
+        return dense_launch_gen_A(p->A.at<decltype(t)>(), n, p->LM, seed, s);
+    });
     if (rc == SG_OK && hipStreamSynchronize(s) != hipSuccess) rc = SG_ERR_HIP;
     if (rc != SG_OK) {
         sg_dense_plan_destroy(p);
@@ -388,7 +345,7 @@ int sg_dense_amp_device(sg_dense_plan *p, const void *d_y, int B, int t_max, voi
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = pick_stream(stream);
     const size_t rs = rsize(p), nb = (size_t)B * p->LM * rs;
-    SG_TRY(p->precision == SG_F64 ? amp_impl<double>(p, d_y, B, t_max, s) : amp_impl<float>(p, d_y, B, t_max, s));
+    SG_TRY(by_precision(p->precision, [&](auto t) { return amp_impl<decltype(t)>(p, d_y, B, t_max, s); }));
     if (d_beta) SG_HIP(hipMemcpyAsync(d_beta, p->ws_beta, nb, hipMemcpyDeviceToDevice, s));
     if (d_s) SG_HIP(hipMemcpyAsync(d_s, p->ws_s, nb, hipMemcpyDeviceToDevice, s));
     return SG_OK;
@@ -430,8 +387,9 @@ int sg_dense_amp_iteration(sg_dense_plan *p, const double *y, const double *beta
     SG_TRY(ensure_device());
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = lib_stream();
-    return p->precision == SG_F64 ? iteration_impl<double>(p, y, beta, z, tau_sqr, beta_out, z_out, tau_sqr_out, s)
-                                  : iteration_impl<float>(p, y, beta, z, tau_sqr, beta_out, z_out, tau_sqr_out, s);
+    return by_precision(p->precision, [&](auto t) {
+        return iteration_impl<decltype(t)>(p, y, beta, z, tau_sqr, beta_out, z_out, tau_sqr_out, s);
+    });
 }
 
 // x[b] = A beta0[b], beta0 one-hot per section with value sqrt(n P / L) at
@@ -483,8 +441,9 @@ int sg_dense_map_device(sg_dense_plan *p, const void *d_s, int B, int32_t *d_idx
     if (B <= 0) return SG_OK;
     SG_TRY(ensure_device());
     hipStream_t s = pick_stream(stream);
-    return p->precision == SG_F64 ? dense_launch_map<double>((const double *)d_s, B, p->L, p->M, d_idx, s)
-                                  : dense_launch_map<float>((const float *)d_s, B, p->L, p->M, d_idx, s);
+    return by_precision(p->precision, [&](auto t) {
+        return dense_launch_map((const decltype(t) *)d_s, B, p->L, p->M, d_idx, s);
+    });
 }
 
 // Bit LLRs of sections [l0, l0 + nl) from soft section estimates beta
@@ -499,11 +458,10 @@ int sg_beta_to_llr_device(int precision, const void *d_beta, int B, int L, int M
     SG_TRY(ensure_device());
     hipStream_t s = pick_stream(stream);
     const double inv = 1.0 / sqrt_nPl;
-    return precision == SG_F64
-               ? glue_launch_llr<double>((const double *)d_beta, B, L, M, l0, nl, inv, llr_ld, (double *)d_llr,
-                                         probs_only, 0, s)
-               : glue_launch_llr<float>((const float *)d_beta, B, L, M, l0, nl, inv, llr_ld, (float *)d_llr,
-                                        probs_only, 0, s);
+    return by_precision(precision, [&](auto t) {
+        using T = decltype(t);
+        return glue_launch_llr<T>((const T *)d_beta, B, L, M, l0, nl, inv, llr_ld, (T *)d_llr, probs_only, 0, s);
+    });
 }
 
 int sg_concat_count_errors_device(int precision, const int32_t *d_map_idx, const int32_t *d_true_idx, int B, int L,
@@ -513,11 +471,10 @@ int sg_concat_count_errors_device(int precision, const int32_t *d_map_idx, const
     SG_CHECK_ARG(L_unprotected >= 0 && L_unprotected <= L && mults >= 0 && K <= N, "bad lengths");
     SG_TRY(ensure_device());
     hipStream_t s = pick_stream(stream);
-    return precision == SG_F64
-               ? concat_launch_count<double>(d_map_idx, d_true_idx, B, L, L_unprotected, logM, (const double *)d_app,
-                                             d_info, mults, N, K, d_counts, s)
-               : concat_launch_count<float>(d_map_idx, d_true_idx, B, L, L_unprotected, logM, (const float *)d_app,
-                                            d_info, mults, N, K, d_counts, s);
+    return by_precision(precision, [&](auto t) {
+        return concat_launch_count(d_map_idx, d_true_idx, B, L, L_unprotected, logM, (const decltype(t) *)d_app, d_info,
+                                   mults, N, K, d_counts, s);
+    });
 }
 
 int sg_integrated_decode_device(sg_dense_plan *p, sg_graph *g, int mode, int K, const void *d_y, int B, int t_max,
@@ -527,8 +484,7 @@ int sg_integrated_decode_device(sg_dense_plan *p, sg_graph *g, int mode, int K, 
     SG_CHECK_ARG(t_max >= 1 && bp_its >= 0 && bp_its_final >= 0, "bad iteration counts");
     int N = 0, nc = 0;
     SG_TRY(sg_ldpc_graph_info(g, &N, &nc, nullptr, nullptr, nullptr));
-    int logM = 0;
-    while ((1 << logM) < p->M) ++logM;
+    const int logM = ilog2(p->M);
     SG_CHECK_ARG(N > 0 && (p->L * logM) % N == 0, "L log2 M = %d bits must be a multiple of the block length %d",
                  p->L * logM, N);  // ldpc_bp's assert (sparc_new.py:1171)
     SG_CHECK_ARG(K > 0 && K <= N, "bad information length %d", K);
@@ -536,9 +492,9 @@ int sg_integrated_decode_device(sg_dense_plan *p, sg_graph *g, int mode, int K, 
     SG_TRY(ensure_device());
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = pick_stream(stream);
-    return p->precision == SG_F64
-               ? integ_impl<double>(p, g, mode, N, K, d_y, B, t_max, bp_its, bp_its_final, d_bits, d_tau2, s)
-               : integ_impl<float>(p, g, mode, N, K, d_y, B, t_max, bp_its, bp_its_final, d_bits, d_tau2, s);
+    return by_precision(p->precision, [&](auto t) {
+        return integ_impl<decltype(t)>(p, g, mode, N, K, d_y, B, t_max, bp_its, bp_its_final, d_bits, d_tau2, s);
+    });
 }
 
 int sg_integrated_decode(sg_dense_plan *p, sg_graph *g, int mode, int K, const double *y, int B, int t_max,
@@ -549,8 +505,7 @@ int sg_integrated_decode(sg_dense_plan *p, sg_graph *g, int mode, int K, const d
     SG_HIP(hipSetDevice(p->device));
     int N = 0;
     SG_TRY(sg_ldpc_graph_info(g, &N, nullptr, nullptr, nullptr, nullptr));
-    int logM = 0;
-    while ((1 << logM) < p->M) ++logM;
+    const int logM = ilog2(p->M);
     SG_CHECK_ARG(N > 0 && (p->L * logM) % N == 0, "L log2 M must be a multiple of the block length");
     const size_t nbits = (size_t)B * (p->L * logM / N) * K;
     hipStream_t s = lib_stream();
@@ -576,13 +531,12 @@ int sg_integrated_decode(sg_dense_plan *p, sg_graph *g, int mode, int K, const d
 
 int sg_bp_output_to_beta(int precision, const double *probs, int B, int L, int M, double sqrt_nPl, double *beta) {
     SG_CHECK_ARG(probs && beta && B >= 0 && L > 0 && M > 1 && (M & (M - 1)) == 0, "bad argument");
-    int logM = 0;
-    while ((1 << logM) < M) ++logM;
-    const size_t np = (size_t)B * L * logM, nbeta = (size_t)B * L * M;
+    const size_t np = (size_t)B * L * ilog2(M), nbeta = (size_t)B * L * M;
     return integ_host_call(precision, {{probs, np}}, {{beta, nbeta}}, [&](auto &in, auto &out, hipStream_t s) {
-        return precision == SG_F64
-                   ? integ_launch_bp_to_beta<double>((const double *)in[0], B, L, M, sqrt_nPl, 0, (double *)out[0], s)
-                   : integ_launch_bp_to_beta<float>((const float *)in[0], B, L, M, sqrt_nPl, 0, (float *)out[0], s);
+        return by_precision(precision, [&](auto t) {
+            using T = decltype(t);
+            return integ_launch_bp_to_beta<T>((const T *)in[0], B, L, M, sqrt_nPl, 0, (T *)out[0], s);
+        });
     });
 }
 
@@ -591,11 +545,10 @@ int sg_update_using_bp_probs(int precision, const double *gamma, const double *a
     SG_CHECK_ARG(gamma && alpha && beta && B >= 0 && L > 0 && M > 0, "bad argument");
     const size_t nn = (size_t)B * L * M;
     return integ_host_call(precision, {{gamma, nn}, {alpha, nn}}, {{beta, nn}}, [&](auto &in, auto &out, hipStream_t s) {
-        return precision == SG_F64
-                   ? integ_launch_update<double>((const double *)in[0], (const double *)in[1], 1.0, B, L, M, sqrt_nPl,
-                                                 (double *)out[0], s)
-                   : integ_launch_update<float>((const float *)in[0], (const float *)in[1], 1.0, B, L, M, sqrt_nPl,
-                                                (float *)out[0], s);
+        return by_precision(precision, [&](auto t) {
+            using T = decltype(t);
+            return integ_launch_update<T>((const T *)in[0], (const T *)in[1], 1.0, B, L, M, sqrt_nPl, (T *)out[0], s);
+        });
     });
 }
 
@@ -604,9 +557,7 @@ int sg_differentiated_eta(int precision, int posteriors, const double *beta, con
                           int M, double sqrt_nPl, double *out) {
     SG_CHECK_ARG(beta && alpha && vk && vk0 && tau2 && out && (!posteriors || gamma), "null argument");
     SG_CHECK_ARG(B >= 0 && L > 0 && M > 1 && (M & (M - 1)) == 0, "bad shape");
-    int logM = 0;
-    while ((1 << logM) < M) ++logM;
-    const size_t nn = (size_t)B * L * M, nv = (size_t)B * L * logM;
+    const size_t nn = (size_t)B * L * M, nv = (size_t)B * L * ilog2(M);
     SG_TRY(ensure_device());
     DevMem mtau, mpart;
     SG_TRY(mtau.ensure(std::max<size_t>(1, B) * 8));
@@ -616,15 +567,12 @@ int sg_differentiated_eta(int precision, int posteriors, const double *beta, con
     return integ_host_call(
         precision, {{beta, nn}, {gamma, gamma ? nn : 0}, {alpha, nn}, {vk, nv}, {vk0, nv}}, {{out, nn}},
         [&](auto &in, auto &o, hipStream_t s) {
-            return precision == SG_F64
-                       ? integ_launch_deta<double>(posteriors ? 1 : 0, (const double *)in[0], (const double *)in[1],
-                                                   (const double *)in[2], 1.0, (const double *)in[3],
-                                                   (const double *)in[4], dtau, B, L, M, sqrt_nPl, dpart, nullptr,
-                                                   (double *)o[0], s)
-                       : integ_launch_deta<float>(posteriors ? 1 : 0, (const float *)in[0], (const float *)in[1],
-                                                  (const float *)in[2], 1.0, (const float *)in[3],
-                                                  (const float *)in[4], dtau, B, L, M, sqrt_nPl, dpart, nullptr,
-                                                  (float *)o[0], s);
+            return by_precision(precision, [&](auto t) {
+                using T = decltype(t);
+                return integ_launch_deta<T>(posteriors ? 1 : 0, (const T *)in[0], (const T *)in[1], (const T *)in[2],
+                                            1.0, (const T *)in[3], (const T *)in[4], dtau, B, L, M, sqrt_nPl, dpart,
+                                            nullptr, (T *)o[0], s);
+            });
         });
 }
 

@@ -39,6 +39,17 @@ struct ProfScope {
     ~ProfScope() { prof_end(tok, s); }
 };
 
+// ceil(log2 v): log2 of a power of two (section sizes, transform lengths)
+inline int ilog2(int v) {
+    int l = 0;
+    while ((1 << l) < v) ++l;
+    return l;
+}
+
+// f(T{}) with T the real type of a precision (SG_F64: double, else float)
+template <typename F>
+int by_precision(int precision, F &&f) { return precision == SG_F64 ? f(double{}) : f(float{}); }
+
 struct HipError {
     hipError_t err;
     const char *what;

@@ -169,8 +169,7 @@ int idct_launch_residual(const T *y, const T *xhat, T *z, int B, int n, int L, d
 template <typename T>
 int idct_launch_section(T *ua, const T *beta, const double *tau, int B, int L, int M, double snp, T *vk0, T *llr,
                         hipStream_t s) {
-    int logM = 0;
-    while ((1 << logM) < M) ++logM;
+    const int logM = ilog2(M);
     if (M < 2 || (1 << logM) != M || M > 2048)
         return fail(SG_ERR_UNSUPPORTED, "integrated section kernel: M = %d is not a power of two in [2, 2048]", M);
     ProfScope ps(SG_PH_ETA, s);

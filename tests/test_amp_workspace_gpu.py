@@ -1,5 +1,5 @@
-"""Regrow and reuse of a plan's workspaces (ensure_ws, ensure_io,
-integ_ensure_ws, amp_plan.cpp): a plan that has grown its batch, grown its NMSE
+"""Regrow and reuse of a plan's workspaces (ensure_ws, ensure_io of
+amp_plan.cpp, IntegWs::ensure of integ_ws.hpp): a plan that has grown its batch, grown its NMSE
 history, run the design operators in the same buffers and shrunk again computes,
 bit for bit, what a freshly created plan computes for the same call.
 
