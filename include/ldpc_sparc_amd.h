@@ -440,8 +440,9 @@ int sg_amp_decode_partial(sg_amp_plan *p, const double *y, int B, const int32_t 
  * launch or allocation: SG_ERR_UNSUPPORTED for M not a power of two in [2, 2048] (one wavefront per section, up to
  * 32 entries per lane); SG_ERR_INVALID for bad t_max, rtol, phi_method, awgn_var as sg_amp_decode_device; B <= 0
  * returns SG_OK with nothing done.  Works in the workspace and the partial buffers of sg_amp_decode_partial_device:
- * clears the last-decode state (no soft output for K = 2) and leaves the plan fit for sg_amp_decode*.  A
- * codeword's results do not depend on the batch it is decoded in. */
+ * clears the last-decode state (sg_amp_llr* refuses after a K = 2 decode; its soft output is sg_amp_bpsk_llr*
+ * below) and leaves the plan fit for sg_amp_decode*.  A codeword's results do not depend on the batch it is
+ * decoded in. */
 int sg_amp_decode_bpsk_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_true_word, double awgn_var,
                               int t_max, double rtol, int phi_method, int32_t *d_map_word, int32_t *d_t_final,
                               double *d_nmse, double *d_psi, void *stream);
@@ -451,6 +452,29 @@ int sg_amp_decode_bpsk(sg_amp_plan *p, const double *y, int B, const int32_t *tr
 /* x = A beta0 [B][n] on the device for section words d_word [B][L] of a real K = 2 SPARC: beta0 holds +1
  * (symbol 0) or -1 at the word's location; a word outside [0, 2M) leaves its section zero. */
 int sg_amp_encode_bpsk_device(sg_amp_plan *p, const int32_t *d_word, int B, void *d_x, void *stream);
+/* Soft output of the K = 2 decoder (amp_bpsk_llr.hip).  The decoder overwrites beta in place, so the bit
+ * marginals need the last effective observation s = beta + tau u of each codeword.  sg_amp_bpsk_soft_output(p, 1)
+ * makes the following sg_amp_decode_bpsk* through this plan keep it: sizeof(real) L M bytes per codeword of the
+ * batch, allocated with the operator loop's buffers on the next K = 2 decode (grow-only, freed with the plan); off
+ * (the default) nothing is allocated and nothing is stored.  map_word, t_final, nmse and psi are the same bits
+ * either way.  Switching clears the state below. */
+int sg_amp_bpsk_soft_output(sg_amp_plan *p, int on);
+/* For sections [l0, l0 + nl) of each of the B codewords of the last K = 2 decode through this plan, in the plan
+ * precision: P(bit = 0) of the log2 M location bits, MSB first, and then of the symbol bit (0: +1) -- the digits
+ * of the section's word -- under the joint posterior p(j, c) = e^{c x_j} / sum_k (e^{x_k} + e^{-x_k}), x = s / tau,
+ * c = +-1, whose mean is the decoder's beta; clipped to [1e-15, 1 - 1e-15] and written as log p - log(1 - p)
+ * (ldpc_bp, sparc_new.py:1167-1169) to d_llr[b * llr_ld + (l - l0) * (log2 M + 1) + i]; probs_only: the unclipped
+ * probabilities.  A codeword that stopped early gives the s and the tau of its last executed iteration.  Enqueued
+ * on the stream; allocates nothing; the same bits on every run, and a codeword's output does not depend on its
+ * batch.  Every refusal precedes any launch or write.  SG_ERR_UNSUPPORTED: M not a power of two in [2, 2048].
+ * SG_ERR_BAD_ARG: soft output off; no K = 2 decode with soft output on record (every decode call of any kind
+ * through the plan, sg_amp_apply*, the encoders and the integrated decoders clear it; a failed or B = 0 decode
+ * leaves it cleared); B different from that decode's; a section range outside [0, L]; llr_ld < nl (log2 M + 1). */
+int sg_amp_bpsk_llr_device(sg_amp_plan *p, int B, int l0, int nl, int llr_ld, int probs_only, void *d_llr,
+                           void *stream);
+/* Host variant: out [B][nl * (log2 M + 1)] as double, blocking.  A decode enqueued on a caller's stream must have
+ * completed. */
+int sg_amp_bpsk_llr(sg_amp_plan *p, int B, int l0, int nl, int probs_only, double *out);
 /* Soft output of the last decode through this plan (sg_amp_decode_device or
  * sg_amp_decode), in the plan precision: for sections [l0, l0 + nl) of each of
  * the B codewords, P(bit = 0) of the log2 M section bits, MSB first, from the

@@ -17,7 +17,8 @@
 //   known_section_kernel    s = beta + tau u (:972), beta = softmax(s / tau) or the one-hot, sum beta^2, the squared
 //                           error against the true index, the first-maximum argmax of s (:997) or the known index
 //   bpsk_section_kernel     s = beta + tau u, beta = eta(s / tau), sum beta^2, the squared error against the true
-//                           word's +-1 one-hot, the word (location << 1) | symbol of the first maximum of |s|
+//                           word's +-1 one-hot, the word (location << 1) | symbol of the first maximum of |s|; with
+//                           OpLoopBufs::s_keep it also stores s (the soft output's input, amp_bpsk_llr.hip)
 //   known_sections_kernel   hard decisions of a BP output -> section indices, -1 where a block did not converge
 //
 // The K = 2 denoiser, with x = s / tau, a = |x| and m the section's maximum of a:
@@ -301,6 +302,7 @@ __global__ __launch_bounds__(256) void bpsk_section_kernel(OpLoopBufs<T> ob) {
         const int j = lane + 64 * i;
         if (j < M) {
             const T s = ob.beta[o + j] + tau * ob.u[o + j];  // sparc.py:972
+            if (ob.s_keep) ob.s_keep[o + j] = s;             // soft output (amp_bpsk_llr.hip)
             x[i] = s / tau;                                  // sparc.py:434
             xm = fmax(xm, fabs(x[i]));
             if (fabs(s) > amax) { amax = fabs(s); word = (j << 1) | (s < T(0) ? 1 : 0); }

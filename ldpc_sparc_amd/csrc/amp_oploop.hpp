@@ -28,6 +28,7 @@ struct OpLoopBufs {
     const T *y;                 // [B][n]
     T *beta;                    // [B][LM]
     T *u;                       // [B][LM] Az(z / phi)
+    T *s_keep;                  // [B][LM] K = 2 soft output: the section kernel's s = beta + tau u, or null (not kept)
     T *r;                       // [B][n]  Ab(beta)
     T *z, *zs;                  // [B][n]  residual, z / phi of the element's row block
     const int32_t *known;       // [B][L] index in [0, M), anything else: unknown; null for K = 2 (nothing is known)
@@ -64,6 +65,14 @@ int oploop_launch_control(const OpLoopBufs<T> &ob, int phase, int t, hipStream_t
 // <= 2048
 template <typename T>
 int oploop_launch_section(const OpLoopBufs<T> &ob, SectionRule rule, hipStream_t s);
+
+// Bit LLRs (or with probs_only P(bit = 0)) of sections [l0, l0 + nl) from the s and tau a K = 2 decode with
+// OpLoopBufs::s_keep left (amp_bpsk_llr.hip): log2 M location bits, MSB first, then the symbol bit, to
+// llr[b llr_ld + (l - l0) (log2 M + 1) + i].  The caller has checked the range, llr_ld and M a power of two in
+// [2, 2048].  s_keep [B][L M] natural order, tau [B][Lc].
+template <typename T>
+int bpsk_launch_llr(const T *s_keep, const double *tau, int B, int L, int M, int Lc, int l0, int nl, int llr_ld,
+                    int probs_only, T *llr, hipStream_t s);
 
 // BP output -> known sections (sg_concat_known_sections_device)
 template <typename T>

@@ -97,9 +97,13 @@ int diag_skip() {
 
 // ---- workspace: every buffer is a slot of one of the plan's pools (device_mem.hpp), released together
 int partial_ensure_ws(sg_amp_plan *p, int B) {
-    if (B <= p->cap_Bp) return SG_OK;
+    // s_keep (K = 2 soft output) joins the pool at the first decode after sg_amp_bpsk_soft_output(p, 1) and stays
+    const bool keep = p->bpsk_soft || p->wp_skeep;
+    if (B <= p->cap_Bp && (p->wp_skeep || !keep)) return SG_OK;
+    B = std::max(B, p->cap_Bp);
     p->wp.release();
     p->cap_Bp = 0;
+    p->wp_skeep = nullptr;
     const size_t rs = p->precision == SG_F64 ? 8 : 4, Bz = (size_t)B;
     SG_TRY(p->wp.alloc(&p->wp_u, Bz * p->LM * rs));
     SG_TRY(p->wp.alloc(&p->wp_r, Bz * p->n * rs));
@@ -110,6 +114,7 @@ int partial_ensure_ws(sg_amp_plan *p, int B) {
     SG_TRY(p->wp.alloc(&p->wp_tau, Bz * p->Lc * sizeof(double)));
     SG_TRY(p->wp.alloc(&p->wp_active, Bz * sizeof(int32_t)));
     SG_TRY(p->wp.alloc(&p->wp_known, Bz * p->L * sizeof(int32_t)));
+    if (keep) SG_TRY(p->wp.alloc(&p->wp_skeep, Bz * p->LM * rs));
     p->cap_Bp = B;
     return SG_OK;
 }

@@ -126,6 +126,13 @@ struct sg_amp_plan {
     void *wp_u = nullptr, *wp_r = nullptr, *wp_z = nullptr;
     double *wp_zz = nullptr, *wp_bsq = nullptr, *wp_err = nullptr, *wp_tau = nullptr;
     int32_t *wp_active = nullptr, *wp_known = nullptr;
+    // Soft output of the K = 2 decoder (sg_amp_bpsk_soft_output, amp_bpsk_llr.hip): while on, partial_ensure_ws also
+    // holds wp_skeep [B][LM] of the plan precision, where bpsk_section_kernel keeps s = beta + tau u.
+    // last_bpsk_B: batch size of the last K = 2 decode through this plan that filled it and whose s / wp_tau are
+    // still there (sg_amp_bpsk_llr_device); 0: none.  Whatever runs in the batch workspace or this pool clears it.
+    bool bpsk_soft = false;
+    void *wp_skeep = nullptr;
+    int last_bpsk_B = 0;
 };
 
 #pragma GCC visibility push(hidden)  // shared between the library's objects, not exported from it

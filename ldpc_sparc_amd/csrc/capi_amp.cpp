@@ -470,6 +470,7 @@ static int oploop_impl(sg_amp_plan *p, const DecodeArgs &a, SectionRule rule, co
     ob.beta = p->regular ? (T *)p->ws_s : (T *)p->ws_beta;
     ob.u = (T *)p->wp_u; ob.r = (T *)p->wp_r; ob.z = (T *)p->wp_z; ob.zs = (T *)p->ws_z;
     ob.known = d_known; ob.truth = a.d_true;
+    if (rule == SectionRule::Bpsk && p->bpsk_soft) ob.s_keep = (T *)p->wp_skeep;  // (partial_ensure_ws holds it)
     ob.zz = p->wp_zz; ob.bsq = p->wp_bsq; ob.err = p->wp_err; ob.map = p->ws_argmax;
     ob.psi = p->ws_psi; ob.psi_prev = p->ws_psi_prev; ob.gamma = p->ws_gamma; ob.bco = p->ws_bco;
     ob.phi = p->ws_phi_prev; ob.tau = p->wp_tau; ob.nmse = p->ws_nmse;
@@ -605,6 +606,7 @@ static void reset_last(sg_amp_plan *p) {
         q->last_handover = -1;
         q->last_piped = 0;
         q->last_B = 0;
+        q->last_bpsk_B = 0;
     }
 }
 
@@ -620,7 +622,9 @@ static int oploop_entry(sg_amp_plan *p, SectionRule rule, int B, double awgn_var
     SG_TRY(oploop_checks(p, rule, awgn_var, t_max, rtol, phi_method));
     if (B <= 0) return SG_OK;
     SG_HIP(hipSetDevice(p->device));
-    return body(pick_stream(stream));
+    SG_TRY(body(pick_stream(stream)));
+    if (rule == SectionRule::Bpsk && p->bpsk_soft) p->last_bpsk_B = B;  // s_keep and wp_tau hold its final state
+    return SG_OK;
 }
 
 extern "C" {
@@ -758,7 +762,7 @@ int sg_amp_apply(sg_amp_plan *p, int transpose, const double *in, int B, double 
     SG_CHECK_ARG(p && in && out, "null argument");
     SG_CHECK_ARG(B >= 0, "negative batch");
     if (B == 0) return SG_OK;
-    p->last_B = 0;  // (the operators run in the workspace that holds a decode's final state)
+    p->last_B = p->last_bpsk_B = 0;  // (the operators run in the workspace that holds a decode's final state)
     SG_TRY(ensure_device());
     SG_HIP(hipSetDevice(p->device));
     hipStream_t s = lib_stream();
@@ -777,7 +781,7 @@ int sg_amp_apply(sg_amp_plan *p, int transpose, const double *in, int B, double 
 int sg_amp_encode_device(sg_amp_plan *p, const int32_t *d_idx, int B, void *d_x, void *stream) {
     SG_CHECK_ARG(p && d_idx && d_x, "null argument");
     if (B <= 0) return SG_OK;
-    p->last_B = 0;
+    p->last_B = p->last_bpsk_B = 0;
     SG_TRY(ensure_device());
     hipStream_t s = pick_stream(stream);
     return by_precision(p->precision, [&](auto t) { return encode_impl(p, d_idx, B, (decltype(t) *)d_x, s); });
@@ -787,7 +791,7 @@ int sg_amp_encode_bpsk_device(sg_amp_plan *p, const int32_t *d_word, int B, void
     SG_TRY(ensure_device());
     SG_CHECK_ARG(p && d_word && d_x, "null argument");
     if (B <= 0) return SG_OK;
-    p->last_B = 0;
+    p->last_B = p->last_bpsk_B = 0;
     hipStream_t s = pick_stream(stream);
     return by_precision(p->precision, [&](auto t) { return encode_impl(p, d_word, B, (decltype(t) *)d_x, s, true); });
 }
@@ -840,7 +844,7 @@ int sg_amp_stage_raw(sg_amp_plan *p, int kernel, uint64_t *out, size_t *items) {
 int sg_amp_apply_device(sg_amp_plan *p, int transpose, const void *d_in, int B, void *d_out, void *stream) {
     SG_CHECK_ARG(p && d_in && d_out, "null argument");
     if (B <= 0) return SG_OK;
-    p->last_B = 0;
+    p->last_B = p->last_bpsk_B = 0;
     SG_TRY(ensure_device());
     hipStream_t s = pick_stream(stream);
     return by_precision(p->precision, [&](auto t) {  // (vectors of the plan precision on both sides)
@@ -911,6 +915,81 @@ int sg_amp_llr(sg_amp_plan *p, int B, int l0, int nl, int probs_only, double *ou
     } else {
         float *df = (float *)(dd + nv);
         SG_TRY(llr_impl<float>(r, B, l0, nl, (int)ld, probs_only, df, s));
+        SG_TRY(amp_launch_uncast<float>(df, dd, nv, s));
+    }
+    SG_HIP(hipMemcpyAsync(out, dd, nv * sizeof(double), hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
+    return SG_OK;
+}
+
+}  // extern "C"
+
+// Soft output of the last K = 2 decode (amp_bpsk_llr.hip).  Final-state contract of the operator loop (DESIGN.md
+// "Soft output of the K = 2 decoder"): the section and control kernels return at once for a stopped codeword, so
+// wp_skeep and wp_tau hold, per codeword, the s and the tau of its last executed iteration.
+static int bpsk_llr_checks(const sg_amp_plan *p, int B, int l0, int nl, long long llr_ld, int *per_out) {
+    if (p->M < 2 || (p->M & (p->M - 1)) != 0 || p->M > 2048)
+        return fail(SG_ERR_UNSUPPORTED, "section size M = %d: the K = 2 soft output takes a power of two in "
+                    "[2, 2048]", p->M);
+    SG_CHECK_ARG(p->bpsk_soft, "soft output is off: sg_amp_bpsk_soft_output(plan, 1) before the decode");
+    SG_CHECK_ARG(p->last_bpsk_B > 0 && p->wp_skeep, "no K = 2 decode with soft output through this plan yet (or its "
+                 "state was overwritten)");
+    SG_CHECK_ARG(B == p->last_bpsk_B, "B = %d, but the last K = 2 decode held %d codewords", B, p->last_bpsk_B);
+    SG_CHECK_ARG(l0 >= 0 && nl >= 0 && l0 <= p->L && nl <= p->L - l0, "sections [%d, %d + %d) outside [0, %d]", l0, l0,
+                 nl, p->L);
+    const int per = ilog2(p->M) + 1;
+    SG_CHECK_ARG(llr_ld >= (long long)nl * per, "llr_ld = %lld < nl (log2 M + 1) = %lld", llr_ld, (long long)nl * per);
+    *per_out = per;
+    return SG_OK;
+}
+
+template <typename T>
+static int bpsk_llr_impl(const sg_amp_plan *p, int B, int l0, int nl, int llr_ld, int probs_only, T *d_llr,
+                         hipStream_t s) {
+    return bpsk_launch_llr<T>((const T *)p->wp_skeep, p->wp_tau, B, p->L, p->M, p->Lc, l0, nl, llr_ld, probs_only,
+                              d_llr, s);
+}
+
+extern "C" {
+
+int sg_amp_bpsk_soft_output(sg_amp_plan *p, int on) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p, "plan is NULL");
+    p->bpsk_soft = on != 0;
+    p->last_bpsk_B = 0;  // s_keep is filled by the next K = 2 decode
+    return SG_OK;
+}
+
+int sg_amp_bpsk_llr_device(sg_amp_plan *p, int B, int l0, int nl, int llr_ld, int probs_only, void *d_llr,
+                           void *stream) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p && d_llr, "null argument");
+    int per = 0;
+    SG_TRY(bpsk_llr_checks(p, B, l0, nl, llr_ld, &per));
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = pick_stream(stream);
+    return by_precision(p->precision, [&](auto t) {
+        return bpsk_llr_impl(p, B, l0, nl, llr_ld, probs_only, (decltype(t) *)d_llr, s);
+    });
+}
+
+int sg_amp_bpsk_llr(sg_amp_plan *p, int B, int l0, int nl, int probs_only, double *out) {
+    SG_TRY(ensure_device());
+    SG_CHECK_ARG(p && out, "null argument");
+    int per = 0;
+    SG_TRY(bpsk_llr_checks(p, B, l0, nl, INT32_MAX, &per));
+    const size_t ld = (size_t)nl * per, nv = (size_t)B * ld;
+    if (nv == 0) return SG_OK;
+    SG_HIP(hipSetDevice(p->device));
+    hipStream_t s = lib_stream();
+    // staging in the plan's I/O buffer (not part of the decode state): doubles, then the plan's reals
+    SG_TRY(ensure_io(p, nv * 16));
+    double *dd = p->io.at<double>();
+    if (p->precision == SG_F64) {
+        SG_TRY(bpsk_llr_impl<double>(p, B, l0, nl, (int)ld, probs_only, dd, s));
+    } else {
+        float *df = (float *)(dd + nv);
+        SG_TRY(bpsk_llr_impl<float>(p, B, l0, nl, (int)ld, probs_only, df, s));
         SG_TRY(amp_launch_uncast<float>(df, dd, nv, s));
     }
     SG_HIP(hipMemcpyAsync(out, dd, nv * sizeof(double), hipMemcpyDeviceToHost, s));

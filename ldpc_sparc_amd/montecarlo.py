@@ -506,7 +506,8 @@ def concat_checkpoint_tag(L, M, n, design="dense", K=1):
     """Checkpoint tag of a concat_ber_sweep: concat_L.. (dense), concat_dct_L.. (DCT design),
     concat_dct3_L.. (DCT design with the final AMP pass, design "dct3"),
     concat_fft_L.._M.._K.. (complex FFT design with K-PSK; K = 1 unmodulated),
-    concat_fft3_L.._M.._K.. (the same with the final AMP pass, design "fft3")."""
+    concat_fft3_L.._M.._K.. (the same with the final AMP pass, design "fft3"),
+    concat_dct_k2_L.. (DCT design with real K = 2 modulated sections, design "dct_k2")."""
     if design in ("fft", "fft3"):
         return f"concat_{design}_L{L}_M{M}_K{K}_n{n}"
     return f"concat_L{L}_M{M}_n{n}" if design == "dense" else f"concat_{design}_L{L}_M{M}_n{n}"
@@ -551,20 +552,30 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
     last pass up to `final_t_max` - 1 iterations, default t_max); its
     checkpoints live under concat_dct3_L.. / concat_fft3_L.._M.._K.. with
     "design": "dct3" / "fft3" and final_t_max in the parameters, so a two-stage
-    sweep never resumes them."""
+    sweep never resumes them.  design="dct" with K=2 is the real K = 2 (BPSK)
+    modulated SPARC on the DCT design (pipeline.DctBpskConcatPipeline, either
+    precision): a section carries log2 M + 1 bits, the noise is real (the
+    factor 2 stays), and its checkpoints live under concat_dct_k2_L.. with
+    "design": "dct_k2" and "K": 2.  Known sections are not built for K = 2,
+    so final_amp=True raises ValueError there."""
     from .ldpc import code
     if design not in ("dense", "dct", "fft"):
         raise ValueError(f"design must be 'dense', 'dct' or 'fft', not {design!r}")
     if final_amp and design == "dense":
         raise ValueError("final_amp needs the DCT or FFT design: design='dct' or 'fft'")
     ftm = int(t_max if final_t_max is None else final_t_max)
-    key = design + "3" if final_amp else design  # what names the campaign in checkpoint tag and parameters
     K = int(K)
-    if design != "fft" and K != 1:
-        raise ValueError("K-PSK modulation needs the complex design: design='fft'")
+    bpsk = design == "dct" and K == 2  # real K = 2 modulated sections on the DCT design
+    if design != "fft" and K != 1 and not bpsk:
+        raise ValueError("K-PSK modulation needs the complex design: design='fft' (design='dct' takes K = 1 or the "
+                         "real K = 2)")
+    if bpsk and final_amp:
+        raise ValueError("final_amp with K = 2 on the DCT design: known sections for K = 2 are not built")
+    # what names the campaign in checkpoint tag and parameters
+    key = "dct_k2" if bpsk else design + "3" if final_amp else design
     agg = agg or Aggregator()
     logM = int(np.log2(M))
-    per = logM + (int(round(np.log2(K))) if design == "fft" else 0)
+    per = logM + (int(round(np.log2(K))) if design == "fft" or bpsk else 0)
     user_bits = L_unprotected * per + mults * code(*ldpc).K
     r_overall = user_bits / n
     if design == "fft":  # complex samples: N0 = awgn_var
@@ -572,8 +583,8 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
     else:
         vars_ = [P / (2 * r_overall * 10 ** (e / 10)) for e in ebn0_db]
     if trial is None:
-        from .pipeline import (ConcatPipeline, CsparcConcat3Pipeline, CsparcConcatPipeline, DctConcat3Pipeline,
-                               DctConcatPipeline)
+        from .pipeline import (ConcatPipeline, CsparcConcat3Pipeline, CsparcConcatPipeline, DctBpskConcatPipeline,
+                               DctConcat3Pipeline, DctConcatPipeline)
         if design == "fft" and final_amp:
             pipe = CsparcConcat3Pipeline(L, M, K, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed,
                                          precision=precision, t_max=t_max, bp_its=bp_its, final_t_max=ftm)
@@ -584,7 +595,7 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
             pipe = DctConcat3Pipeline(L, M, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed,
                                       precision=precision, t_max=t_max, bp_its=bp_its, final_t_max=ftm)
         else:
-            make = DctConcatPipeline if design == "dct" else ConcatPipeline
+            make = DctBpskConcatPipeline if bpsk else DctConcatPipeline if design == "dct" else ConcatPipeline
             pipe = make(L, M, n, P, L_unprotected, mults, ldpc=ldpc, design_seed=design_seed, precision=precision,
                         t_max=t_max, bp_its=bp_its)
         trial = ConcatTrial(pipe, vars_, seed, rng, granule)
@@ -605,7 +616,7 @@ def concat_ber_sweep(L, M, n, P, L_unprotected, mults, ebn0_db, *, codewords, bl
             params["design"] = key
         if final_amp:
             params["final_t_max"] = ftm
-        if design == "fft":
+        if design == "fft" or bpsk:
             params["K"] = K
         if granule is not None:
             params["granule"] = int(granule)

@@ -53,7 +53,7 @@ class ConcatPipeline:
         self.d_app = _native.DeviceBuffer(B * self.mults * c.N * sz)
         self.d_it = _native.DeviceBuffer(B * self.mults * 4)
         self.d_info = _native.DeviceBuffer(B * self.mults * c.K)
-        self.d_unp = _native.DeviceBuffer(max(1, B * self.L_unp * self.logM))
+        self.d_unp = _native.DeviceBuffer(max(1, B * self.L_unp * self.bits_per_section))
         self.d_cw = _native.DeviceBuffer(B * self.mults * c.N)
         self.d_cnt = _native.DeviceBuffer(5 * 8)
         self._cap = B
@@ -65,14 +65,16 @@ class ConcatPipeline:
     def make_batch(self, B, awgn_var, rng):
         """Random user bits -> LDPC blocks -> section indices; x = A beta0 on
         the GPU; y = x + AWGN (host RNG).  Leaves y, the true indices and the
-        information bits resident on the device."""
+        information bits resident on the device.  A section's index is the
+        MSB-first value of its bits_per_section bits (log2 M on the
+        unmodulated designs)."""
         self._ensure(B)
-        c, logM = self.c, self.logM
-        unp = rng.integers(0, 2, (B, self.L_unp * logM))
+        c, per = self.c, self.bits_per_section
+        unp = rng.integers(0, 2, (B, self.L_unp * per))
         info = rng.integers(0, 2, (B * self.mults, c.K))
         cw = c.encode_batch(info).reshape(B, self.mults * c.N)
-        bits = np.concatenate([unp, cw], axis=1).reshape(B, self.L, logM)
-        idx = (bits.astype(np.int64) @ (1 << np.arange(logM)[::-1])).astype(np.int32)
+        bits = np.concatenate([unp, cw], axis=1).reshape(B, self.L, per)
+        idx = (bits.astype(np.int64) @ (1 << np.arange(per)[::-1])).astype(np.int32)
         self.d_true.upload(idx)
         self.d_info.upload(info.reshape(B, -1).astype(np.uint8))
         self._encode(B)
@@ -94,18 +96,18 @@ class ConcatPipeline:
         on (seed, stream_id, b): a Monte-Carlo block keyed by (point, block) is
         the same whatever the rank count."""
         self._ensure(B)
-        c, logM, lib = self.c, self.logM, _native.lib()
+        c, per, lib = self.c, self.bits_per_section, _native.lib()
         off = _native.offset
-        nu = self.L_unp * logM
+        nu = self.L_unp * per
         if nu:
             _native.check(lib.sg_rng_bits_device(seed, stream_id, B, nu, self.d_unp.ptr, None))
-            _native.check(lib.sg_bits_to_sections_strided_device(self.d_unp.ptr, nu, B, self.L_unp, logM,
+            _native.check(lib.sg_bits_to_sections_strided_device(self.d_unp.ptr, nu, B, self.L_unp, per,
                                                                  self.d_true.ptr, self.L, None))
         _native.check(lib.sg_rng_bits_device(seed ^ self._SEED_INFO, stream_id, B * self.mults, c.K, self.d_info.ptr,
                                              None))
         c.encode_device(self.d_info.ptr, B * self.mults, self.d_cw.ptr)
         _native.check(lib.sg_bits_to_sections_strided_device(self.d_cw.ptr, self.mults * c.N, B, self.L - self.L_unp,
-                                                             logM, off(self.d_true.ptr, 4 * self.L_unp), self.L, None))
+                                                             per, off(self.d_true.ptr, 4 * self.L_unp), self.L, None))
         self._encode(B)
         _native.check(lib.sg_awgn_device(self.prec, seed, stream_id, self.d_x.ptr, B, self.n,
                                          float(np.sqrt(awgn_var)), self.d_y.ptr, None))
@@ -217,6 +219,61 @@ class DctConcatPipeline(ConcatPipeline):
     def _soft_output(self):
         _native.check(_native.lib().sg_amp_llr_device(self.plan, self.B, self.L_unp, self.L - self.L_unp,
                                                       self.mults * self.c.N, 0, self.d_llr.ptr, None))
+
+
+class DctBpskConcatPipeline(DctConcatPipeline):
+    """The concatenated scheme on a real K = 2 (BPSK) modulated SPARC with the
+    sub-sampled DCT design: a section carries log2 M location bits, MSB first,
+    and then one symbol bit (0: +1, 1: -1) -- the digits of its word
+    (location << 1) | symbol (sparc.bpsk_words) -- so bits_per_section =
+    log2 M + 1 stands where the unmodulated pipelines have logM, and d_true /
+    d_idx hold words.  The last L - L_unprotected sections hold `mults` LDPC
+    blocks.  Same methods, device buffers and counter layout as
+    ConcatPipeline, so montecarlo.ConcatTrial takes it unchanged.
+
+    `op` is a real sparc.DesignOperator over (L, M, n): flat, power-allocated
+    or spatially coupled, either precision -- every plan
+    sg_amp_decode_bpsk_device takes (M a power of two in [2, 2048]).  By
+    default the flat design W = P with the orders drawn from `design_seed`.
+
+    decode() per batch, nothing returning to the host but the five counters:
+    sg_amp_decode_bpsk_device with soft output on (its map_word gives the
+    unprotected bits) -> sg_amp_bpsk_llr_device over the protected sections
+    (bit LLRs from the joint posterior over (location, sign) of the decoder's
+    last s and tau) -> sg_ldpc_decode_device -> sg_concat_count_errors_device
+    on the words.  There is no final AMP pass for K = 2 (known sections are
+    not built for this family)."""
+
+    def __init__(self, L, M, n, P, L_unprotected, mults, ldpc=("802.11n", "1/2", 81), design_seed=0,
+                 precision="f32", t_max=25, rtol=1e-6, phi_method=1, bp_dectype="sumprod2", bp_its=200, op=None):
+        from . import sparc
+        self.K = 2
+        self._init_common(L, M, n, P, int(round(np.log2(int(M)))), 1, L_unprotected, mults, ldpc, precision, t_max,
+                          bp_dectype, bp_its)
+        self.rtol, self.phi_method = float(rtol), int(phi_method)
+        if op is None:
+            W = np.array(float(P))
+            o0, o1 = sparc.generate_ordering(W, self.n, self.L * self.M, design_seed)
+            op = sparc.DesignOperator(W, self.L, self.M, self.n, o0, o1)
+        if op.csparc or (op.L, op.M, op.n) != (self.L, self.M, self.n):
+            raise ValueError(f"op must be a real DesignOperator with L = {self.L}, M = {self.M}, n = {self.n}")
+        self.op = op
+        self.plan = op.plan(self.prec)
+        op.soft_output(True, self.prec)
+        self.graph = self.c._device_graph()
+
+    def _encode(self, B):
+        """x = A beta0 [B, n] on the device for the section words in d_true."""
+        _native.check(_native.lib().sg_amp_encode_bpsk_device(self.plan, self.d_true.ptr, B, self.d_x.ptr, None))
+
+    def _amp(self):
+        _native.check(_native.lib().sg_amp_decode_bpsk_device(
+            self.plan, self.d_y.ptr, self.B, None, self.awgn_var, self.t_max, self.rtol, self.phi_method,
+            self.d_idx.ptr, None, None, None, None))
+
+    def _soft_output(self):
+        _native.check(_native.lib().sg_amp_bpsk_llr_device(self.plan, self.B, self.L_unp, self.L - self.L_unp,
+                                                           self.mults * self.c.N, 0, self.d_llr.ptr, None))
 
 
 class DctConcat3Pipeline(DctConcatPipeline):

@@ -607,6 +607,14 @@ class DesignOperator:
             self._plans[precision] = h
         return self._plans[precision]
 
+    def soft_output(self, on=True, precision=_native.SG_F64):
+        """Make the following amp_decode_bpsk_batch calls through this
+        operator at `precision` keep their last effective observation s for
+        amp_llr_bpsk (sg_amp_bpsk_soft_output): L M reals per codeword of the
+        batch, nothing while off (the default).  The unmodulated decoders
+        need no switch (amp_llr)."""
+        _native.check(_native.lib().sg_amp_bpsk_soft_output(self.plan(precision), int(bool(on))))
+
     def __del__(self):
         for h in getattr(self, "_plans", {}).values():
             try:
@@ -819,6 +827,26 @@ def amp_llr(op, B, l0, nl, probs_only=False, precision=_native.SG_F64):
     out = np.empty((int(B), int(nl) * logM))
     _native.check(_native.lib().sg_amp_llr(op.plan(precision), int(B), int(l0), int(nl), int(bool(probs_only)),
                                            _native.ptr(out)))
+    return out
+
+
+def amp_llr_bpsk(op, B, l0, nl, probs_only=False, precision=_native.SG_F64):
+    """Soft output of the last amp_decode_bpsk_batch of B codewords through
+    `op` at this precision, decoded after op.soft_output(True, precision): for
+    sections [l0, l0 + nl) the LLRs log p - log(1 - p) of the section's
+    log2 M location bits, MSB first, and then of its symbol bit (0: +1) -- the
+    digits of its word (bpsk_words) -- with p = P(bit = 0) under the joint
+    posterior over (location, sign) whose mean is the K=2 denoiser, from each
+    codeword's last effective observation s and its tau (a codeword that
+    stopped early: those of its last iteration), clipped to
+    [1e-15, 1 - 1e-15]; with probs_only the unclipped p.  Returns float64
+    [B, nl * (log2 M + 1)] (computed in the plan's precision)."""
+    if op.csparc:
+        raise ValueError("amp_llr_bpsk needs a real DesignOperator (complex designs: camp_llr with K=2)")
+    per = int(np.log2(op.M)) + 1
+    out = np.empty((int(B), int(nl) * per))
+    _native.check(_native.lib().sg_amp_bpsk_llr(op.plan(precision), int(B), int(l0), int(nl), int(bool(probs_only)),
+                                                _native.ptr(out)))
     return out
 
 
