@@ -23,6 +23,8 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
 }
 
 // Two standard normals from one Philox output (Box-Muller on 53-bit uniforms).
+// The literal 2^53 + 1 below is not a double and reads as 2^53, so u1 = (k + 1) 2^-53 exactly: it
+// reaches 1 at k = 2^53 - 1, where r = 0 and both normals are 0.  tests/philox_ref.py defines the stream.
 __device__ __forceinline__ void philox_normal2(const uint32_t c[4], double *g0, double *g1) {
     const double u1 = ((double)(((uint64_t)c[0] << 21) ^ (c[1] >> 11)) + 1.0) * (1.0 / 9007199254740993.0);  // (0,1]
     const double u2 = (double)(((uint64_t)c[2] << 21) ^ (c[3] >> 11)) * (1.0 / 9007199254740992.0);           // [0,1)
