@@ -28,13 +28,6 @@
 namespace sg {
 
 template <typename T>
-__device__ __forceinline__ T dexp(T x);
-template <>
-__device__ __forceinline__ float dexp<float>(float x) { return __expf(x); }
-template <>
-__device__ __forceinline__ double dexp<double>(double x) { return exp(x); }
-
-template <typename T>
 __device__ __forceinline__ cx<T> big_twiddle(const AmpTables<T> &tb, int e) {
     return cmul(tb.twHi[e >> 10], tb.twLo[e & 1023]);
 }
@@ -211,7 +204,7 @@ __global__ __launch_bounds__(256) void eta_kernel(AmpTables<T> tb, AmpBufs<T> bf
 #pragma unroll
     for (int k = 0; k < EPL; ++k) {
         const int e = lane + 64 * k;
-        if (e < tb.M) { x[k] = dexp<T>(x[k] - xmax); den += x[k]; }
+        if (e < tb.M) { x[k] = fexp<T>(x[k] - xmax); den += x[k]; }
     }
     den = wave_sum(den);
     const int truth = bf.true_idx ? bf.true_idx[(size_t)cw * tb.L + l] : -1;

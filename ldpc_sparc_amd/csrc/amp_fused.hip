@@ -30,13 +30,6 @@ namespace sg {
 // round size: bit-identical results)
 constexpr int FUSED_RC = 16;
 
-template <typename T>
-__device__ __forceinline__ T rexp(T x);
-template <>
-__device__ __forceinline__ float rexp<float>(float x) { return __expf(x); }
-template <>
-__device__ __forceinline__ double rexp<double>(double x) { return exp(x); }
-
 // Exponent argument (v - m) / tau of the section softmax.  Double precision
 // follows the reference's x = s / tau, x - max(x) (sparc.py:430-431); single
 // precision multiplies by 1/tau.
@@ -179,7 +172,7 @@ __global__ __launch_bounds__(reg_s1_threads(EPT, LOG2P)) void reg_ab_stage1(RegT
             for (int i = 0; i < REG_CH; ++i)
                 if (base + i * nthr < q1) {
                     const int l = e[i] >> 16;
-                    dr[e[i] & 0xffffu] = rexp<T>(sm_arg_st<T>(v[i], sM[l], tau, inv_tau)) * sI[l];
+                    dr[e[i] & 0xffffu] = fexp<T>(sm_arg_st<T>(v[i], sM[l], tau, inv_tau)) * sI[l];
                 }
         }
     } else if (bf.mode != 0) {
@@ -445,7 +438,7 @@ __global__ __launch_bounds__(reg_s1_threads(EPT, LOG2P)) void reg_az_stage2(RegT
             if (q < qe) {
                 T b = T(0);
                 const int l = e[i] >> 16;
-                if (have_beta) b = rexp<T>(sm_arg_st<T>(v[i], sM[l], tp, inv_tp)) * sI[l];
+                if (have_beta) b = fexp<T>(sm_arg_st<T>(v[i], sM[l], tp, inv_tp)) * sI[l];
                 snv[c + i] = b + tau * dr[e[i] & 0xffffu];
             }
         }
@@ -482,7 +475,7 @@ __global__ __launch_bounds__(reg_s1_threads(EPT, LOG2P)) void reg_az_stage2(RegT
                         const bool up = v[i] > m;
                         // <= 0; -inf on the first entry, whose (S + 1) e then vanishes
                         const T dlt = up ? (m - v[i]) : (v[i] - m);
-                        const T e = rexp<T>(dlt * inv_tau);
+                        const T e = fexp<T>(dlt * inv_tau);
                         S1 = up ? (S1 + T(1)) * e : S1 + e;
                         S2 = up ? (S2 + T(1)) * (e * e) : S2 + e * e;
                         m = up ? v[i] : m;
@@ -514,7 +507,7 @@ __global__ __launch_bounds__(reg_s1_threads(EPT, LOG2P)) void reg_az_stage2(RegT
 #pragma unroll
             for (int i = 0; i < RC; ++i)
                 if (c + i < b) {
-                    T e = rexp<T>(sm_arg_st<T>(v[i], mst, tau, inv_tau));
+                    T e = fexp<T>(sm_arg_st<T>(v[i], mst, tau, inv_tau));
                     if (!seen && v[i] == m) {
                         seen = true;
                         e = T(0);
@@ -706,7 +699,7 @@ __global__ __launch_bounds__(1024) void reg_merge(RegTables<T> tb, RegBufs<T> bf
                             R1 += s1[i];
                             R2 += s2[i];
                         } else {
-                            const T f = rexp<T>(sm_arg<T>(mv[i], M, tau, inv_tau));
+                            const T f = fexp<T>(sm_arg<T>(mv[i], M, tau, inv_tau));
                             R1 += (T(1) + s1[i]) * f;
                             R2 += (T(1) + s2[i]) * (f * f);
                         }
@@ -723,7 +716,7 @@ __global__ __launch_bounds__(1024) void reg_merge(RegTables<T> tb, RegBufs<T> bf
                     if (st == M)  // the true entry is a maximum: |beta - beta0|^2 = R1^2 + R2 over (1 + R1)^2
                         e += (r1 * r1 + r2) * i2;
                     else {
-                        const double bt = (double)(rexp<T>(sm_arg<T>(st, M, tau, inv_tau)) * inv);
+                        const double bt = (double)(fexp<T>(sm_arg<T>(st, M, tau, inv_tau)) * inv);
                         e += (1.0 + r2) * i2 - 2.0 * bt + 1.0;
                     }
                 }
@@ -738,7 +731,7 @@ __global__ __launch_bounds__(1024) void reg_merge(RegTables<T> tb, RegBufs<T> bf
                     const T *p = pm + (size_t)m2 * 3 * Lb;
                     const T S = p[Lb + ll];
                     if (S > T(0)) {
-                        const T f = rexp<T>(sm_arg<T>(p[ll], M, tau, inv_tau));
+                        const T f = fexp<T>(sm_arg<T>(p[ll], M, tau, inv_tau));
                         S1 += S * f;
                         S2 += p[2 * Lb + ll] * (f * f);
                     }
@@ -749,7 +742,7 @@ __global__ __launch_bounds__(1024) void reg_merge(RegTables<T> tb, RegBufs<T> bf
                 const double ss = (double)(S2 * inv * inv);
                 double err = ss;
                 if (jt >= 0) {
-                    const double bt = (double)(rexp<T>(sm_arg<T>(s[jt], M, tau, inv_tau)) * inv);
+                    const double bt = (double)(fexp<T>(sm_arg<T>(s[jt], M, tau, inv_tau)) * inv);
                     err = ss - 2.0 * bt + 1.0;
                 }
                 a += ss;

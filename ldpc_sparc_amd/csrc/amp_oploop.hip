@@ -38,12 +38,6 @@ namespace {
 constexpr int OB = 256;  // block size of the residual, control and init kernels
 
 template <typename T>
-__device__ __forceinline__ T oexp(T x);
-template <>
-__device__ __forceinline__ float oexp<float>(float x) { return __expf(x); }
-template <>
-__device__ __forceinline__ double oexp<double>(double x) { return exp(x); }
-template <typename T>
 __device__ __forceinline__ T oexpm1(T x);
 template <>
 __device__ __forceinline__ float oexpm1<float>(float x) { return expm1f(x); }
@@ -255,7 +249,7 @@ __global__ __launch_bounds__(256) void known_section_kernel(OpLoopBufs<T> ob) {
     T den = T(0);
 #pragma unroll
     for (int i = 0; i < VMAX; ++i) {
-        x[i] = lane + 64 * i < M ? oexp<T>(x[i] - xmax) : T(0);
+        x[i] = lane + 64 * i < M ? fexp<T>(x[i] - xmax) : T(0);
         den += x[i];
     }
     den = wave_sum(den);
@@ -317,7 +311,7 @@ __global__ __launch_bounds__(256) void bpsk_section_kernel(OpLoopBufs<T> ob) {
 #pragma unroll
     for (int i = 0; i < VMAX; ++i) {
         const T a = fabs(x[i]);
-        const T e = oexp<T>(a - xm), q = -oexpm1<T>(T(-2) * a);
+        const T e = fexp<T>(a - xm), q = -oexpm1<T>(T(-2) * a);
         den += lane + 64 * i < M ? e * (T(2) - q) : T(0);
         x[i] = copysign(e * q, x[i]);
     }

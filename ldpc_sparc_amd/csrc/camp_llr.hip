@@ -14,11 +14,11 @@
 #include <algorithm>
 
 #include "camp_section.hpp"
+#include "section_bits.hpp"
 
 namespace sg {
 namespace {
 
-constexpr int LLR_HI = 5;   // location bits above the six lane bits (M <= 2048)
 constexpr int LLR_SYM = 6;  // symbol bits (K <= 64)
 
 // exponent argument of (entry x, symbol k): Re x for K = 1, else Re(x conj c_k).  The host's constellation is
@@ -27,14 +27,12 @@ __device__ __forceinline__ double llr_arg(int K, const cxd *__restrict__ c, cxd 
     return K == 1 ? x.x : x.x * c[k].x + x.y * c[k].y;
 }
 
-// One wavefront per section, lane owns entries e = lane, lane + 64, ...: two
-// passes over the section (the maximum, then the accumulation) with no
-// per-entry register arrays, so every M up to 2048 runs in the same few
-// registers.  Per lane, in double: the total, the partial sums of the location
-// bits 6 and up (over the e whose bit of e >> 6 is clear) and of the symbol
-// bits (over the k whose Gray code has the bit clear).  The six low location
-// bits are lane-masked wave sums of the lanes' totals.  Fixed xor-butterfly
-// reductions, no atomics: the output is the same bits on every run.
+// One wavefront per section, lane owns entries e = lane, lane + 64, ...  Unlike the VMAX kernels of the real
+// engines this one makes two passes over the section (the maximum, then the accumulation) and keeps no per-entry
+// register array: K exponentials per entry would not fit one, and every M up to 2048 runs in the same few
+// registers.  An entry's weight is its sum over the symbols; the location bits and the tail are
+// section_bits.hpp's (all five high bits, index e >> 6), the symbol bits are log2 K more positions: per lane the
+// sums over the k whose Gray code has the bit clear, then a wave sum each.
 // s [B][LM] natural order; tau [B][Lc] (x = s / (tau / 2)) or null (x = s).
 __global__ __launch_bounds__(256) void camp_llr_kernel(const cxd *__restrict__ sbuf, const double *__restrict__ taubuf,
                                                        int L, int Lc, int M, int K, const cxd *__restrict__ cs, int l0,
@@ -53,7 +51,8 @@ __global__ __launch_bounds__(256) void camp_llr_kernel(const cxd *__restrict__ s
         for (int k = 0; k < K; ++k) m = fmax(m, llr_arg(K, cs, x, k));
     }
     m = wave_max(m);
-    double tot = 0.0, hp[LLR_HI] = {0.0, 0.0, 0.0, 0.0, 0.0}, sp[LLR_SYM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    LaneBits<hi_bits(32)> acc;
+    double sp[LLR_SYM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int e = lane; e < M; e += 64) {
         const cxd x{s[e].x / th, s[e].y / th};
         double we = 0.0;
@@ -65,22 +64,10 @@ __global__ __launch_bounds__(256) void camp_llr_kernel(const cxd *__restrict__ s
             for (int i = 0; i < LLR_SYM; ++i)
                 if (i < logK && ((g >> (logK - 1 - i)) & 1) == 0) sp[i] += w;  // MSB first
         }
-        tot += we;
-#pragma unroll
-        for (int h = 0; h < LLR_HI; ++h)
-            if ((((e >> 6) >> h) & 1) == 0) hp[h] += we;
+        acc.add(e >> 6, we);
     }
-    const double total = wave_sum(tot);
-    double out = 0.0;
-    for (int pos = 0; pos < logM; ++pos) {
-        const int bit = logM - 1 - pos;  // MSB first
-        double p = ((lane >> bit) & 1) == 0 ? tot : 0.0;
-#pragma unroll
-        for (int h = 0; h < LLR_HI; ++h)
-            if (bit == 6 + h) p = hp[h];
-        p = wave_sum(p);
-        if (lane == pos) out = p;
-    }
+    const double total = wave_sum(acc.tot);
+    double out = location_bits(acc, logM, lane);
 #pragma unroll
     for (int i = 0; i < LLR_SYM; ++i) {
         if (i < logK) {
@@ -88,12 +75,8 @@ __global__ __launch_bounds__(256) void camp_llr_kernel(const cxd *__restrict__ s
             if (lane == logM + i) out = p;
         }
     }
-    if (lane < logM + logK) {
-        const double p = out / total;
-        const double eps = 1e-15;
-        const double pc = fmin(fmax(p, eps), 1.0 - eps);  // ldpc_bp's clip (sparc_new.py:1167)
-        llr[(size_t)cw * llr_ld + (size_t)li * (logM + logK) + lane] = probs_only ? p : log(pc) - log(1.0 - pc);
-    }
+    if (lane < logM + logK)
+        llr[(size_t)cw * llr_ld + (size_t)li * (logM + logK) + lane] = bit_out<double>(out / total, probs_only);
 }
 
 // bits_to_psk_sections_kernel (camp_campaign.hip) with row strides: codeword b's bits at bits + b * bit_stride,
@@ -143,11 +126,8 @@ int camp_launch_llr(const cxd *s, const double *tau, int B, int L, int Lc, int M
                     int nl, int llr_ld, int probs_only, double *llr, hipStream_t st) {
     if (M > 2048) return fail(SG_ERR_UNSUPPORTED, "bit LLRs of sections of M = %d > 2048 entries", M);
     if (B <= 0 || nl <= 0) return SG_OK;
-    int logM = 0, logK = 0;
-    while ((1 << logM) < M) ++logM;
-    while ((1 << logK) < K) ++logK;
     hipLaunchKernelGGL(camp_llr_kernel, dim3((nl + 3) / 4, B), dim3(256), 0, st, s, tau, L, Lc, M, K, constel, l0, nl,
-                       logM, logK, llr_ld, probs_only, llr);
+                       ilog2(M), ilog2(K), llr_ld, probs_only, llr);
     SG_HIP(hipGetLastError());
     return SG_OK;
 }

@@ -866,12 +866,29 @@ static int llr_checks(sg_amp_plan *p, int B, int l0, int nl, int llr_ld, int *lo
     SG_CHECK_ARG(p->M >= 2 && (p->M & (p->M - 1)) == 0, "section size M = %d must be a power of two >= 2", p->M);
     SG_CHECK_ARG(p->last_ran && p->last_B > 0, "no decode through this plan yet (or its state was overwritten)");
     SG_CHECK_ARG(B == p->last_B, "B = %d, but the last decode held %d codewords", B, p->last_B);
-    SG_CHECK_ARG(l0 >= 0 && nl >= 0 && l0 <= p->L && nl <= p->L - l0, "sections [%d, %d + %d) outside [0, %d]", l0, l0,
-                 nl, p->L);
-    const int logM = ilog2(p->M);
-    SG_CHECK_ARG((long long)llr_ld >= (long long)nl * logM, "llr_ld = %d < nl log2 M = %lld", llr_ld,
-                 (long long)nl * logM);
-    *logM_out = logM;
+    *logM_out = ilog2(p->M);
+    return section_range_check(p->L, l0, nl, llr_ld, *logM_out, "log2 M");
+}
+
+// The host variants: launch(d_llr, stream) fills [B][ld] values of the plan's real type on the device (nv = B ld in
+// all); out gets them as doubles.  Staging in io's own I/O buffer (not part of the decode state): doubles, then the
+// plan's reals.
+template <typename F>
+static int llr_to_host(sg_amp_plan *io, int device, int precision, size_t nv, double *out, F &&launch) {
+    if (nv == 0) return SG_OK;
+    SG_HIP(hipSetDevice(device));
+    hipStream_t s = lib_stream();
+    SG_TRY(ensure_io(io, nv * 16));
+    double *dd = io->io.at<double>();
+    if (precision == SG_F64) {
+        SG_TRY(launch(dd, s));
+    } else {
+        float *df = (float *)(dd + nv);
+        SG_TRY(launch(df, s));
+        SG_TRY(amp_launch_uncast<float>(df, dd, nv, s));
+    }
+    SG_HIP(hipMemcpyAsync(out, dd, nv * sizeof(double), hipMemcpyDeviceToHost, s));
+    SG_HIP(hipStreamSynchronize(s));
     return SG_OK;
 }
 
@@ -902,24 +919,11 @@ int sg_amp_llr(sg_amp_plan *p, int B, int l0, int nl, int probs_only, double *ou
     SG_CHECK_ARG(p && out, "null argument");
     int logM = 0;
     SG_TRY(llr_checks(p, B, l0, nl, INT32_MAX, &logM));
-    const size_t ld = (size_t)nl * logM, nv = (size_t)B * ld;
-    if (nv == 0) return SG_OK;
     const sg_amp_plan *r = p->last_ran;
-    SG_HIP(hipSetDevice(r->device));
-    hipStream_t s = lib_stream();
-    // staging in the handle's own I/O buffer (not part of the decode state): doubles, then the plan's reals
-    SG_TRY(ensure_io(p, nv * 16));
-    double *dd = p->io.at<double>();
-    if (r->precision == SG_F64) {
-        SG_TRY(llr_impl<double>(r, B, l0, nl, (int)ld, probs_only, dd, s));
-    } else {
-        float *df = (float *)(dd + nv);
-        SG_TRY(llr_impl<float>(r, B, l0, nl, (int)ld, probs_only, df, s));
-        SG_TRY(amp_launch_uncast<float>(df, dd, nv, s));
-    }
-    SG_HIP(hipMemcpyAsync(out, dd, nv * sizeof(double), hipMemcpyDeviceToHost, s));
-    SG_HIP(hipStreamSynchronize(s));
-    return SG_OK;
+    const int ld = nl * logM;  // (<= INT32_MAX: checked)
+    return llr_to_host(p, r->device, r->precision, (size_t)B * ld, out, [&](auto *d, hipStream_t s) {
+        return llr_impl(r, B, l0, nl, ld, probs_only, d, s);
+    });
 }
 
 }  // extern "C"
@@ -935,12 +939,8 @@ static int bpsk_llr_checks(const sg_amp_plan *p, int B, int l0, int nl, long lon
     SG_CHECK_ARG(p->last_bpsk_B > 0 && p->wp_skeep, "no K = 2 decode with soft output through this plan yet (or its "
                  "state was overwritten)");
     SG_CHECK_ARG(B == p->last_bpsk_B, "B = %d, but the last K = 2 decode held %d codewords", B, p->last_bpsk_B);
-    SG_CHECK_ARG(l0 >= 0 && nl >= 0 && l0 <= p->L && nl <= p->L - l0, "sections [%d, %d + %d) outside [0, %d]", l0, l0,
-                 nl, p->L);
-    const int per = ilog2(p->M) + 1;
-    SG_CHECK_ARG(llr_ld >= (long long)nl * per, "llr_ld = %lld < nl (log2 M + 1) = %lld", llr_ld, (long long)nl * per);
-    *per_out = per;
-    return SG_OK;
+    *per_out = ilog2(p->M) + 1;
+    return section_range_check(p->L, l0, nl, llr_ld, *per_out, "(log2 M + 1)");
 }
 
 template <typename T>
@@ -978,23 +978,10 @@ int sg_amp_bpsk_llr(sg_amp_plan *p, int B, int l0, int nl, int probs_only, doubl
     SG_CHECK_ARG(p && out, "null argument");
     int per = 0;
     SG_TRY(bpsk_llr_checks(p, B, l0, nl, INT32_MAX, &per));
-    const size_t ld = (size_t)nl * per, nv = (size_t)B * ld;
-    if (nv == 0) return SG_OK;
-    SG_HIP(hipSetDevice(p->device));
-    hipStream_t s = lib_stream();
-    // staging in the plan's I/O buffer (not part of the decode state): doubles, then the plan's reals
-    SG_TRY(ensure_io(p, nv * 16));
-    double *dd = p->io.at<double>();
-    if (p->precision == SG_F64) {
-        SG_TRY(bpsk_llr_impl<double>(p, B, l0, nl, (int)ld, probs_only, dd, s));
-    } else {
-        float *df = (float *)(dd + nv);
-        SG_TRY(bpsk_llr_impl<float>(p, B, l0, nl, (int)ld, probs_only, df, s));
-        SG_TRY(amp_launch_uncast<float>(df, dd, nv, s));
-    }
-    SG_HIP(hipMemcpyAsync(out, dd, nv * sizeof(double), hipMemcpyDeviceToHost, s));
-    SG_HIP(hipStreamSynchronize(s));
-    return SG_OK;
+    const int ld = nl * per;  // (<= INT32_MAX: checked)
+    return llr_to_host(p, p->device, p->precision, (size_t)B * ld, out, [&](auto *d, hipStream_t s) {
+        return bpsk_llr_impl(p, B, l0, nl, ld, probs_only, d, s);
+    });
 }
 
 // Every refusal of the integrated decoders, before anything is launched or allocated (header, sg_amp_integrated_decode_device)

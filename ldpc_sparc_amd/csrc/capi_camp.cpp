@@ -625,15 +625,10 @@ static int camp_llr_checks(sg_camp_plan *p, int B, int K, const double *constel,
     SG_CHECK_ARG(B == p->last_B, "B = %d, but the last decode held %d codewords", B, p->last_B);
     SG_CHECK_ARG(K == p->last_K, "K = %d, but the last decode ran K = %d", K, p->last_K);
     SG_CHECK_ARG(K == 1 || constel, "K > 1 needs the constellation");
-    SG_CHECK_ARG(l0 >= 0 && nl >= 0 && l0 <= p->L && nl <= p->L - l0, "sections [%d, %d + %d) outside [0, %d]", l0, l0,
-                 nl, p->L);
     SG_CHECK_ARG(p->M >= 2, "section size M = %d must be a power of two >= 2", p->M);
     if (p->M > 2048) return fail(SG_ERR_UNSUPPORTED, "bit LLRs of sections of M = %d > 2048 entries", p->M);
-    const int per = bits_per_section(p->M, K);
-    SG_CHECK_ARG(llr_ld >= (long long)nl * per, "llr_ld = %lld < nl (log2 M + log2 K) = %lld", llr_ld,
-                 (long long)nl * per);
-    *per_out = per;
-    return SG_OK;
+    *per_out = bits_per_section(p->M, K);
+    return section_range_check(p->L, l0, nl, llr_ld, *per_out, "(log2 M + log2 K)");
 }
 
 extern "C" {

@@ -91,4 +91,13 @@ static inline int set_max_lds(const void *fn, size_t lds, size_t *done) {
     return SG_OK;
 }
 
+// The section range and the row length of a soft-output call: sections [l0, l0 + nl) inside [0, L] and rows of at
+// least nl * per values (per bits per section, spelled per_name in the refusal).  Argument checks only: the callers
+// run it before anything is launched or allocated.
+static inline int section_range_check(int L, int l0, int nl, long long llr_ld, int per, const char *per_name) {
+    SG_CHECK_ARG(l0 >= 0 && nl >= 0 && l0 <= L && nl <= L - l0, "sections [%d, %d + %d) outside [0, %d]", l0, l0, nl, L);
+    SG_CHECK_ARG(llr_ld >= (long long)nl * per, "llr_ld = %lld < nl %s = %lld", llr_ld, per_name, (long long)nl * per);
+    return SG_OK;
+}
+
 }  // namespace sg

@@ -10,6 +10,7 @@
 // small designs) uses plain FMA kernels.
 #include "dense.hpp"
 #include "philox.hpp"
+#include "section_bits.hpp"
 
 namespace sg {
 
@@ -482,12 +483,6 @@ __global__ void tau2_kernel(const double *z2part, int nblk, int n, double *tau2)
 // beta = sqrt(n P_l) softmax(sqrt(n P_l) s / tau^2) per section (sparc_new.py:1058-1066,
 // per-section maximum: same value as the reference's global shift), and the
 // section's sum of beta^2.  One wavefront per section.
-template <typename T>
-__device__ __forceinline__ T dexp2(T x);
-template <>
-__device__ __forceinline__ float dexp2<float>(float x) { return __expf(x); }
-template <>
-__device__ __forceinline__ double dexp2<double>(double x) { return exp(x); }
 
 constexpr int DETA_R = 16;  // entries per lane held in registers (sections of M <= 1024)
 template <typename T>
@@ -518,7 +513,7 @@ __global__ __launch_bounds__(256) void dense_eta_kernel(DenseBufs<T> d) {
         T den = T(0);
 #pragma unroll
         for (int r = 0; r < DETA_R; ++r) {
-            x[r] = lane + 64 * r < d.M ? dexp2<T>(x[r] - mx) : T(0);
+            x[r] = lane + 64 * r < d.M ? fexp<T>(x[r] - mx) : T(0);
             den += x[r];
         }
         for (int o = 32; o > 0; o >>= 1) den += __shfl_xor(den, o, 64);
@@ -535,10 +530,10 @@ __global__ __launch_bounds__(256) void dense_eta_kernel(DenseBufs<T> d) {
         for (int j = lane; j < d.M; j += 64) mx = fmax(mx, c * (s[j] / tau2));
         for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
         T den = T(0);
-        for (int j = lane; j < d.M; j += 64) den += dexp2<T>(c * (s[j] / tau2) - mx);
+        for (int j = lane; j < d.M; j += 64) den += fexp<T>(c * (s[j] / tau2) - mx);
         for (int o = 32; o > 0; o >>= 1) den += __shfl_xor(den, o, 64);
         for (int j = lane; j < d.M; j += 64) {
-            const T v = c * (dexp2<T>(c * (s[j] / tau2) - mx) / den);
+            const T v = c * (fexp<T>(c * (s[j] / tau2) - mx) / den);
             beta[j] = v;
             sq += (double)v * (double)v;
         }
@@ -589,33 +584,28 @@ __global__ __launch_bounds__(256) void dense_map_kernel(const T *s, int B, int L
 
 // ------------------------------------------------------------------ glue
 // LLR of each (MSB-first) bit of the protected sections from the soft
-// estimate: p0 = sum over indices whose bit is 0 of beta / sqrt(n P_l),
-// clipped to [1e-15, 1 - 1e-15], LLR = log p0 - log(1 - p0) (positive => 0).
+// estimate: p0 = sum over indices whose bit is 0 of beta / sqrt(n P_l), then
+// the clip and log ratio of section_bits.hpp.  The dense pipeline's contract
+// (round_p = 0) clips the double sum itself; the DCT engines' soft output
+// (round_p = 1) the sum as probs_only returns it, rounded to T, as bit_llr.
 template <typename T>
-__global__ __launch_bounds__(256) void glue_llr_kernel(const T *beta, int B, int L, int M, int l0, int nl,
+__global__ __launch_bounds__(256) void glue_llr_kernel(const T *beta, int B, int L, int M, int logM, int l0, int nl,
                                                        double inv_snp, int llr_ld, T *llr, int probs_only,
                                                        int round_p) {
     const int lane = threadIdx.x & 63;
     const int li = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int b = blockIdx.y;
     if (li >= nl) return;
-    int logM = 0;
-    while ((1 << logM) < M) ++logM;
     const T *bs = beta + (long)b * L * M + (long)(l0 + li) * M;
     for (int pos = 0; pos < logM; ++pos) {
         const int bit = logM - 1 - pos;
         double p = 0.0;
         for (int j = lane; j < M; j += 64)
             if (((j >> bit) & 1) == 0) p += (double)bs[j] * inv_snp;
-        for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
-        if (lane == 0) {
-            const double eps = 1e-15;
-            // round_p (the DCT engines' soft output): the LLR of the probability as probs_only returns it, as
-            // reg_llr_kernel (amp_llr.hip); the dense pipeline clips the double sum
-            const double pr = round_p ? (double)(T)p : p;
-            const double pc = fmin(fmax(pr, eps), 1.0 - eps);  // ldpc_bp's clip (sparc_new.py:1167)
-            llr[(long)b * llr_ld + (long)li * logM + pos] = probs_only ? (T)p : (T)(log(pc) - log(1.0 - pc));
-        }
+        p = wave_sum(p);
+        if (lane == 0)
+            llr[(long)b * llr_ld + (long)li * logM + pos] =
+                probs_only ? (T)p : (T)clip_llr(round_p ? (double)(T)p : p);
     }
 }
 
@@ -771,8 +761,8 @@ template <typename T>
 int glue_launch_llr(const T *beta, int B, int L, int M, int l0, int nl, double inv_snp, int llr_ld, T *llr,
                     int probs_only, int round_p, hipStream_t s) {
     if (B <= 0 || nl <= 0) return SG_OK;
-    hipLaunchKernelGGL((glue_llr_kernel<T>), dim3((nl + 3) / 4, B), dim3(256), 0, s, beta, B, L, M, l0, nl, inv_snp,
-                       llr_ld, llr, probs_only, round_p);
+    hipLaunchKernelGGL((glue_llr_kernel<T>), dim3((nl + 3) / 4, B), dim3(256), 0, s, beta, B, L, M, ilog2(M), l0, nl,
+                       inv_snp, llr_ld, llr, probs_only, round_p);
     SG_HIP(hipGetLastError());
     return SG_OK;
 }

@@ -1,6 +1,6 @@
-// Device helpers shared by the kernels: 64-lane butterfly reductions, the
-// fixed-order workgroup sum, raw-buffer resources with their typed loads and
-// stores, the lane-half swap.  All __forceinline__ and free of tuning: the
+// Device helpers shared by the kernels: the exponential of the real type,
+// 64-lane butterfly reductions, the fixed-order workgroup sum, raw-buffer
+// resources with their typed loads and stores, the lane-half swap.  All __forceinline__ and free of tuning: the
 // kernels compile to the same code as with a private copy.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,6 +8,15 @@
 #include <cstdint>
 
 namespace sg {
+
+// ---- the exponential of the kernels' real type: the fast intrinsic in single
+// precision, the library function in double
+template <typename T>
+__device__ __forceinline__ T fexp(T x);
+template <>
+__device__ __forceinline__ float fexp<float>(float x) { return __expf(x); }
+template <>
+__device__ __forceinline__ double fexp<double>(double x) { return exp(x); }
 
 // ---- one wavefront (64 lanes): every lane gets the result.  (Kernels that
 // spell the butterfly out in place keep it: replaced by a call, the same

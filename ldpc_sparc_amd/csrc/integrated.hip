@@ -34,13 +34,6 @@ __device__ __forceinline__ int log2i(int M) {
 }
 
 template <typename T>
-__device__ __forceinline__ T iexp(T x);
-template <>
-__device__ __forceinline__ float iexp<float>(float x) { return __expf(x); }
-template <>
-__device__ __forceinline__ double iexp<double>(double x) { return exp(x); }
-
-template <typename T>
 __device__ __forceinline__ T ilog(T x);
 template <>
 __device__ __forceinline__ float ilog<float>(float x) { return __logf(x); }
@@ -49,7 +42,9 @@ __device__ __forceinline__ double ilog<double>(double x) { return log(x); }
 
 }  // namespace
 
-// probabilities of bit 0 -> LLRs: clip to [1e-15, 1 - 1e-15], log p - log(1 - p)
+// probabilities of bit 0 -> LLRs: clip, log p - log(1 - p).  Not bit_llr (section_bits.hpp) on purpose: this is the
+// dense loop's reference-order arithmetic, the clip and both logs in T (__logf in single precision, where the upper
+// bound rounds to 1), and the dense integrated decoders are pinned to it bit for bit.
 template <typename T>
 __global__ __launch_bounds__(256) void llr_from_probs_kernel(const T *p, size_t nn, T *llr) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < nn; i += (size_t)gridDim.x * blockDim.x) {
@@ -63,7 +58,7 @@ __global__ __launch_bounds__(256) void llr_from_probs_kernel(const T *p, size_t 
 template <typename T>
 __global__ __launch_bounds__(256) void probs_from_app_kernel(const T *app, size_t nn, T *p) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < nn; i += (size_t)gridDim.x * blockDim.x) {
-        const T e = iexp<T>(app[i]);
+        const T e = fexp<T>(app[i]);
         p[i] = e / (T(1) + e);
     }
 }

@@ -11,20 +11,13 @@
 //                          one pass for the dense loop's dense_launch_eta, glue_launch_llr, integ_launch_llr
 // Fixed-order reductions, no atomics: the same bits on every run.
 #include "dense.hpp"
-#include "device_util.hpp"
+#include "section_bits.hpp"
 
 namespace sg {
 
 namespace {
 
 constexpr int RB = 256;  // block size of the residual kernel
-
-template <typename T>
-__device__ __forceinline__ T sexp(T x);
-template <>
-__device__ __forceinline__ float sexp<float>(float x) { return __expf(x); }
-template <>
-__device__ __forceinline__ double sexp<double>(double x) { return exp(x); }
 
 }  // namespace
 
@@ -72,14 +65,11 @@ __global__ __launch_bounds__(RB) void idct_residual_kernel(const T *y, const T *
 
 // One wavefront per section, four per workgroup (the shape of reg_llr_kernel, amp_llr.hip, on natural-order
 // data): lane holds the entries j = lane + 64 i, i < VMAX; lanes >= M idle when M < 64.  ua holds u = Az(z) on
-// entry and the weighted alpha on return (each lane rewrites the entries it read).  The bit-0 marginal of a low
-// index bit (one of the six lane bits) is a wave sum of the lanes' totals over the lanes whose bit is clear, that
-// of a high bit a wave sum of per-lane partial sums over the i whose bit is clear (static indices); sums in double.
-// The LLR is that of vk0 as stored in T, clipped to [1e-15, 1 - 1e-15], both logs in double.
+// entry and the weighted alpha on return (each lane rewrites the entries it read).  vk0 is the bit-0 marginal of
+// alpha as stored in T and llr its LLR (section_bits.hpp).
 template <typename T, int VMAX>
 __global__ __launch_bounds__(256) void idct_section_kernel(T *ua, const T *beta, const double *tau, int L, int M,
                                                            int logM, double snp, T *vk0, T *llr) {
-    constexpr int NH = VMAX == 32 ? 5 : VMAX == 8 ? 3 : 0;  // index bits above the lane bits
     const int lane = threadIdx.x & 63;
     const int l = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int b = blockIdx.y;
@@ -94,56 +84,39 @@ __global__ __launch_bounds__(256) void idct_section_kernel(T *ua, const T *beta,
         v[i] = j < M ? c * ((beta[o + j] + ua[o + j] / c) / tau2) : T(-INFINITY);
         m = fmax(m, v[i]);
     }
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) m = fmax(m, __shfl_xor(m, o2, 64));
+    m = wave_max(m);
     T den = T(0);
 #pragma unroll
     for (int i = 0; i < VMAX; ++i) {
-        v[i] = lane + 64 * i < M ? sexp<T>(v[i] - m) : T(0);
+        v[i] = lane + 64 * i < M ? fexp<T>(v[i] - m) : T(0);
         den += v[i];
     }
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) den += __shfl_xor(den, o2, 64);
-    double tot = 0.0, hp[NH > 0 ? NH : 1] = {0.0};
+    den = wave_sum(den);
+    LaneBits<hi_bits(VMAX)> acc;
 #pragma unroll
     for (int i = 0; i < VMAX; ++i) {
         const int j = lane + 64 * i;
         const T a = v[i] / den;  // alpha of entry j (0 past M)
         if (j < M) ua[o + j] = c * a;
-        tot += (double)a;
-#pragma unroll
-        for (int h = 0; h < NH; ++h)
-            if (((i >> h) & 1) == 0) hp[h] += (double)a;
+        acc.add(i, (double)a);
     }
-    double out = 0.0;
-    for (int pos = 0; pos < logM; ++pos) {
-        const int bit = logM - 1 - pos;  // MSB first
-        double p = ((lane >> bit) & 1) == 0 ? tot : 0.0;
-#pragma unroll
-        for (int h = 0; h < NH; ++h)
-            if (bit == 6 + h) p = hp[h];
-#pragma unroll
-        for (int o2 = 32; o2 > 0; o2 >>= 1) p += __shfl_xor(p, o2, 64);
-        if (lane == pos) out = p;
-    }
+    const double out = location_bits(acc, logM, lane);
     if (lane < logM) {
         const size_t k = ((size_t)b * L + l) * logM + lane;
         const T pt = (T)out;
-        const double eps = 1e-15;
-        const double pc = fmin(fmax((double)pt, eps), 1.0 - eps);  // ldpc_bp's clip (sparc_new.py:1167)
         vk0[k] = pt;
-        llr[k] = (T)(log(pc) - log(1.0 - pc));
+        llr[k] = bit_llr<T>(pt);
     }
 }
 
 // app LLRs -> P(bit = 0) = exp(app) / (1 + exp(app)) (ldpc_bp, sparc_new.py:1190) written as 1 / (1 + exp(-app)):
 // the same value, and finite for every app.  probs_from_app_kernel (integrated.hip) forms exp(app) first, which in
 // single precision is inf from app = 88.8 on and gives inf / inf; the LLRs of this loop's section kernel reach
-// +-34.5 per bit (the clip at 1e-15), so a few BP iterations pass that.
+// +-34.5 per bit (the clip of clip_llr, section_bits.hpp), so a few BP iterations pass that.
 template <typename T>
 __global__ __launch_bounds__(256) void idct_probs_kernel(const T *app, size_t nn, T *p) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < nn; i += (size_t)gridDim.x * blockDim.x)
-        p[i] = T(1) / (T(1) + sexp<T>(-app[i]));
+        p[i] = T(1) / (T(1) + fexp<T>(-app[i]));
 }
 
 // every codeword active and phi = 1: what the general engine's operator kernels read (apply_impl uploads them)
@@ -173,13 +146,11 @@ int idct_launch_section(T *ua, const T *beta, const double *tau, int B, int L, i
     if (M < 2 || (1 << logM) != M || M > 2048)
         return fail(SG_ERR_UNSUPPORTED, "integrated section kernel: M = %d is not a power of two in [2, 2048]", M);
     ProfScope ps(SG_PH_ETA, s);
-    const dim3 grid((L + 3) / 4, B), block(256);
-    if (M <= 64)
-        hipLaunchKernelGGL((idct_section_kernel<T, 1>), grid, block, 0, s, ua, beta, tau, L, M, logM, snp, vk0, llr);
-    else if (M <= 512)
-        hipLaunchKernelGGL((idct_section_kernel<T, 8>), grid, block, 0, s, ua, beta, tau, L, M, logM, snp, vk0, llr);
-    else
-        hipLaunchKernelGGL((idct_section_kernel<T, 32>), grid, block, 0, s, ua, beta, tau, L, M, logM, snp, vk0, llr);
+    SG_TRY(with_vmax(M, [&](auto vmax) {
+        hipLaunchKernelGGL((idct_section_kernel<T, decltype(vmax)::value>), dim3((L + 3) / 4, B), dim3(256), 0, s, ua,
+                           beta, tau, L, M, logM, snp, vk0, llr);
+        return SG_OK;
+    }));
     SG_HIP(hipGetLastError());
     return SG_OK;
 }
