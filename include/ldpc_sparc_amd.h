@@ -449,6 +449,29 @@ int sg_amp_decode_bpsk_device(sg_amp_plan *p, const void *d_y, int B, const int3
 /* Host variant: arrays as sg_amp_decode with words in the place of indices; blocking. */
 int sg_amp_decode_bpsk(sg_amp_plan *p, const double *y, int B, const int32_t *true_word, double awgn_var, int t_max,
                        double rtol, int phi_method, int32_t *map_word, int32_t *t_final, double *nmse, double *psi);
+/* Real K = 2 AMP with known section words (amp_oploop.hip): sg_amp_decode_bpsk_device's loop in which some sections
+ * of a codeword are given, the final pass of the three-stage K = 2 decoder.  d_known_word [B][L] holds a section's
+ * word (location << 1) | symbol in [0, 2M) -- what sg_concat_known_sections_device writes at log2 M + 1 bits per
+ * section -- or -1 for a section to decode; the known set is per codeword.  The denoiser of a known section returns
+ * the +-1 one-hot of its word: +1 (symbol 0) or -1 at the location.  It adds 1 to sum beta^2, 0 to psi, and to the
+ * section's squared error against d_true_word 0 where the words agree, 4 at the same location with the opposite
+ * sign, 2 at another location, 1 without a true word.  The start is beta0 = the known one-hots, z0 = y - Ab(beta0),
+ * psi0_c = the share of unknown sections of column block c, gamma0 from psi0, no Onsager term in iteration 0;
+ * everything else is sg_amp_decode_bpsk_device's loop, and a known section reports its known word in d_map_word.
+ * With every entry -1 the outputs are sg_amp_decode_bpsk_device's, bit for bit.  Flat, power-allocated and spatially
+ * coupled W, both precisions.  Refusals as sg_amp_decode_bpsk_device, all before any launch or allocation; the device
+ * variant treats a word outside [0, 2M) as unknown.  A decode with known words keeps no soft state, whatever
+ * sg_amp_bpsk_soft_output says: s is not stored and sg_amp_bpsk_llr* refuses afterwards, until the next
+ * sg_amp_decode_bpsk*.  A codeword's results do not depend on the batch it is decoded in. */
+int sg_amp_decode_bpsk_partial_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_known_word,
+                                      const int32_t *d_true_word, double awgn_var, int t_max, double rtol,
+                                      int phi_method, int32_t *d_map_word, int32_t *d_t_final, double *d_nmse,
+                                      double *d_psi, void *stream);
+/* Host variant: arrays as sg_amp_decode_bpsk plus known_word [B][L]; blocking.  It scans known_word: an entry
+ * outside [-1, 2M) is SG_ERR_BAD_ARG naming its index, before anything is launched. */
+int sg_amp_decode_bpsk_partial(sg_amp_plan *p, const double *y, int B, const int32_t *known_word,
+                               const int32_t *true_word, double awgn_var, int t_max, double rtol, int phi_method,
+                               int32_t *map_word, int32_t *t_final, double *nmse, double *psi);
 /* x = A beta0 [B][n] on the device for section words d_word [B][L] of a real K = 2 SPARC: beta0 holds +1
  * (symbol 0) or -1 at the word's location; a word outside [0, 2M) leaves its section zero. */
 int sg_amp_encode_bpsk_device(sg_amp_plan *p, const int32_t *d_word, int B, void *d_x, void *stream);

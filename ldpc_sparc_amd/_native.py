@@ -103,6 +103,11 @@ SIGNATURES = [
     ("sg_amp_decode_bpsk_device", ct.c_int, [vp, vp, ct.c_int, vp, ct.c_double, ct.c_int, ct.c_double,
                                              ct.c_int, vp, vp, vp, vp, vp]),
     ("sg_amp_encode_bpsk_device", ct.c_int, [vp, vp, ct.c_int, vp, vp]),
+    # K = 2 with known section words (the final pass of the three-stage K = 2 decoder)
+    ("sg_amp_decode_bpsk_partial", ct.c_int, [vp, vp, ct.c_int, vp, vp, ct.c_double, ct.c_int, ct.c_double,
+                                              ct.c_int, vp, vp, vp, vp]),
+    ("sg_amp_decode_bpsk_partial_device", ct.c_int, [vp, vp, ct.c_int, vp, vp, ct.c_double, ct.c_int, ct.c_double,
+                                                     ct.c_int, vp, vp, vp, vp, vp]),
     # soft output of the K = 2 decoder
     ("sg_amp_bpsk_soft_output", ct.c_int, [vp, ct.c_int]),
     ("sg_amp_bpsk_llr_device", ct.c_int, [vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, vp, vp]),

@@ -6,10 +6,12 @@
 //   Known  AMP with known sections (sg_amp_decode_partial_device): the denoiser of a known section is the one-hot
 //          of its index, and the loop starts from beta0 = the known one-hots and z0 = y - Ab(beta0)
 //   Bpsk   real K = 2 modulated AMP (sg_amp_decode_bpsk_device): the denoiser of sparc.py:433-441 and the final
-//          decision of sparc.py:488-492; nothing is known (OpLoopBufs::known null)
+//          decision of sparc.py:488-492; with OpLoopBufs::known (sg_amp_decode_bpsk_partial_device) the denoiser of
+//          a known section is the +-1 one-hot of its word (location << 1) | symbol, and the loop starts from those
 //
-//   oploop_init_kernel      nmse = 1, psi0 = 1 or, with known sections, beta0 and psi0_c = the share of unknown
-//                           sections of column block c; gamma0_r = sum_c W_rc psi0_c / Lc
+//   oploop_init_kernel      nmse = 1, psi0 = 1 or, with known sections, beta0 (the rule's one-hots: the rule is a
+//                           kernel argument) and psi0_c = the share of unknown sections of column block c;
+//                           gamma0_r = sum_c W_rc psi0_c / Lc
 //   oploop_residual_kernel  z <- y - Ab(beta) + b_r z (t = 0: y - Ab(beta0)) and partial sums of z^2 per row block
 //   oploop_control_kernel   phase 0: phi_r (:949-955), tau_c (:958-969), zs = z / phi_r
 //                           phase 1: psi, the NMSE row, the stop decision (:976-988), then gamma_r and
@@ -18,7 +20,8 @@
 //                           error against the true index, the first-maximum argmax of s (:997) or the known index
 //   bpsk_section_kernel     s = beta + tau u, beta = eta(s / tau), sum beta^2, the squared error against the true
 //                           word's +-1 one-hot, the word (location << 1) | symbol of the first maximum of |s|; with
-//                           OpLoopBufs::s_keep it also stores s (the soft output's input, amp_bpsk_llr.hip)
+//                           OpLoopBufs::s_keep it also stores s (the soft output's input, amp_bpsk_llr.hip); a known
+//                           section keeps the +-1 one-hot of its word and reports that word (s_keep not written)
 //   known_sections_kernel   hard decisions of a BP output -> section indices, -1 where a block did not converge
 //
 // The K = 2 denoiser, with x = s / tau, a = |x| and m the section's maximum of a:
@@ -53,11 +56,14 @@ __device__ __forceinline__ double gamma_row(const double *W, const double *psi, 
 
 }  // namespace
 
-// One workgroup per codeword.  beta was zeroed by the caller.
+// One workgroup per codeword.  beta was zeroed by the caller.  A known entry is an index in [0, M) (rule Known)
+// or a word in [0, 2M) (rule Bpsk: +1 for symbol 0, -1 for symbol 1 at the word's location).
 template <typename T>
-__global__ __launch_bounds__(OB) void oploop_init_kernel(OpLoopBufs<T> ob) {
+__global__ __launch_bounds__(OB) void oploop_init_kernel(OpLoopBufs<T> ob, SectionRule rule) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int L = ob.L, Lr = ob.Lr, Lc = ob.Lc, spc = L / Lc;
+    const bool words = rule == SectionRule::Bpsk;
+    const int kend = words ? 2 * ob.M : ob.M;  // known: an entry in [0, kend)
     double *psi = ob.psi + (size_t)b * Lc;
     double *nmse = ob.nmse + (size_t)b * ob.t_max * Lc;
     for (int i = tid; i < ob.t_max * Lc; i += OB) nmse[i] = 1.0;
@@ -65,13 +71,16 @@ __global__ __launch_bounds__(OB) void oploop_init_kernel(OpLoopBufs<T> ob) {
         const int32_t *known = ob.known + (size_t)b * L;
         for (int l = tid; l < L; l += OB) {
             const int k = known[l];
-            if (k >= 0 && k < ob.M) ob.beta[(size_t)b * ob.LM + (size_t)l * ob.M + k] = T(1);
+            if (k >= 0 && k < kend) {
+                const size_t at = (size_t)b * ob.LM + (size_t)l * ob.M + (words ? k >> 1 : k);
+                ob.beta[at] = (words && (k & 1)) ? T(-1) : T(1);
+            }
         }
         for (int c = tid >> 6; c < Lc; c += OB / 64) {  // one wavefront per column block
             double unk = 0.0;
             for (int l = c * spc + lane; l < (c + 1) * spc; l += 64) {
                 const int k = known[l];
-                unk += (k >= 0 && k < ob.M) ? 0.0 : 1.0;
+                unk += (k >= 0 && k < kend) ? 0.0 : 1.0;
             }
             unk = wave_sum(unk);
             if (lane == 0) psi[c] = unk / spc;
@@ -284,6 +293,15 @@ __global__ __launch_bounds__(256) void bpsk_section_kernel(OpLoopBufs<T> ob) {
     if (l >= L || !ob.active[b]) return;
     const size_t sl = (size_t)b * L + l;
     const int truth = ob.truth ? ob.truth[sl] : -1;
+    const int k = ob.known ? ob.known[sl] : -1;
+    if (k >= 0 && k < 2 * M) {  // known: beta stays the +-1 one-hot that oploop_init_kernel wrote
+        if (lane == 0) {
+            ob.bsq[sl] = 1.0;
+            ob.err[sl] = k == truth ? 0.0 : (truth < 0 || truth >= 2 * M) ? 1.0 : (k >> 1) == (truth >> 1) ? 4.0 : 2.0;
+            ob.map[sl] = k;
+        }
+        return;
+    }
     const int tloc = truth >= 0 ? truth >> 1 : -1;
     const T tval = (truth & 1) ? T(-1) : T(1);
     const T tau = (T)ob.tau[(size_t)b * ob.Lc + l / (L / ob.Lc)];
@@ -362,9 +380,9 @@ __global__ __launch_bounds__(256) void known_sections_kernel(const T *app, const
 }
 
 template <typename T>
-int oploop_launch_init(const OpLoopBufs<T> &ob, hipStream_t s) {
+int oploop_launch_init(const OpLoopBufs<T> &ob, SectionRule rule, hipStream_t s) {
     ProfScope ps(SG_PH_CONTROL, s);
-    hipLaunchKernelGGL((oploop_init_kernel<T>), dim3(ob.B), dim3(OB), 0, s, ob);
+    hipLaunchKernelGGL((oploop_init_kernel<T>), dim3(ob.B), dim3(OB), 0, s, ob, rule);
     SG_HIP(hipGetLastError());
     return SG_OK;
 }
@@ -420,7 +438,7 @@ int part_launch_known(const T *app, const int32_t *it, int max_it, int B, int mu
 }
 
 #define SG_OPLOOP_INST(T)                                                                                     \
-    template int oploop_launch_init<T>(const OpLoopBufs<T> &, hipStream_t);                                   \
+    template int oploop_launch_init<T>(const OpLoopBufs<T> &, SectionRule, hipStream_t);                      \
     template int oploop_launch_residual<T>(const OpLoopBufs<T> &, int, hipStream_t);                          \
     template int oploop_launch_control<T>(const OpLoopBufs<T> &, int, int, hipStream_t);                      \
     template int oploop_launch_section<T>(const OpLoopBufs<T> &, SectionRule, hipStream_t);                   \

@@ -1,7 +1,7 @@
 // The operator-loop AMP decoder (oploop_impl, capi_amp.cpp): sparc_amp on the plan's operators Ab / Az over
-// natural-order vectors, for AMP with known sections (sg_amp_decode_partial) and real K = 2 modulated AMP
-// (sg_amp_decode_bpsk), and the BP -> known-sections glue of the three-stage concatenated decoder: the launch
-// interface of amp_oploop.hip.
+// natural-order vectors, for AMP with known sections (sg_amp_decode_partial), real K = 2 modulated AMP
+// (sg_amp_decode_bpsk) and K = 2 with known words (sg_amp_decode_bpsk_partial), and the BP -> known-sections glue
+// of the three-stage concatenated decoders: the launch interface of amp_oploop.hip.
 #pragma once
 #include <algorithm>
 
@@ -14,7 +14,8 @@ constexpr int PART_MAX = 32;  // most partial sums of z^2 per row block and code
 // What a section's denoiser and decision are: the only part of the loop that differs between the two families
 enum class SectionRule {
     Known,  // softmax, or the one-hot of a known index; sections are indices in [0, M)
-    Bpsk,   // the K = 2 denoiser; sections are words (location << 1) | symbol in [0, 2M)
+    Bpsk,   // the K = 2 denoiser, or the +-1 one-hot of a known word; sections are words (location << 1) | symbol
+            // in [0, 2M)
 };
 
 inline const char *rule_name(SectionRule rule) { return rule == SectionRule::Bpsk ? "K = 2" : "partial"; }
@@ -31,7 +32,8 @@ struct OpLoopBufs {
     T *s_keep;                  // [B][LM] K = 2 soft output: the section kernel's s = beta + tau u, or null (not kept)
     T *r;                       // [B][n]  Ab(beta)
     T *z, *zs;                  // [B][n]  residual, z / phi of the element's row block
-    const int32_t *known;       // [B][L] index in [0, M), anything else: unknown; null for K = 2 (nothing is known)
+    const int32_t *known;       // [B][L] rule Known: index in [0, M); rule Bpsk: word in [0, 2M); anything else:
+                                // unknown; null: nothing is known (rule Bpsk only)
     const int32_t *truth;       // [B][L] the transmitted indices or words, or null
     double *zz;                 // [B][Lr][np] partial sums of z^2
     double *bsq, *err;          // [B][L] per section: sum beta^2, sum (beta - beta0)^2
@@ -51,9 +53,10 @@ inline int part_count(int n) { return std::min(PART_MAX, std::max(1, (n + 1023) 
 inline size_t oploop_zz_count(int Lr, int Mr) { return std::max<size_t>(PART_MAX, (size_t)Lr * part_count(Mr)); }
 
 // nmse = 1, gamma0, b = 0, active = 1, t_final = 0, and psi0 = 1 or, with known sections, beta0 = their one-hots
-// and psi0 = the share of unknown sections per column block
+// and psi0 = the share of unknown sections per column block.  The rule is a kernel argument (not a field of
+// OpLoopBufs): it says whether a known entry is an index (one-hot +1) or a word (+1 / -1 at word >> 1).
 template <typename T>
-int oploop_launch_init(const OpLoopBufs<T> &ob, hipStream_t s);
+int oploop_launch_init(const OpLoopBufs<T> &ob, SectionRule rule, hipStream_t s);
 // z = y - r + b z (t = 0: y - r) with b of the element's row block, and the partial sums of z^2
 template <typename T>
 int oploop_launch_residual(const OpLoopBufs<T> &ob, int t, hipStream_t s);

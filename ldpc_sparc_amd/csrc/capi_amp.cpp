@@ -451,7 +451,8 @@ static int integ_dct_impl(sg_amp_plan *p, sg_graph *g, int mode, int N, int K, c
 }
 
 // The operator-loop decoder (amp_oploop.hip), for AMP with known sections (rule Known, d_known given) and real
-// K = 2 modulated AMP (rule Bpsk, d_known null; a.d_true then holds words): sparc_amp with the plan's operators on
+// K = 2 modulated AMP (rule Bpsk; a.d_true then holds words, and so does d_known: null for the plain decode, given
+// for the decode with known words, which keeps no soft state): sparc_amp with the plan's operators on
 // natural-order vectors, as integ_dct_impl runs them.  beta lives in the plan's [B][LM] workspace (ws_s of a
 // regular plan, ws_beta of a general one) and z / phi in ws_z, where apply_enqueue reads them without a copy; z,
 // r = Ab(beta), u = Az(z / phi), the sums of z^2 per row block and the section sums in the loop's own buffers
@@ -470,7 +471,7 @@ static int oploop_impl(sg_amp_plan *p, const DecodeArgs &a, SectionRule rule, co
     ob.beta = p->regular ? (T *)p->ws_s : (T *)p->ws_beta;
     ob.u = (T *)p->wp_u; ob.r = (T *)p->wp_r; ob.z = (T *)p->wp_z; ob.zs = (T *)p->ws_z;
     ob.known = d_known; ob.truth = a.d_true;
-    if (rule == SectionRule::Bpsk && p->bpsk_soft) ob.s_keep = (T *)p->wp_skeep;  // (partial_ensure_ws holds it)
+    if (rule == SectionRule::Bpsk && !d_known && p->bpsk_soft) ob.s_keep = (T *)p->wp_skeep;  // (partial_ensure_ws)
     ob.zz = p->wp_zz; ob.bsq = p->wp_bsq; ob.err = p->wp_err; ob.map = p->ws_argmax;
     ob.psi = p->ws_psi; ob.psi_prev = p->ws_psi_prev; ob.gamma = p->ws_gamma; ob.bco = p->ws_bco;
     ob.phi = p->ws_phi_prev; ob.tau = p->wp_tau; ob.nmse = p->ws_nmse;
@@ -480,7 +481,7 @@ static int oploop_impl(sg_amp_plan *p, const DecodeArgs &a, SectionRule rule, co
     ob.phi_method = a.phi_method;
     SG_HIP(hipMemsetAsync(ob.beta, 0, (size_t)B * p->LM * sizeof(T), s));
     if (!p->regular) SG_TRY(idct_launch_ones(p->ws_active, B, p->ws_phi, B * p->Lr, s));
-    SG_TRY(oploop_launch_init<T>(ob, s));
+    SG_TRY(oploop_launch_init<T>(ob, rule, s));
     ActivePoll poll{p, B, s, false, p->wp_active};
     for (int t = 0; t < t_max - 1; ++t) {
         SG_TRY(apply_enqueue<T>(p, 0, ob.beta, B, ob.r, s));  // r = Ab(beta) (t = 0: of the known one-hots, or of zero)
@@ -507,9 +508,10 @@ static int param_checks(double awgn_var, int t_max, double rtol, int phi_method)
     return SG_OK;
 }
 
-// Every refusal of an operator-loop decode that needs no device (header, sg_amp_decode_partial_device and
-// sg_amp_decode_bpsk_device).  The merged kernels would serve a spatially coupled W with known sections; nothing
-// holds that against a reference yet, so it stays refused.
+// Every refusal of an operator-loop decode that needs no device (header, sg_amp_decode_partial_device,
+// sg_amp_decode_bpsk_device and sg_amp_decode_bpsk_partial_device).  The K = 2 rule takes a spatially coupled W
+// with and without known words (held against tests/bpsk_partial_ref.py); the unmodulated rule with known sections
+// has no reference on such a W, so that stays refused.
 static int oploop_checks(const sg_amp_plan *p, SectionRule rule, double awgn_var, int t_max, double rtol,
                          int phi_method) {
     if (rule == SectionRule::Known && p->ndim == 2)
@@ -522,8 +524,8 @@ static int oploop_checks(const sg_amp_plan *p, SectionRule rule, double awgn_var
 }
 
 // The host side of a decode, after the entry point's refusals: y (and the known and true sections) into the plan's
-// buffers, the decode there, the results back.  No rule: decode_impl; a rule: oploop_impl with it (known_idx for
-// Known; for Bpsk true_idx and map_idx hold section words).
+// buffers, the decode there, the results back.  No rule: decode_impl; a rule: oploop_impl with it (for Bpsk
+// known_idx, true_idx and map_idx hold section words, and known_idx may be null).
 static int decode_host(sg_amp_plan *p, const double *y, int B, std::optional<SectionRule> rule,
                        const int32_t *known_idx, const int32_t *true_idx, double awgn_var, int t_max, double rtol,
                        int phi_method, int32_t *map_idx, int32_t *t_final, double *nmse, double *psi) {
@@ -610,12 +612,13 @@ static void reset_last(sg_amp_plan *p) {
     }
 }
 
-// What the four entry points of the operator-loop decoder share: every refusal that needs no buffer, then `body`
+// What the six entry points of the operator-loop decoder share: every refusal that needs no buffer, then `body`
 // on the call's stream (the host variants go on through decode_host, on the library's).  The call clears the
-// last-decode state: the loop runs in the workspace that holds a decode's final state.
+// last-decode state: the loop runs in the workspace that holds a decode's final state.  keeps_soft: a plain K = 2
+// decode (nothing known), the only one that fills s_keep.
 template <typename Body>
-static int oploop_entry(sg_amp_plan *p, SectionRule rule, int B, double awgn_var, int t_max, double rtol,
-                        int phi_method, void *stream, Body &&body) {
+static int oploop_entry(sg_amp_plan *p, SectionRule rule, bool keeps_soft, int B, double awgn_var, int t_max,
+                        double rtol, int phi_method, void *stream, Body &&body) {
     SG_TRY(ensure_device());
     SG_CHECK_ARG(p, "plan is NULL");
     reset_last(p);
@@ -623,7 +626,7 @@ static int oploop_entry(sg_amp_plan *p, SectionRule rule, int B, double awgn_var
     if (B <= 0) return SG_OK;
     SG_HIP(hipSetDevice(p->device));
     SG_TRY(body(pick_stream(stream)));
-    if (rule == SectionRule::Bpsk && p->bpsk_soft) p->last_bpsk_B = B;  // s_keep and wp_tau hold its final state
+    if (keeps_soft && p->bpsk_soft) p->last_bpsk_B = B;  // s_keep and wp_tau hold its final state
     return SG_OK;
 }
 
@@ -698,7 +701,7 @@ int sg_amp_decode(sg_amp_plan *p, const double *y, int B, const int32_t *true_id
 int sg_amp_decode_partial_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_known_idx,
                                  const int32_t *d_true_idx, double awgn_var, int t_max, double rtol, int phi_method,
                                  int32_t *d_map_idx, int32_t *d_t_final, double *d_nmse, double *d_psi, void *stream) {
-    return oploop_entry(p, SectionRule::Known, B, awgn_var, t_max, rtol, phi_method, stream, [&](hipStream_t s) {
+    return oploop_entry(p, SectionRule::Known, false, B, awgn_var, t_max, rtol, phi_method, stream, [&](hipStream_t s) {
         SG_CHECK_ARG(d_y && d_known_idx, "d_y or d_known_idx is NULL");
         const DecodeArgs a{d_y, B, d_true_idx, awgn_var, t_max, rtol, phi_method, d_map_idx, d_t_final, d_nmse, d_psi};
         return by_precision(p->precision, [&](auto t) {
@@ -710,7 +713,7 @@ int sg_amp_decode_partial_device(sg_amp_plan *p, const void *d_y, int B, const i
 int sg_amp_decode_partial(sg_amp_plan *p, const double *y, int B, const int32_t *known_idx, const int32_t *true_idx,
                           double awgn_var, int t_max, double rtol, int phi_method, int32_t *map_idx, int32_t *t_final,
                           double *nmse, double *psi) {
-    return oploop_entry(p, SectionRule::Known, B, awgn_var, t_max, rtol, phi_method, nullptr, [&](hipStream_t) {
+    return oploop_entry(p, SectionRule::Known, false, B, awgn_var, t_max, rtol, phi_method, nullptr, [&](hipStream_t) {
         SG_CHECK_ARG(y && known_idx && map_idx && t_final && nmse && psi, "null host buffer");
         for (size_t i = 0; i < (size_t)B * p->L; ++i)
             SG_CHECK_ARG(known_idx[i] >= -1 && known_idx[i] < p->M, "known_idx[%zu] = %d outside [-1, %d)", i,
@@ -723,7 +726,7 @@ int sg_amp_decode_partial(sg_amp_plan *p, const double *y, int B, const int32_t 
 int sg_amp_decode_bpsk_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_true_word, double awgn_var,
                               int t_max, double rtol, int phi_method, int32_t *d_map_word, int32_t *d_t_final,
                               double *d_nmse, double *d_psi, void *stream) {
-    return oploop_entry(p, SectionRule::Bpsk, B, awgn_var, t_max, rtol, phi_method, stream, [&](hipStream_t s) {
+    return oploop_entry(p, SectionRule::Bpsk, true, B, awgn_var, t_max, rtol, phi_method, stream, [&](hipStream_t s) {
         SG_CHECK_ARG(d_y, "d_y is NULL");
         const DecodeArgs a{d_y, B, d_true_word, awgn_var, t_max, rtol, phi_method, d_map_word, d_t_final, d_nmse,
                            d_psi};
@@ -735,9 +738,36 @@ int sg_amp_decode_bpsk_device(sg_amp_plan *p, const void *d_y, int B, const int3
 
 int sg_amp_decode_bpsk(sg_amp_plan *p, const double *y, int B, const int32_t *true_word, double awgn_var, int t_max,
                        double rtol, int phi_method, int32_t *map_word, int32_t *t_final, double *nmse, double *psi) {
-    return oploop_entry(p, SectionRule::Bpsk, B, awgn_var, t_max, rtol, phi_method, nullptr, [&](hipStream_t) {
+    return oploop_entry(p, SectionRule::Bpsk, true, B, awgn_var, t_max, rtol, phi_method, nullptr, [&](hipStream_t) {
         SG_CHECK_ARG(y && map_word && t_final && nmse && psi, "null host buffer");
         return sg::decode_host(p, y, B, SectionRule::Bpsk, nullptr, true_word, awgn_var, t_max, rtol, phi_method,
+                               map_word, t_final, nmse, psi);
+    });
+}
+
+int sg_amp_decode_bpsk_partial_device(sg_amp_plan *p, const void *d_y, int B, const int32_t *d_known_word,
+                                      const int32_t *d_true_word, double awgn_var, int t_max, double rtol,
+                                      int phi_method, int32_t *d_map_word, int32_t *d_t_final, double *d_nmse,
+                                      double *d_psi, void *stream) {
+    return oploop_entry(p, SectionRule::Bpsk, false, B, awgn_var, t_max, rtol, phi_method, stream, [&](hipStream_t s) {
+        SG_CHECK_ARG(d_y && d_known_word, "d_y or d_known_word is NULL");
+        const DecodeArgs a{d_y, B, d_true_word, awgn_var, t_max, rtol, phi_method, d_map_word, d_t_final, d_nmse,
+                           d_psi};
+        return by_precision(p->precision, [&](auto t) {
+            return oploop_impl<decltype(t)>(p, a, SectionRule::Bpsk, d_known_word, s);
+        });
+    });
+}
+
+int sg_amp_decode_bpsk_partial(sg_amp_plan *p, const double *y, int B, const int32_t *known_word,
+                               const int32_t *true_word, double awgn_var, int t_max, double rtol, int phi_method,
+                               int32_t *map_word, int32_t *t_final, double *nmse, double *psi) {
+    return oploop_entry(p, SectionRule::Bpsk, false, B, awgn_var, t_max, rtol, phi_method, nullptr, [&](hipStream_t) {
+        SG_CHECK_ARG(y && known_word && map_word && t_final && nmse && psi, "null host buffer");
+        for (size_t i = 0; i < (size_t)B * p->L; ++i)
+            SG_CHECK_ARG(known_word[i] >= -1 && known_word[i] < 2 * p->M, "known_word[%zu] = %d outside [-1, %d)", i,
+                         (int)known_word[i], 2 * p->M);
+        return sg::decode_host(p, y, B, SectionRule::Bpsk, known_word, true_word, awgn_var, t_max, rtol, phi_method,
                                map_word, t_final, nmse, psi);
     });
 }

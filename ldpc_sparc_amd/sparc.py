@@ -814,6 +814,32 @@ def amp_decode_bpsk_batch(Y, op, awgn_var, t_max, rtol=1e-6, phi_est_method=1, t
     return map_word, t_final, nmse, psi
 
 
+def amp_decode_bpsk_partial_batch(Y, op, known_word, awgn_var, t_max, rtol=1e-6, phi_est_method=1, true_word=None,
+                                  precision=_native.SG_F64):
+    """amp_decode_bpsk_batch with some sections of each codeword given:
+    known_word [B, L] holds a section's word (bpsk_words) in [0, 2M), or -1
+    for a section to decode (the set is per codeword).  A known section's
+    estimate is the +-1 one-hot of its word from the start, the residual
+    starts at y - A beta_known, and the state evolution starts at the share of
+    unknown sections; map_word reports the known word there.  With every entry
+    -1 this is amp_decode_bpsk_batch, bit for bit.  Flat, power-allocated and
+    spatially coupled DCT designs, M a power of two in [2, 2048], either
+    precision.  It keeps no soft output: amp_llr_bpsk refuses after it.  Same
+    returns: (map_word [B, L], t_final [B], nmse [B, t_max, Lc], psi [B, Lc])."""
+    if op.csparc:
+        raise ValueError("amp_decode_bpsk_partial_batch needs a real DesignOperator (complex designs: "
+                         "camp_decode_partial_batch with K=2)")
+    Y, B = _received_words(Y, op, np.float64)
+    known = _known_sections(known_word, "known_word", B, op)
+    tw = None if true_word is None else _true_sections(true_word, B, op)
+    map_word, t_final, nmse, psi = _decode_outputs(B, op, t_max)
+    _native.check(_native.lib().sg_amp_decode_bpsk_partial(
+        op.plan(precision), _native.ptr(Y), B, _native.ptr(known), _native.ptr(tw), float(awgn_var), int(t_max),
+        float(rtol), int(phi_est_method), _native.ptr(map_word), _native.ptr(t_final), _native.ptr(nmse),
+        _native.ptr(psi)))
+    return map_word, t_final, nmse, psi
+
+
 def amp_llr(op, B, l0, nl, probs_only=False, precision=_native.SG_F64):
     """Soft output of the last amp_decode_batch of B codewords through `op` at
     this precision: for sections [l0, l0 + nl), the LLRs log p - log(1 - p) of
